@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- fused poses/sec of the GPS<->SLAM fusion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5] [--fit-rows reference|all] [--no-cpu-baseline] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5] [--fit-rows reference|all] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extra] [--no-other-rows]]
 
 A "step" is one pass of the hot path over one batch of synthetic, HBM-resident trajectories: one launch of the fused
 pipeline kernel (Umeyama fit -> Sim3 of pose 0 -> EKF predict/update + per-outage RTS), i.e. steps 3-5 of the reference's
 main_process_gui (EKFGPSSLAM.py:1002-1010) for every trajectory of the batch.  The rows of the fit are the ones main_process_gui
 hands to its fit (--fit-rows reference, the default: first gap-free segment of the valid rows, <= 180 s, two fall-backs; ref :973-998)
-or every valid row (--fit-rows all, the operator of rounds 1-3); the line reports both.
+or every valid row (--fit-rows all, the operator of rounds 1-3); a --full line reports both.
 Workloads (BASELINE.json configs):
   c2 (default, configs[1]) 1k synthetic KITTI-04-length (271-pose) trajectories per GPU
   c3 (configs[2])          100k synthetic 1k-pose trajectories per GPU (HBM-bound regime)
@@ -16,9 +17,11 @@ Workloads (BASELINE.json configs):
 N > 1: one process per GPU.  `python bench.py --gpus N` starts its own N ranks (before anything touches the GPU in the parent);
 under a launcher (torch.distributed.run: WORLD_SIZE set) it is one of the ranks.  Trajectories are sharded by contiguous id
 blocks (weak scaling: fixed per-GPU batch, no collective on the data path); the timed region is the K steps plus the ONE RCCL
-all-gather that collects the fused poses (north star / SURVEY 8e).  The collect is also reported on its own ("collect"), and a
-C5-shaped leg ("c5") reports compute-only vs compute+gather rates and per-link GB/s.
-Prints ONE JSON line on rank 0 (contract in the round brief): metric/value/unit + roofline + cpu_baseline.
+all-gather that collects the fused poses (north star / SURVEY 8e).  Under --full the collect is also reported on its own ("collect"), and
+a C5-shaped leg ("c5") reports compute-only vs compute+gather rates and per-link GB/s.
+Prints ONE JSON line on rank 0: metric/value/unit/ms_per_step + roofline.  A plain run sets up, warms up, times the K steps (and writes
+their outputs with --dump-outputs); --full adds the accuracy gate against the CPU oracle, the other row rule, the extras, the CPU
+baseline and, for N > 1, the collect report and the C5-shaped leg.
 """
 import argparse
 import glob
@@ -285,7 +288,7 @@ STALL_EXIT_CODE = 3                # a rank whose collect leg stalled has printe
 
 
 def run_c5(torch, B, D, rank, world, dev, rehearsal, traj_per_gpu, chunk_traj, N, passes=1, stall_cb=None, stall_seconds=240.0,
-           leg_budget_s=150.0, inject_stall_s=0.0, fit_rows="reference"):
+           leg_budget_s=150.0, inject_stall_s=0.0, fit_rows="reference", warmup=0, checks=True, dump_cb=None):
     import ctypes as C
     import threading
 
@@ -331,28 +334,35 @@ def run_c5(torch, B, D, rank, world, dev, rehearsal, traj_per_gpu, chunk_traj, N
                                                  B._p(batch.gps[lo:]), B._p(batch.valid[lo:]), C.byref(cfg), M, N, B._p(R[lo:]), B._p(t[lo:]), B._p(s[lo:]),
                                                  B._p(o), B._p(o[P * 3:]), B._p(status[lo:])))
 
-    # ---- compute only
+    # ---- compute only: `warmup` untimed passes over the shard, then `passes` timed ones (ms = one pass)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     with torch.cuda.stream(s_comp):
         fuse(0)
+        for _ in range(warmup):
+            for k in range(nchunk):
+                fuse(k)
         s_comp.synchronize()
         D.barrier(dev)
         ev[0].record()
-        for k in range(nchunk):
-            fuse(k)
+        for _ in range(passes):
+            for k in range(nchunk):
+                fuse(k)
         ev[1].record()
         s_comp.synchronize()
-    comp_ms = D.max_over_ranks(ev[0].elapsed_time(ev[1]), dev)
-    info["compute_only"] = {"ms": comp_ms, "poses_per_s": world * T * N / (comp_ms * 1e-3), "alg_GBps_per_gpu": T * N * ALG_BYTES_PER_POSE / comp_ms / 1e6,
+    comp_ms = D.max_over_ranks(ev[0].elapsed_time(ev[1]), dev) / passes
+    info["compute_only"] = {"ms": comp_ms, "passes": passes, "poses_per_s": world * T * N / (comp_ms * 1e-3), "alg_GBps_per_gpu": T * N * ALG_BYTES_PER_POSE / comp_ms / 1e6,
                             "hbm_frac": T * N * ALG_BYTES_PER_POSE / comp_ms / 1e6 / HBM_PEAK_GBS}
+    if dump_cb is not None and rank == 0:
+        dump_cb(out, R, t, s, status, M, T)
     local_sum = out.view(torch.int64).sum()                                # integer checksum of this rank's fused poses (exact, order-free)
-    # accuracy on device: the reference's error metric (Q15) of a sample of the fused tracks against the synthetic GNSS
-    ns = min(256, M)
-    st, _ = B.eval_errors_batch(batch.ts[:ns], out[:P * 3].view(M, N, 3)[:ns].contiguous(), batch.gps[:ns], batch.valid[:ns], 5.0)
-    info["q15_rmse_vs_gnss_m_sample_mean"] = float(st[:, 3].nanmean().item())
-    info["status_counts"] = {"had_outage": int((status & 1).ne(0).sum()), "rts_applied": int((status & 2).ne(0).sum()),
-                             "sharp_turn": int((status & 4).ne(0).sum()), "ended_in_outage": int((status & 8).ne(0).sum()),
-                             "fit_none": int(((status >> 8) & 1).ne(0).sum()), "fit_fallbacks": int(((status >> 8) & 16).ne(0).sum())}
+    if checks:
+        # accuracy on device: the reference's error metric (Q15) of a sample of the fused tracks against the synthetic GNSS
+        ns = min(256, M)
+        st, _ = B.eval_errors_batch(batch.ts[:ns], out[:P * 3].view(M, N, 3)[:ns].contiguous(), batch.gps[:ns], batch.valid[:ns], 5.0)
+        info["q15_rmse_vs_gnss_m_sample_mean"] = float(st[:, 3].nanmean().item())
+        info["status_counts"] = {"had_outage": int((status & 1).ne(0).sum()), "rts_applied": int((status & 2).ne(0).sum()),
+                                 "sharp_turn": int((status & 4).ne(0).sum()), "ended_in_outage": int((status & 8).ne(0).sum()),
+                                 "fit_none": int(((status >> 8) & 1).ne(0).sum()), "fit_fallbacks": int(((status >> 8) & 16).ne(0).sum())}
     if world == 1:
         info["checksum_int64"] = int(local_sum.item())
         del batch, out
@@ -488,6 +498,48 @@ def oracle_gate(np, torch, B, bt, pos_out, status, idx, fit_rows, R=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# --dump-outputs DIR: what the timed path handed its caller in the last step, one float64 .npy per array, trajectory-major
+# ----------------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 60_000_000       # payload of every file together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(np, torch, dirname, n_traj, doubles_per_traj, take):
+    """Writes take(idx) -- {name: tensor with one leading row per trajectory of idx} -- to dirname/<name>.npy as float64.  All trajectories
+    when they fit the budget, else a fixed sample (sorted, drawn from a generator seeded with SEED): the same files for the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    n = min(n_traj, max(1, DUMP_BUDGET_BYTES // (8 * doubles_per_traj)))
+    if n == n_traj:
+        idx, how = np.arange(n_traj), "every trajectory"
+    else:
+        idx, how = np.sort(np.random.default_rng(SEED).choice(n_traj, n, replace=False)), f"{n} trajectories drawn with numpy default_rng({SEED})"
+    arrays = take(torch.as_tensor(idx, dtype=torch.int64))
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.to(torch.float64).cpu().numpy())
+    return {"dir": dirname, "arrays": sorted(arrays), "trajectories": int(n), "of": int(n_traj), "sample": how, "dtype": "float64"}
+
+
+def dump_timed_outputs(x):
+    """c2 / c3: the fused poses, status words (and for the pipeline the Sim3 R, t, s) of this rank's shard after the K timed steps."""
+    torch, out, N = x.torch, x.out, x.N
+    torch.cuda.synchronize()
+
+    def take(idx):
+        i = idx.to(x.dev)
+        if x.time_major:                                                  # (N, 3, B) / (N, 4, B) -> (b, N, 3) / (b, N, 4)
+            a = {"pos": out.pos.index_select(2, i).permute(2, 0, 1), "quat": out.quat.index_select(2, i).permute(2, 0, 1)}
+        else:
+            a = {"pos": out.pos.index_select(0, i), "quat": out.quat.index_select(0, i)}
+        a["status"] = out.status.index_select(0, i)
+        if x.R is not None:
+            a["R"] = x.R.index_select(0, i)
+            a["t"] = x.t.index_select(0, i)
+            a["s"] = x.s.index_select(0, i)
+        return a
+    per_traj = N * 7 + 1 + (13 if x.R is not None else 0)
+    return dump_outputs(x.np, torch, x.args.dump_outputs, x.Bn, per_traj, take)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 def setup(args):
     """Process-level set-up of one rank: imports, device, process group, the library context with the run's options, the fields every
     line carries.  Returns a namespace the per-workload functions share."""
@@ -589,9 +641,24 @@ def headline_c5(x):
                                 "frac": co["hbm_frac"], "traffic": None, "traffic_note": "no PMC pass at this size", "alg_bytes_per_launch": info["chunk_trajectories"] * N * ALG_BYTES_PER_POSE,
                                 "kernel_ms": co["ms"] / info["chunks"]},
                       c5=info)
+        if x.dump_info is not None:
+            result["dump_outputs"] = x.dump_info
         print(json.dumps(result), flush=True)
+
+    def dump(out, R, t, s, status, M, T):                                  # chunk k of `out` = [pos (M,N,3) | quat (M,N,4)]
+        P = M * N
+        o = out.view(T // M, P * 7)
+        pos4, quat4 = o[:, :P * 3].view(-1, M, N, 3), o[:, P * 3:].view(-1, M, N, 4)
+
+        def take(idx):
+            i = idx.to(x.dev)
+            k, j = i // M, i % M
+            return {"pos": pos4[k, j], "quat": quat4[k, j], "status": status[i], "R": R[i], "t": t[i], "s": s[i]}
+        x.dump_info = dump_outputs(x.np, x.torch, args.dump_outputs, T, N * 7 + 14, take)
+    x.dump_info = None
     info = run_c5(x.torch, x.B, x.D, x.rank, world, x.dev, x.rehearsal, x.Bn, chunk, N, passes=max(1, x.steps), stall_cb=emit_c5,
-                  stall_seconds=args.stall_seconds, inject_stall_s=args.inject_stall, fit_rows=args.fit_rows)
+                  stall_seconds=args.stall_seconds, inject_stall_s=args.inject_stall, fit_rows=args.fit_rows, warmup=x.warmup,
+                  checks=args.full, dump_cb=dump if args.dump_outputs else None)
     emit_c5(info)
 
 
@@ -607,10 +674,10 @@ def timed_steps(x):
     f = dict(dtype=torch.float64, device=dev)
     cfg = _lib.EkfConfig.from_config(B.CONFIG)
     h, p = x.ctx.handle, B._p
-    x.R = None
+    x.R = x.t = x.s = None
     if args.kernel == "pipeline":
         R, t, s = torch.empty((Bn, 9), **f), torch.empty((Bn, 3), **f), torch.empty((Bn,), **f)
-        x.R = R
+        x.R, x.t, x.s = R, t, s
 
         def launch(h=h):
             _lib.check(L.gsf_fuse_pipeline_batch_dev(h, batch.layout, p(batch.ts), p(batch.pos), p(batch.quat), p(batch.gps), p(batch.valid),
@@ -924,22 +991,27 @@ def worker(args):
         return
     timed_steps(x)
     result = headline_result(x)
-    if x.world > 1:
-        result["collect"] = collect_report(x)
+    if x.rank == 0 and args.dump_outputs:
+        result["dump_outputs"] = dump_timed_outputs(x)
     x.partial.update(result)
-    if x.rank == 0:
-        accuracy_gate(x, result)
-    if args.kernel == "pipeline" and not args.no_other_rows:
-        result["fit_rows"] = other_rows_report(x)
-    # extras (rank 0, N=1): PCIe-inclusive rate, the HBM-regime config, the robust and the whole-run chains, the drop-in's single-run latency
-    if x.world == 1 and not args.no_extra and not x.time_major:
-        result["extra"] = extras(x.torch, x.B, x.L, x.ctx, x.batch, x.out, x.launch, x.Bn, x.N, x.dev, args)
-    x.batch = x.out = x.launch = x.collect = x.gathered = x.R = None
-    x.torch.cuda.empty_cache()
-    if x.world > 1 and not args.no_extra:
-        result["c5"] = c5_leg(x, result)
-    if x.rank == 0 and x.world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(x.B, x.N, fit_rows=args.fit_rows)
+    # everything past the headline (collect report, accuracy gate, the other row rule, extras, C5 leg, CPU baseline) only under --full
+    if args.full:
+        if x.world > 1:
+            result["collect"] = collect_report(x)
+        x.partial.update(result)
+        if x.rank == 0:
+            accuracy_gate(x, result)
+        if args.kernel == "pipeline" and not args.no_other_rows:
+            result["fit_rows"] = other_rows_report(x)
+        # extras (rank 0, N=1): PCIe-inclusive rate, the HBM-regime config, the robust and the whole-run chains, the drop-in's single-run latency
+        if x.world == 1 and not args.no_extra and not x.time_major:
+            result["extra"] = extras(x.torch, x.B, x.L, x.ctx, x.batch, x.out, x.launch, x.Bn, x.N, x.dev, args)
+        x.batch = x.out = x.launch = x.collect = x.gathered = x.R = None
+        x.torch.cuda.empty_cache()
+        if x.world > 1 and not args.no_extra:
+            result["c5"] = c5_leg(x, result)
+        if x.rank == 0 and x.world == 1 and not args.no_cpu_baseline:
+            result["cpu_baseline"] = cpu_baseline(x.B, x.N, fit_rows=args.fit_rows)
     if x.rank == 0:
         print(json.dumps(result))
     finish(x)
@@ -1405,10 +1477,16 @@ def main():
     ap.add_argument("--traj-per-gpu", type=int, default=None, help="override the workload's trajectories per GPU (c5: default 1 250 000, sized down to what fits)")
     ap.add_argument("--chunk-traj", type=int, default=None, help="c5: trajectories per chunk (default 32 768)")
     ap.add_argument("--poses", type=int, default=None, help="override the workload's poses per trajectory (counter studies: two track lengths 64 poses apart differ by exactly one chunk of the wave kernel)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-rows", action="store_true", help="do not time the other --fit-rows definition after the headline (counter passes: every launch of the run is then the headline's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the checks and the other measurements: accuracy gate vs the oracle, the other --fit-rows definition, "
+                         "extras (C3 figures, PCIe-inclusive rate, chains, C1 latency), CPU baseline; N>1: collect report and the C5 leg; c5: sample checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returned in its last step as DIR/<name>.npy (float64, trajectory-major, "
+                         "rank 0's shard; a fixed seeded sample of trajectories when all of them would exceed 60 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-other-rows", action="store_true", help="--full: do not time the other --fit-rows definition after the headline (counter passes: every launch of the run is then the headline's)")
     ap.add_argument("--no-graph", action="store_true", help="time K eager launches instead of one hipGraph replay of them")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra measurements (C3 figures, PCIe-inclusive rate, C1 latency; N>1: the C5 leg)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra measurements (C3 figures, PCIe-inclusive rate, C1 latency; N>1: the C5 leg)")
     ap.add_argument("--stall-seconds", type=float, default=240.0, help="N>1: watchdog per collect leg of the C5-shaped run (stall -> partial line, exit code 3)")
     ap.add_argument("--deadline-s", type=float, default=540.0, help="N>1: run-wide deadline; when it fires rank 0 prints what it has and every rank exits with code 3")
     ap.add_argument("--inject-stall", type=float, default=0.0, help="test hook: every collect leg of the C5-shaped run sleeps this long first")

@@ -1,5 +1,5 @@
-"""The bench.py output contract, checked on the committed sample line (profiles/rNN_bench_default_under_rocprof.json of the latest round: the default
-`python bench.py` run of make_profiles.sh on an MI355X) and on bench.py's own constants and helpers -- CPU tier, no GPU needed."""
+"""The bench.py output contract, checked on the committed sample line (profiles/rNN_bench_default_under_rocprof.json of the latest round: the
+`python bench.py --full` run of make_profiles.sh on an MI355X) and on bench.py's own constants and helpers -- CPU tier, no GPU needed."""
 import ast
 import json
 import os
@@ -97,6 +97,30 @@ def test_bench_constants():
     consts = {n.targets[0].id: ast.literal_eval(n.value) for n in tree.body
               if isinstance(n, ast.Assign) and isinstance(n.targets[0], ast.Name) and n.targets[0].id in ("ALG_BYTES_PER_POSE", "HBM_PEAK_GBS")}
     assert consts == {"ALG_BYTES_PER_POSE": 145, "HBM_PEAK_GBS": 8000.0}       # 89 B read + 56 B written; MI355X HBM3E spec
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every trajectory while the arrays fit the budget, else the same seeded sample on every run; float64 files."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    pos = torch.arange(40 * 5 * 3, dtype=torch.float64).view(40, 5, 3)
+    take = lambda idx: {"pos": pos[idx], "status": idx.to(torch.int32)}
+    assert bench.DUMP_BUDGET_BYTES + 64 * 128 <= 64_000_000           # payload + one .npy header per array stays under 64 MB
+    info = bench.dump_outputs(np, torch, str(tmp_path / "all"), 40, 16, take)
+    assert info["trajectories"] == 40 and info["sample"] == "every trajectory"
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "pos.npy"), pos.numpy())
+    assert np.load(tmp_path / "all" / "status.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8 * 16 * 7)
+    a = bench.dump_outputs(np, torch, str(tmp_path / "a"), 40, 16, take)
+    b = bench.dump_outputs(np, torch, str(tmp_path / "b"), 40, 16, take)
+    assert a["trajectories"] == 7 and a["sample"] == b["sample"]
+    ia, ib = np.load(tmp_path / "a" / "status.npy"), np.load(tmp_path / "b" / "status.npy")
+    np.testing.assert_array_equal(ia, ib)
+    assert (np.diff(ia) > 0).all() and ia.max() < 40
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "pos.npy"), pos.numpy()[ia.astype(np.int64)])
 
 
 def test_spawned_ranks_report_a_stalled_or_failed_rank(monkeypatch):

@@ -532,13 +532,45 @@ def test_two_rank_real_kernels_gathered_equals_unsharded(tmp_path):
             assert res[f"layout{layout}_{key}"] is True, (layout, key, res)
 
 
+def test_bench_plain_run_dumps_identical_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps, prints the headline line without the --full parts, and with
+    --dump-outputs writes the last step's outputs (float64, trajectory-major, under 64 MB); two runs with the same arguments write the same bits."""
+    import subprocess
+    import sys
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        res = json.loads(lines[0])
+        assert res["steps"] == 7 and res["warmup"] == 2 and res["n_gpus"] == 1
+        assert res["metric"].startswith("fused poses/sec") and res["unit"] == "fused poses/s" and res["higher_is_better"] is True and res["dtype"] == "f64"
+        poses = res["config"]["trajectories_per_gpu"] * res["config"]["poses_per_trajectory"]
+        assert abs(res["value"] - poses / (res["ms_per_step"] * 1e-3)) / res["value"] < 1e-9
+        for k in ("extra", "cpu_baseline", "gated", "fit_rows"):
+            assert k not in res, k
+        names = sorted(f.name for f in d.iterdir())
+        assert names == ["R.npy", "pos.npy", "quat.npy", "s.npy", "status.npy", "t.npy"] and res["dump_outputs"]["arrays"] == [n[:-4] for n in names]
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 2 ** 20
+        a = {n[:-4]: np.load(d / n) for n in names}
+        B_, N_ = res["config"]["trajectories_per_gpu"], res["config"]["poses_per_trajectory"]
+        assert a["pos"].shape == (B_, N_, 3) and a["quat"].shape == (B_, N_, 4) and a["R"].shape == (B_, 9) and a["status"].shape == (B_,)
+        assert all(v.dtype == np.float64 for v in a.values()) and np.isfinite(a["pos"]).mean() > 0.9
+        dumps.append(a)
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k], err_msg=k)
+
+
 def test_bench_two_ranks_self_spawned():
     """`python bench.py --gpus 2` with no launcher starts its own ranks (gloo rehearsal on the one GPU), exits 0 and prints ONE JSON
     line with the collect block (gathered blocks == every rank's own checksum) and the C5-shaped leg."""
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -562,7 +594,7 @@ def test_bench_under_the_drivers_launcher_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     port = 29600 + (os.getpid() % 300)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -583,7 +615,7 @@ def test_bench_five_ranks_rehearsal_chunked_c5_leg():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "5", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "5", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--traj-per-gpu", "512", "--chunk-traj", "128"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
@@ -605,7 +637,7 @@ def test_bench_two_ranks_stalled_collect_leg_exits_nonzero():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--inject-stall", "6", "--stall-seconds", "1.5", "--traj-per-gpu", "2048"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode != 0, "a stalled leg must not look like success"

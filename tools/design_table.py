@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Regenerates the measurement table of DESIGN.md section 5 from the committed rocprofv3 summaries (profiles/rNN_*): kernel time =
-rocprofv3's average duration of that kernel at that grid in the kernel trace of the default `python3 bench.py` run (and of
+rocprofv3's average duration of that kernel at that grid in the kernel trace of the `python3 bench.py --full` run (and of
 tools/bench_kernels.py for the auxiliary kernels), traffic = the PMC passes collected in rNN_traffic.json.  The table between the
 markers in DESIGN.md is REPLACED, so the document cannot quote a number the profiles do not hold.
 

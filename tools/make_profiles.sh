@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run on the GPU box (through gpurun) from the repo root: rocprofv3 evidence for the bench's kernels.
-#   1. kernel trace + stats of the DEFAULT bench command (python3 bench.py)
+#   1. kernel trace + stats of the full bench command (python3 bench.py --full)
 #   2. PMC passes (separate runs: gpurun forbids mixing --pmc with trace domains) for HBM traffic and issue mix
 # Outputs under gpurun_out/profiles_raw/; tools/collect_profiles.py turns them into the committed profiles/*.
 # usage: tools/make_profiles.sh            every pass;
@@ -16,7 +16,7 @@ if [ "$SECTIONS" = "all" ]; then rm -rf $OUT; fi
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if want trace; then
-rm -rf $OUT/trace_bench_default; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench_default -- python3 $R/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || echo "trace failed"
+rm -rf $OUT/trace_bench_default; timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench_default -- python3 $R/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || echo "trace failed"
 fi
 if [ "$SECTIONS" = "trace" ]; then ls $OUT/trace_bench_default; exit 0; fi
 if want main; then
@@ -37,7 +37,7 @@ for spec in "c2ekf:--kernel ekf" "c2block:--set-option block_kernel=1 --fit-rows
     rm -rf $OUT/pmc_${wl}_$n; timeout -k 10 300 rocprofv3 --pmc $p --output-format csv -d $OUT/pmc_${wl}_$n -- python3 $R/bench.py --workload c2 $fl --no-extra --no-cpu-baseline --no-other-rows --steps 3 --warmup 1 > $OUT/pmc_${wl}_$n.json 2> $OUT/pmc_${wl}_$n.err || echo "pmc $wl $n failed"
   done
 done
-rm -rf $OUT/trace_c2block; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c2block -- python3 $R/bench.py --workload c2 --set-option block_kernel=1 --fit-rows all --no-extra --no-cpu-baseline > $OUT/bench_c2block.json 2> $OUT/bench_c2block.err || echo "trace c2block failed"
+rm -rf $OUT/trace_c2block; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c2block -- python3 $R/bench.py --workload c2 --set-option block_kernel=1 --fit-rows all --full --no-extra --no-cpu-baseline > $OUT/bench_c2block.json 2> $OUT/bench_c2block.err || echo "trace c2block failed"
 ls $OUT
 fi
 if want aux; then
