@@ -76,6 +76,7 @@ class RunConfig(C.Structure):
 
 
 RUN_GPS_EMPTY, RUN_GPS_FEW, RUN_PREFILTER_UNHANDLED, RUN_SIM3_FAILED, RUN_BAD_QUAT = 1, 2, 4, 8, 16      # run_status bits of gsf_run_fusion_batch_dev
+RUN_GT_EMPTY, RUN_GT_FEW, RUN_GT_UNHANDLED, RUN_SLAM_EMPTY = 32, 64, 128, 256                          # ... and of gsf_run_fusion_ragged_dev only
 SIM3_FLAG_SATURATED = 256
 
 
@@ -125,6 +126,10 @@ SIGNATURES = {
     "gsf_gps_prefilter_auto_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.POINTER(PrefilterConfig), _vp, _vp, _vp, _vp]),
     "gsf_run_fusion_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, C.POINTER(RunConfig), _vp] + [_vp] * 18),
     "gsf_run_fusion_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, C.POINTER(RunConfig), _vp] + [_vp] * 18),
+    "gsf_run_fusion_ragged_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32,
+                                            C.POINTER(RunConfig), C.POINTER(PrefilterConfig), _vp] + [_vp] * 25),
+    "gsf_run_fusion_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RunConfig), C.POINTER(PrefilterConfig), _vp]
+                              + [_vp] * 25),
     "gsf_sim3_umeyama_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "gsf_sim3_umeyama_windows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "gsf_sim3_umeyama_windows": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),

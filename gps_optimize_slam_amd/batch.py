@@ -235,6 +235,167 @@ def run_fusion_batch(gb, mt_state, config=None, early_exit=True, skip_seconds=5.
     return r
 
 
+def _read_slam_file(path):
+    """rows of a TUM file exactly as load_slam_trajectory parses them (EKFGPSSLAM.py:110-125): (ts (n,), pos (n,3), quat (n,4))"""
+    import numpy as np
+    try:
+        data = np.loadtxt(path)
+        if data.ndim == 1:
+            data = data.reshape(1, -1)
+        if data.shape[1] != 8:
+            raise ValueError(f"expected 8 columns (ts x y z qx qy qz qw), got {data.shape[1]}")
+    except Exception as e:
+        raise ValueError(f"SLAM file {path}: {e}") from e
+    return data[:, 0].astype(float), data[:, 1:4].astype(float), data[:, 4:8].astype(float)
+
+
+def _read_gnss_file(path):
+    """rows of a GNSS text file exactly as load_gps_data reads them (EKFGPSSLAM.py:252-256): split on space, then on comma; (n, 4)"""
+    import numpy as np
+    try:
+        try:
+            raw = np.loadtxt(path, delimiter=" ")
+        except ValueError:
+            raw = np.loadtxt(path, delimiter=",")
+        if raw.ndim == 1:
+            raw = raw.reshape(1, -1)
+        if raw.shape[1] < 4:
+            raise ValueError(f"needs at least 4 columns (ts lat lon alt), got {raw.shape[1]}")
+    except Exception as e:
+        raise ValueError(f"GNSS file {path}: {e}") from e
+    return np.ascontiguousarray(raw[:, :4], dtype=np.float64)
+
+
+class RaggedGeodeticBatch:
+    """B SLAM tracks of ANY lengths with their primary GNSS logs and optional ground-truth logs, as the reference's loaders read them:
+    flat ts (P,), pos (P,3), quat (P,4) with slam_offsets (B+1,); fixes gps_t (T,), gps_llh (T,3) with gps_offsets (B+1,); ground truth
+    gt_t / gt_llh / gt_offsets (None: no track has one; an empty range: that track has none).  max_poses / max_fixes / gt_max_fixes are
+    host values that size the device workspace: the longest track / log, read here from the offsets (one small copy to the host per batch);
+    a value given that is below it raises ValueError.  Input of run_fusion_ragged()."""
+
+    def __init__(self, ts, pos, quat, slam_offsets, gps_t, gps_llh, gps_offsets, gt_t=None, gt_llh=None, gt_offsets=None, max_poses=None,
+                 max_fixes=None, gt_max_fixes=None):
+        self.ts, self.pos, self.quat, self.slam_offsets = ts, pos, quat, slam_offsets
+        self.gps_t, self.gps_llh, self.gps_offsets = gps_t, gps_llh, gps_offsets
+        self.gt_t, self.gt_llh, self.gt_offsets = gt_t, gt_llh, gt_offsets
+        self.B = int(slam_offsets.numel()) - 1
+        sizes = [self._longest(slam_offsets, max_poses, "slam_offsets", "max_poses", int(ts.numel())),
+                 self._longest(gps_offsets, max_fixes, "gps_offsets", "max_fixes", int(gps_t.numel())),
+                 (0, 0) if gt_offsets is None else self._longest(gt_offsets, gt_max_fixes, "gt_offsets", "gt_max_fixes", int(gt_t.numel()))]
+        self._ranges = tuple(lo for lo, _ in sizes)                      # the longest ranges themselves (run_fusion_ragged checks against them)
+        self.max_poses, self.max_fixes, self.gt_max_fixes = (v for _, v in sizes)
+
+    def _longest(self, offsets, given, name, size_name, rows):
+        """(longest range of `offsets`, the size to use): offsets must hold B+1 non-decreasing values from 0 to `rows`; `given` may not be below it"""
+        o = offsets.detach().to("cpu", torch.int64)
+        if o.numel() != self.B + 1:
+            raise ValueError(f"{name}: expected {self.B + 1} values, got {o.numel()}")
+        d = o[1:] - o[:-1]
+        if int(o[0]) != 0 or int(o[-1]) != rows or (d < 0).any():
+            raise ValueError(f"{name} must rise from 0 to {rows} (the rows given) without decreasing")
+        longest = int(d.max()) if d.numel() else 0
+        if given is None:
+            return longest, longest
+        if int(given) < longest:
+            raise ValueError(f"{size_name} = {int(given)} is below the longest range of {name} ({longest}): it sizes the device workspace")
+        return longest, int(given)
+
+    @staticmethod
+    def _flat(arrs, cols):
+        import numpy as np
+        counts = np.array([len(a) for a in arrs], dtype=np.int64)
+        offs = np.zeros(len(arrs) + 1, dtype=np.int64); offs[1:] = np.cumsum(counts)
+        rows = [np.asarray(a, dtype=np.float64).reshape(len(a), -1)[:, :cols] if len(a) else np.zeros((0, cols)) for a in arrs]
+        flat = np.concatenate(rows) if counts.sum() else np.zeros((0, cols))
+        return np.ascontiguousarray(flat), offs, int(counts.max(initial=0))
+
+    @classmethod
+    def from_host(cls, tracks, logs, gt_logs=None, device="cuda"):
+        """tracks: list of B (ts (n_b,), pos (n_b,3), quat (n_b,4)); logs: B arrays (m_b, >= 4) = stamp, lat, lon, alt columns of the text file
+        (ref :258); gt_logs: None, or B entries each None (no ground truth for that track) or such an array."""
+        import numpy as np
+        if len(logs) != len(tracks) or (gt_logs is not None and len(gt_logs) != len(tracks)):
+            raise ValueError("tracks, logs and gt_logs must have one entry per track")
+        rows = [np.column_stack((np.asarray(t_, np.float64).reshape(-1), np.asarray(p_, np.float64).reshape(-1, 3), np.asarray(q_, np.float64).reshape(-1, 4)))
+                for t_, p_, q_ in tracks]
+        slam, so, mp = cls._flat(rows, 8)
+        g, go, mf = cls._flat(logs, 4)
+        f = dict(dtype=torch.float64, device=device)
+        tt = lambda a: torch.as_tensor(np.ascontiguousarray(a), **f)
+        gt_t = gt_llh = gt_o = None
+        gmf = 0
+        if gt_logs is not None:
+            gl, gto, gmf = cls._flat([np.zeros((0, 4)) if l is None else l for l in gt_logs], 4)
+            gt_t, gt_llh, gt_o = tt(gl[:, 0]), tt(gl[:, 1:4]), torch.as_tensor(gto, device=device)
+        return cls(tt(slam[:, 0]), tt(slam[:, 1:4]), tt(slam[:, 4:8]), torch.as_tensor(so, device=device), tt(g[:, 0]), tt(g[:, 1:4]),
+                   torch.as_tensor(go, device=device), gt_t, gt_llh, gt_o, mp, mf, gmf)
+
+    @classmethod
+    def from_files(cls, slam_paths, gps_paths, gt_paths=None, device="cuda"):
+        """B SLAM (TUM) / GNSS / optional ground-truth GNSS files (an entry of gt_paths may be None), parsed exactly as load_slam_trajectory
+        and load_gps_data parse them; ValueError naming the file on any unreadable one, before any device work."""
+        if len(gps_paths) != len(slam_paths) or (gt_paths is not None and len(gt_paths) != len(slam_paths)):
+            raise ValueError("slam_paths, gps_paths and gt_paths must have one entry per track")
+        tracks = [_read_slam_file(p) for p in slam_paths]
+        logs = [_read_gnss_file(p) for p in gps_paths]
+        gts = None if gt_paths is None else [None if p is None else _read_gnss_file(p) for p in gt_paths]
+        return cls.from_host(tracks, logs, gts, device=device)
+
+
+def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5.0, max_windows=0, want_mask=True, projected=False):
+    """Steps 1-6 of main_process_gui (EKFGPSSLAM.py:959-1075) for the tracks of a RaggedGeodeticBatch as ONE device chain
+    (gsf_run_fusion_ragged_dev): the chain of run_fusion_batch on tracks of different lengths, plus the optional ground-truth log --
+    loaded with config['ground_truth_gps_filtering'] (:964) between the primary pre-filter and the fit, so its draws come between theirs --
+    and step 6 against it (:1035-1062).  mt_state (B, 625) as in run_fusion_batch.  projected=True: gps_llh / gt_llh hold (E, N, alt) rows
+    already; zone / south / gt_zone / gt_south are then None.  The context's ransac_early_exit is restored afterwards.
+    Returns a RunResult: per-pose fields flat over the P rows (fused.pos (P,3), fused.quat (P,4), aligned, valid, sim3_pos, inlier_mask,
+    gt_aligned, gt_valid), slam_offsets / gps_offsets / gt_offsets, gt_utm / gt_keep, err_stats (2, 3, B, 4) = {primary, ground truth} x
+    {raw SLAM, Sim3, EKF} x {count, mean, median, RMSE}, plot_ref (B,) = 0 none / 1 primary / 2 ground truth (:1064-1075), run_status."""
+    # the host-known sizes first, before any device work: below the longest track / log they would undersize the workspace
+    for v, lo, name in zip((rb.max_poses, rb.max_fixes, rb.gt_max_fixes), rb._ranges, ("max_poses", "max_fixes", "gt_max_fixes")):
+        if int(v) < lo:
+            raise ValueError(f"run_fusion_ragged: {name} = {int(v)} is below the longest range of the batch ({lo})")
+    if rb.max_poses > 28000 or rb.max_fixes > 14000 or rb.gt_max_fixes > 14000:
+        raise ValueError("run_fusion_ragged: at most 28 000 poses per track and 14 000 fixes per log")
+    g = config or CONFIG
+    ctx = context()
+    rc = _lib.RunConfig.from_config(g, skip_seconds, max_windows)
+    gtf = _lib.PrefilterConfig.from_config(g["ground_truth_gps_filtering"], max_windows)
+    B, dev = rb.B, rb.ts.device
+    P, T = int(rb.ts.numel()), int(rb.gps_t.numel())
+    has_gt = rb.gt_offsets is not None
+    Tg = int(rb.gt_t.numel()) if has_gt else 0
+    f = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    out = FusedPoses(LAYOUT_TRAJ_MAJOR, 1, P, dev)
+    out.pos, out.quat = out.pos.view(P, 3), out.quat.view(P, 4)
+    out.status = torch.empty((B,), **i32)
+    r = RunResult(fused=out, R=torch.empty((B, 9), **f), t=torch.empty((B, 3), **f), s=torch.empty((B,), **f), n_inliers=torch.empty((B,), **i32),
+                  zone=None if projected else torch.empty((B,), **i32), south=None if projected else torch.empty((B,), **i32),
+                  gps_utm=rb.gps_llh.clone() if projected else torch.empty((T, 3), **f), gps_keep=torch.empty((T,), **u8),
+                  aligned=torch.empty((P, 3), **f), valid=torch.empty((P,), **u8), sim3_pos=torch.empty((P, 3), **f),
+                  gt_zone=torch.empty((B,), **i32) if has_gt and not projected else None, gt_south=torch.empty((B,), **i32) if has_gt and not projected else None,
+                  gt_utm=(rb.gt_llh.clone() if projected else torch.empty((Tg, 3), **f)) if has_gt else None,
+                  gt_keep=torch.empty((Tg,), **u8) if has_gt else None, gt_aligned=torch.empty((P, 3), **f) if has_gt else None,
+                  gt_valid=torch.empty((P,), **u8) if has_gt else None, err_stats=torch.empty((2, 3, B, 4), **f), plot_ref=torch.empty((B,), **i32),
+                  run_status=torch.empty((B,), **i32), inlier_mask=torch.empty((P,), **u8) if want_mask else None, trial_info=torch.empty((B, 2), **i32),
+                  slam_offsets=rb.slam_offsets, gps_offsets=rb.gps_offsets, gt_offsets=rb.gt_offsets)
+    saved = ctx.options.get("ransac_early_exit", 0)
+    ctx.set_option("ransac_early_exit", 1 if early_exit else 0)
+    try:
+        check(_lib.load().gsf_run_fusion_ragged_dev(
+            ctx.handle, _p(rb.ts), _p(rb.pos), _p(rb.quat), _p(rb.slam_offsets), B, P, rb.max_poses, _p(rb.gps_t), None if projected else _p(rb.gps_llh),
+            _p(rb.gps_offsets), T, rb.max_fixes, _p(rb.gt_t) if has_gt else None, None if (projected or not has_gt) else _p(rb.gt_llh), _p(rb.gt_offsets),
+            Tg, rb.gt_max_fixes, C.byref(rc), C.byref(gtf), _p(mt_state), _p(r.R), _p(r.t), _p(r.s), _p(out.pos), _p(out.quat), _p(out.status),
+            _p(r.n_inliers), _p(r.zone), _p(r.south), _p(r.gps_utm), _p(r.gps_keep), _p(r.aligned), _p(r.valid), _p(r.sim3_pos), _p(r.gt_zone),
+            _p(r.gt_south), _p(r.gt_utm), _p(r.gt_keep), _p(r.gt_aligned), _p(r.gt_valid), _p(r.err_stats), _p(r.plot_ref), _p(r.run_status),
+            _p(r.inlier_mask), _p(r.trial_info)))
+    finally:
+        ctx.set_option("ransac_early_exit", saved)
+    return r
+
+
 class FusedPoses:
     """Fused poses of a batch.  pos and quat are views of ONE allocation `buf` = [pos | quat] (7 doubles per pose), so the
     multi-GPU collect is a single all-gather of `buf`.  `buf` may be a caller-provided slice of a larger arena."""

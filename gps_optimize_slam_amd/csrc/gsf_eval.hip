@@ -29,15 +29,20 @@ __device__ __forceinline__ double block_reduce_sum(double v, double* sh, int tid
 __global__ __launch_bounds__(EVAL_THREADS) void eval_errors_kernel(const double* __restrict__ ts, const double* __restrict__ traj,
                                                                    const double* __restrict__ gps, const uint8_t* __restrict__ valid,
                                                                    int64_t N, double skip, double* __restrict__ stats,
-                                                                   double* __restrict__ errors)
+                                                                   double* __restrict__ errors, const int64_t* __restrict__ offsets)
 {
     __shared__ double sh[EVAL_THREADS / 64];
     __shared__ double sh_med[2];
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const double* t = ts + b * N; const double* p = traj + b * N * 3; const double* g = gps + b * N * 3;
-    const uint8_t* v = valid + b * N;
-    double* e = errors + b * N;
+    int64_t base = b * N;
+    if (offsets) {                                                       // ragged batch: this track's rows and length (block-uniform)
+        base = offsets[b]; N = offsets[b + 1] - base;
+        if (N <= 0) { if (tid == 0) { stats[b * 4] = 0.0; stats[b * 4 + 1] = NAN; stats[b * 4 + 2] = NAN; stats[b * 4 + 3] = NAN; } return; }
+    }
+    const double* t = ts + base; const double* p = traj + base * 3; const double* g = gps + base * 3;
+    const uint8_t* v = valid + base;
+    double* e = errors + base;
     const double thr = t[0] + skip;                                      // :1018
     // candidate / query set: valid, finite fix, after the first `skip` seconds (:1016-1021)
     auto in_set = [&](int64_t i) { return v[i] != 0 && t[i] > thr && !(isnan(g[i * 3]) || isnan(g[i * 3 + 1]) || isnan(g[i * 3 + 2])); };
@@ -309,19 +314,25 @@ struct EvalSets { const double* traj[3]; };
 __global__ __launch_bounds__(EVAL_THREADS) void eval_errors_lds_kernel(const double* __restrict__ ts, EvalSets sets,
                                                                        const double* __restrict__ gps, const uint8_t* __restrict__ valid,
                                                                        int64_t N, double skip, double* __restrict__ stats,
-                                                                       double* __restrict__ errors)
+                                                                       double* __restrict__ errors, const int64_t* __restrict__ offsets)
 {
     const double* __restrict__ traj = sets.traj[blockIdx.y];
-    stats += (int64_t)blockIdx.y * gridDim.x * 4; errors += (int64_t)blockIdx.y * gridDim.x * N;
+    // (offsets: a ragged batch -- trajectory b = rows offsets[b] .. offsets[b + 1], the LDS sized for the longest; set k's errors start at k * offsets[B])
+    stats += (int64_t)blockIdx.y * gridDim.x * 4; errors += (int64_t)blockIdx.y * (offsets ? offsets[gridDim.x] : gridDim.x * N);
     extern __shared__ double dynl[];                                     // cx[N], cy[N], cz[N], err[N], then int32 qidx[N]
     __shared__ double sh[EVAL_THREADS / 64];
     __shared__ double sh_med[2];
     __shared__ int sh_cnt[EVAL_THREADS / 64 + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = (int)N;
     const int64_t b = blockIdx.x;
-    const double* t = ts + b * N; const double* p = traj + b * N * 3; const double* g = gps + b * N * 3;
-    const uint8_t* v = valid + b * N;
-    double* e = errors + b * N;
+    int64_t row0 = b * N;
+    if (offsets) {
+        row0 = offsets[b]; N = offsets[b + 1] - row0;
+        if (N <= 0) { if (threadIdx.x == 0) { stats[b * 4] = 0.0; stats[b * 4 + 1] = NAN; stats[b * 4 + 2] = NAN; stats[b * 4 + 3] = NAN; } return; }
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = (int)N;
+    const double* t = ts + row0; const double* p = traj + row0 * 3; const double* g = gps + row0 * 3;
+    const uint8_t* v = valid + row0;
+    double* e = errors + row0;
     // long tracks (n > EVAL_PRUNE_MIN_M): the error array doubles as the sort buffer of P = next power of two >= n doubles, and a uint16 index
     // array of P entries follows qidx (pruned search below); else cx[n], cy[n], cz[n], err[n], int32 qidx[n]
     const bool long_layout = n > EVAL_PRUNE_MIN_M;
@@ -437,19 +448,24 @@ static size_t eval_lds_bytes(int64_t N)
 }
 // step 6 for the three tracks main_process_gui prints (raw SLAM, Sim3, EKF; ref :1027) against the same aligned fixes: ONE launch for tracks
 // up to EVAL_LDS_MAX_N poses; stats[3][B][4], errors[3][B][N]
+// A ragged batch (offsets) takes the kernel its LONGEST track (N) would take, the LDS sized for it: one launch whatever the mix of lengths.
+// (Splitting the batch by length would give short tracks the LDS kernel next to a long one, but needs the lengths on the host or a bucketing
+// pass; the all-pairs kernel costs a batch with a track over EVAL_LDS_MAX_N poses its O(n^2) on that track anyway.)
 int launch_eval_errors3(gsf_ctx* ctx, const double* ts, const double* traj0, const double* traj1, const double* traj2, const double* aligned_gps,
-                        const uint8_t* valid, int64_t B, int64_t N, double skip_seconds, double* stats, double* errors)
+                        const uint8_t* valid, int64_t B, int64_t N, double skip_seconds, double* stats, double* errors, const int64_t* offsets,
+                        int64_t total_rows)
 {
     if (N <= EVAL_LDS_MAX_N) {
         hipLaunchKernelGGL(eval_errors_lds_kernel, dim3((unsigned)B, 3), dim3(EVAL_THREADS), eval_lds_bytes(N), ctx->stream, ts, EvalSets{ { traj0, traj1, traj2 } },
-                           aligned_gps, valid, N, skip_seconds, stats, errors);
+                           aligned_gps, valid, N, skip_seconds, stats, errors, offsets);
         GSF_HIP(hipGetLastError());
         return GSF_OK;
     }
     const double* tr[3] = { traj0, traj1, traj2 };
+    const size_t rows = offsets ? (size_t)total_rows : (size_t)B * (size_t)N;
     for (int k = 0; k < 3; ++k) {
         hipLaunchKernelGGL(eval_errors_kernel, dim3((unsigned)B), dim3(EVAL_THREADS), 0, ctx->stream, ts, tr[k], aligned_gps, valid, N, skip_seconds,
-                           stats + (size_t)k * (size_t)B * 4, errors + (size_t)k * (size_t)B * (size_t)N);
+                           stats + (size_t)k * (size_t)B * 4, errors + (size_t)k * rows, offsets);
         GSF_HIP(hipGetLastError());
     }
     return GSF_OK;
@@ -467,9 +483,10 @@ int gsf_eval_errors_batch_dev(gsf_ctx* ctx, const double* ts, const double* traj
     GSF_HIP(hipSetDevice(ctx->device));
     if (N <= EVAL_LDS_MAX_N)
         hipLaunchKernelGGL(eval_errors_lds_kernel, dim3((unsigned)B), dim3(EVAL_THREADS), eval_lds_bytes(N), ctx->stream, ts, EvalSets{ { traj_pos, nullptr, nullptr } },
-                           aligned_gps, valid, N, skip_seconds, stats, errors);
+                           aligned_gps, valid, N, skip_seconds, stats, errors, (const int64_t*)nullptr);
     else
-        hipLaunchKernelGGL(eval_errors_kernel, dim3((unsigned)B), dim3(EVAL_THREADS), 0, ctx->stream, ts, traj_pos, aligned_gps, valid, N, skip_seconds, stats, errors);
+        hipLaunchKernelGGL(eval_errors_kernel, dim3((unsigned)B), dim3(EVAL_THREADS), 0, ctx->stream, ts, traj_pos, aligned_gps, valid, N, skip_seconds, stats, errors,
+                           (const int64_t*)nullptr);
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }

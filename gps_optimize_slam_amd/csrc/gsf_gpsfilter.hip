@@ -869,15 +869,27 @@ int gsf_gps_prefilter_chain_dev(gsf_ctx* ctx, const double* t, const double* pos
 namespace gsf {
 // the chain with the windows found ON THE DEVICE from the stamps (filter_gps_outliers_ransac as a whole, ref :136-247); counts (may be
 // NULL): log b = rows offsets[b] .. offsets[b] + counts[b]
-int launch_gps_prefilter_auto(gsf_ctx* ctx, const double* t, const double* pos, const int64_t* offsets, const int32_t* counts, int64_t B,
-                              int32_t max_log_rows, const gsf_prefilter_config* f, uint32_t* mt_state, uint8_t* keep, int32_t* log_status, int32_t* log_info)
+// what launch_gps_prefilter_auto requires of its configuration and log length, checked without launching (a chain with two pre-filters checks
+// both before the first one draws); jseq_elems / lds (may be NULL): the launch's sampler buffer and dynamic LDS
+int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems, size_t* lds)
 {
     GSF_REQUIRE(f->max_trials >= 1 && f->max_trials <= CH_MAX_TRIALS, "pre-filter max_trials must be in [1,1024]");
     GSF_REQUIRE(f->min_samples >= 1 && f->min_samples <= RP_MAX_SAMPLES, "pre-filter min_samples must be in [1,16]");
     GSF_REQUIRE(f->polynomial_degree >= 1 && f->polynomial_degree <= RP_MAX_DEGREE, "pre-filter polynomial degree must be in [1,3]");
     GSF_REQUIRE(max_log_rows >= 1 && max_log_rows <= 14000, "a log must hold 1 .. 14000 fixes for the device pre-filter");
+    int je = 0; size_t l = 0;
+    GSF_REQUIRE(chain_lds(f->max_trials, f->min_samples, max_log_rows, B, je, l) == 0, "max_trials x min_samples / log length exceed the device sampler's LDS budget");
+    if (jseq_elems) *jseq_elems = je;
+    if (lds) *lds = l;
+    return GSF_OK;
+}
+
+int launch_gps_prefilter_auto(gsf_ctx* ctx, const double* t, const double* pos, const int64_t* offsets, const int32_t* counts, int64_t B,
+                              int32_t max_log_rows, const gsf_prefilter_config* f, uint32_t* mt_state, uint8_t* keep, int32_t* log_status, int32_t* log_info)
+{
     int jseq_elems = 0; size_t lds = 0;
-    GSF_REQUIRE(chain_lds(f->max_trials, f->min_samples, max_log_rows, B, jseq_elems, lds) == 0, "max_trials x min_samples / log length exceed the device sampler's LDS budget");
+    const int rc = check_gps_prefilter(f, max_log_rows, B, &jseq_elems, &lds);
+    if (rc) return rc;
     const WinGen gen{ f->use_sliding_window ? 1 : 2, f->min_samples, f->window_duration_seconds, f->window_duration_seconds * f->window_step_factor,
                       f->enabled ? 1 : 0, f->max_windows > 0 ? f->max_windows : 4096, ctx->prefilter_first_batch, ctx->prefilter_speculate, ctx->prefilter_miss_batch };
     hipLaunchKernelGGL(gps_prefilter_chain_kernel, dim3((unsigned)B), dim3(64), lds, ctx->stream, t, pos, offsets, counts, (const int32_t*)nullptr,

@@ -109,14 +109,24 @@ int launch_ekf_block(gsf_ctx* ctx, bool pipeline, const double* ts, const double
                      int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status);
 
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
+int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);
 int launch_gps_prefilter_auto(gsf_ctx* ctx, const double* t, const double* pos, const int64_t* offsets, const int32_t* counts, int64_t B,
                               int32_t max_log_rows, const gsf_prefilter_config* f, uint32_t* mt_state, uint8_t* keep, int32_t* log_status, int32_t* log_info);
 
 // step 6 for raw SLAM / Sim3 / EKF in one launch (gsf_eval.hip): stats[3][B][4], errors[3][B][N]
 int launch_apply_sim3(gsf_ctx* ctx, const double* pos, const double* quat, const int64_t* offsets, int64_t B, const double* R, const double* t,
                       const double* s, double* pos_out, double* quat_out, int32_t* bad_quat, bool bad_quat_zeroed);
+// (offsets: a ragged batch, trajectory b = rows offsets[b] .. offsets[b + 1], N >= the longest; errors then [3][offsets[B]])
 int launch_eval_errors3(gsf_ctx* ctx, const double* ts, const double* traj0, const double* traj1, const double* traj2, const double* aligned_gps,
-                        const uint8_t* valid, int64_t B, int64_t N, double skip_seconds, double* stats, double* errors);
+                        const uint8_t* valid, int64_t B, int64_t N, double skip_seconds, double* stats, double* errors,
+                        const int64_t* offsets = nullptr, int64_t total_rows = 0);
+
+// steps 3-5 of the robust chain (gsf_robust.hip): the body of gsf_fuse_pipeline_robust_info_batch_dev; offsets == NULL: B x N rows, else
+// trajectory b = rows offsets[b] .. offsets[b + 1] of total_rows, N >= the longest (host-known: sizes the draws' LDS)
+int robust_chain(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                 const gsf_ekf_config* cfg, int64_t B, int64_t N, const int64_t* offsets, int64_t total_rows, int32_t min_samples,
+                 double residual_threshold, int32_t max_trials, int32_t min_inliers_needed, uint32_t* mt_state, double* R, double* t, double* s,
+                 double* pos_out, double* quat_out, int32_t* status, int32_t* n_inliers, uint8_t* inlier_mask, int32_t* trial_info);
 
 // main_process_gui's row choice as a launch of its own (gsf_robust.hip: sim3_rows_kernel; ref :973-998): row_mask[B*N] / ragged, n_rows[B], status[B]
 int launch_sim3_rows(gsf_ctx* ctx, const double* ts, const double* gps, const uint8_t* valid, const int64_t* offsets, int64_t B, int64_t N,
@@ -159,7 +169,7 @@ public:
 
 private:
     struct Out { void* host; size_t off, bytes; };
-    static constexpr int MAX_OUT = 24;
+    static constexpr int MAX_OUT = 32;
     void* take(size_t bytes, size_t& at);
     void* in_bytes(const void* host, size_t bytes);
     void* out_bytes(void* host, size_t bytes);

@@ -14,7 +14,8 @@ using namespace gsf;
 
 namespace {
 
-// (optional, the robust chain: fixed-stride trajectories) the chosen rows compacted into slot [b*N, b*N + n_b) by the same pass that marks them --
+// (optional, the robust chain) the chosen rows compacted into slot [base_b, base_b + n_b) -- base_b = b*N, or offsets[b] for a ragged batch -- by the
+// same pass that marks them --
 // what compact_valid_kernel does from the mask, without the mask's trip through memory and without its launch
 struct RowsCompact { const double* pos; double* src; double* dst; int32_t* rowmap; int32_t* counts; int64_t* offsets; int64_t B; };
 
@@ -125,25 +126,28 @@ __global__ __launch_bounds__(64) void sim3_rows_kernel(const double* __restrict_
     }
     if (lane == 0) {
         n_rows[b] = count; if (status) status[b] = flag;
-        if (cp.src) { cp.counts[b] = total; cp.offsets[b] = base; if (b == cp.B - 1) cp.offsets[cp.B] = cp.B * N; }
+        if (cp.src) { cp.counts[b] = total; cp.offsets[b] = base; if (b == cp.B - 1) cp.offsets[cp.B] = offsets ? offsets[cp.B] : cp.B * N; }
     }
 }
 
 // one wave per trajectory: stable compaction of the rows with valid, finite GNSS -- or, under the reference's row choice, of the rows
-// `rowsel` marks -- into slot [b*N, b*N + n_b)
+// `rowsel` marks -- into slot [base_b, base_b + n_b) (base_b = b*N, or slam_offsets[b] for a ragged batch)
 __global__ __launch_bounds__(64) void compact_valid_kernel(const double* __restrict__ pos, const double* __restrict__ gps, const uint8_t* __restrict__ valid,
                                                            const uint8_t* __restrict__ rowsel,
                                                            int64_t B, int64_t N, double* __restrict__ src, double* __restrict__ dst,
-                                                           int32_t* __restrict__ rowmap, int32_t* __restrict__ counts, int64_t* __restrict__ offsets)
+                                                           int32_t* __restrict__ rowmap, int32_t* __restrict__ counts, int64_t* __restrict__ offsets,
+                                                           const int64_t* __restrict__ slam_offsets)
 {
     const int lane = threadIdx.x;
-    const int64_t b = blockIdx.x, base = b * N;
+    const int64_t b = blockIdx.x;
+    int64_t base = b * N, nt = N;
+    if (slam_offsets) { base = uniform64(slam_offsets[b]); nt = uniform64(slam_offsets[b + 1]) - base; }
     int n = 0;
-    for (int64_t c0 = 0; c0 < N; c0 += 64) {
+    for (int64_t c0 = 0; c0 < nt; c0 += 64) {
         const int64_t i = c0 + lane;
         bool ok = false;
         double z0 = 0, z1 = 0, z2 = 0;
-        if (i < N) {
+        if (i < nt) {
             z0 = gps[(base + i) * 3]; z1 = gps[(base + i) * 3 + 1]; z2 = gps[(base + i) * 3 + 2];
             ok = rowsel ? rowsel[base + i] != 0 : (valid[base + i] != 0 && !(isnan(z0) || isnan(z1) || isnan(z2)));
         }
@@ -157,7 +161,7 @@ __global__ __launch_bounds__(64) void compact_valid_kernel(const double* __restr
         }
         n += __popcll(m);
     }
-    if (lane == 0) { counts[b] = n; offsets[b] = base; if (b == B - 1) offsets[B] = B * N; }
+    if (lane == 0) { counts[b] = n; offsets[b] = base; if (b == B - 1) offsets[B] = slam_offsets ? slam_offsets[B] : B * N; }
 }
 
 
@@ -319,19 +323,23 @@ __global__ __launch_bounds__(64) void robust_probe_kernel(uint32_t* __restrict__
 }
 
 // lane per trajectory: Sim3 of pose 0 (transform_trajectory row 0, ref :464-466)
+// (slam_offsets: a ragged batch, pose 0 of trajectory b is row slam_offsets[b]; an empty trajectory has no pose 0 and its fit is None)
 __global__ __launch_bounds__(64) void robust_init_pose_kernel(const double* __restrict__ pos, const double* __restrict__ quat, int64_t B, int64_t N,
                                                               const double* __restrict__ R, const double* __restrict__ t, const double* __restrict__ s,
                                                               const int32_t* __restrict__ fit, double* __restrict__ init_pos, double* __restrict__ init_quat,
-                                                              int32_t* __restrict__ fail)
+                                                              int32_t* __restrict__ fail, const int64_t* __restrict__ slam_offsets)
 {
     const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    Quat qn; const bool qok = quat_unit(Quat{ quat[b * N * 4], quat[b * N * 4 + 1], quat[b * N * 4 + 2], quat[b * N * 4 + 3] }, qn);
-    const bool none = (fit[b] & 1) != 0;
+    int64_t r0 = b * N;
+    bool empty = false;
+    if (slam_offsets) { r0 = slam_offsets[b]; empty = slam_offsets[b + 1] <= r0; if (empty) r0 = 0; }
+    Quat qn; const bool qok = !empty && quat_unit(Quat{ quat[r0 * 4], quat[r0 * 4 + 1], quat[r0 * 4 + 2], quat[r0 * 4 + 3] }, qn);
+    const bool none = (fit[b] & 1) != 0 || empty;
     double Rb[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) Rb[k] = R[b * 9 + k];
-    const double x = pos[b * N * 3], y = pos[b * N * 3 + 1], z = pos[b * N * 3 + 2], sb = s[b];
+    const double x = empty ? 0.0 : pos[r0 * 3], y = empty ? 0.0 : pos[r0 * 3 + 1], z = empty ? 0.0 : pos[r0 * 3 + 2], sb = s[b];
     Vec3 p0{ sb * (x * Rb[0] + y * Rb[1] + z * Rb[2]) + t[b * 3], sb * (x * Rb[3] + y * Rb[4] + z * Rb[5]) + t[b * 3 + 1],
              sb * (x * Rb[6] + y * Rb[7] + z * Rb[8]) + t[b * 3 + 2] };
     Quat q0 = quat_mul(quat_from_matrix(Rb), qn);
@@ -342,15 +350,19 @@ __global__ __launch_bounds__(64) void robust_init_pose_kernel(const double* __re
 }
 
 // one wave per trajectory: status word, inlier mask in original row order, NaN rows when the fit is None / pose 0 is invalid
+// (slam_offsets: a ragged batch, trajectory b = rows slam_offsets[b] .. slam_offsets[b + 1])
 __global__ __launch_bounds__(64) void robust_finish_kernel(int64_t N, const int32_t* __restrict__ fit, const int32_t* __restrict__ fail,
                                                            const int32_t* __restrict__ rows_status, const int32_t* __restrict__ counts, const int32_t* __restrict__ rowmap,
                                                            const uint8_t* __restrict__ mask_c, uint8_t* __restrict__ inlier_mask,
                                                            double* __restrict__ pos_out, double* __restrict__ quat_out, int32_t* __restrict__ status,
                                                            const int32_t* __restrict__ decided, const unsigned long long* __restrict__ keys,
-                                                           int32_t* __restrict__ trial_info, const int32_t* __restrict__ probe_info, int max_trials, int min_samples)
+                                                           int32_t* __restrict__ trial_info, const int32_t* __restrict__ probe_info, int max_trials, int min_samples,
+                                                           const int64_t* __restrict__ slam_offsets)
 {
     const int lane = threadIdx.x;
-    const int64_t b = blockIdx.x, base = b * N;
+    const int64_t b = blockIdx.x;
+    int64_t base = b * N;
+    if (slam_offsets) { base = uniform64(slam_offsets[b]); N = uniform64(slam_offsets[b + 1]) - base; }
     const int f = fail[b];
     const int32_t sat = (decided && decided[b]) ? SIM3_FLAG_SATURATED : 0;
     if (trial_info && lane == 0) {
@@ -398,6 +410,75 @@ int launch_sim3_rows(gsf_ctx* ctx, const double* ts, const double* gps, const ui
 }
 }  // namespace gsf
 
+namespace gsf {
+// the body of gsf_fuse_pipeline_robust_info_batch_dev for fixed-stride (offsets == NULL: B x N rows) or ragged batches (trajectory b = rows
+// offsets[b] .. offsets[b + 1], total_rows of them, N = the longest, known to the host: it sizes the draws' LDS).  The fixed-stride form
+// launches what the public entry always launched.
+int robust_chain(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                 const gsf_ekf_config* cfg, int64_t B, int64_t N, const int64_t* offsets, int64_t total_rows, int32_t min_samples,
+                 double residual_threshold, int32_t max_trials, int32_t min_inliers_needed, uint32_t* mt_state, double* R, double* t, double* s,
+                 double* pos_out, double* quat_out, int32_t* status, int32_t* n_inliers, uint8_t* inlier_mask, int32_t* trial_info)
+{
+    GSF_REQUIRE(min_samples >= 1 && min_samples <= 64 && max_trials >= 0 && max_trials <= (1 << 20), "min_samples must be in [1,64], max_trials in [0, 2^20]");
+    const size_t P = offsets ? (size_t)total_rows : (size_t)B * (size_t)N, nb = (size_t)B;
+    // workspace (context scratch, grow-only): point sets, row map, compact mask, counts/offsets, sample sets, fit status, initial poses
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off = align_up(off + bytes); return at; };
+    const size_t o_src = take(P * 24), o_dst = take(P * 24), o_map = take(P * 4), o_mask = take(P), o_cnt = take(nb * 4), o_off = take((nb + 1) * 8),
+                 o_idx = take(nb * (size_t)max_trials * (size_t)min_samples * 4 + 4), o_fit = take(nb * 4), o_fail = take(nb * 4), o_ip = take(nb * 24),
+                 o_iq = take(nb * 32), o_sel = take(P), o_rst = take(nb * 4), o_rn = take(nb * 4), o_key = take(nb * 16), o_dec = take(nb * 4),
+                 o_pinfo = take(nb * 8);
+    int rc = ensure_scratch(ctx, off);
+    if (rc) return rc;
+    char* w = (char*)ctx->scratch;
+    double* src = (double*)(w + o_src); double* dst = (double*)(w + o_dst); int32_t* rowmap = (int32_t*)(w + o_map); uint8_t* mask_c = (uint8_t*)(w + o_mask);
+    int32_t* counts = (int32_t*)(w + o_cnt); int64_t* cofs = (int64_t*)(w + o_off); int32_t* idx = (int32_t*)(w + o_idx);
+    int32_t* fit = (int32_t*)(w + o_fit); int32_t* fail = (int32_t*)(w + o_fail); double* ip = (double*)(w + o_ip); double* iq = (double*)(w + o_iq);
+    // the rows the fit may draw from: every valid row, or the reference's choice (ref :973-998)
+    uint8_t* rowsel = nullptr; int32_t* rows_status = nullptr;
+    if (ctx->fit_rows.mode != 0) {                                        // row choice and compaction in one launch
+        rowsel = (uint8_t*)(w + o_sel); rows_status = (int32_t*)(w + o_rst);
+        const RowsCompact cp{ pos, src, dst, rowmap, counts, cofs, B };
+        if (offsets)                                                      // (the tile reads row n - 1 of a track: not for empty ones)
+            hipLaunchKernelGGL(sim3_rows_kernel<false>, dim3((unsigned)B), dim3(64), 0, ctx->stream, ts, gps, valid, offsets, N, ctx->fit_rows, rowsel,
+                               (int32_t*)(w + o_rn), rows_status, cp);
+        else if (N <= 64 * ROWS_TILE)
+            hipLaunchKernelGGL(sim3_rows_kernel<true>, dim3((unsigned)B), dim3(64), 0, ctx->stream, ts, gps, valid, (const int64_t*)nullptr, N, ctx->fit_rows, rowsel,
+                               (int32_t*)(w + o_rn), rows_status, cp);
+        else
+            hipLaunchKernelGGL(sim3_rows_kernel<false>, dim3((unsigned)B), dim3(64), 0, ctx->stream, ts, gps, valid, (const int64_t*)nullptr, N, ctx->fit_rows, rowsel,
+                               (int32_t*)(w + o_rn), rows_status, cp);
+    } else {
+        hipLaunchKernelGGL(compact_valid_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, pos, gps, valid, (const uint8_t*)rowsel, B, N, src, dst, rowmap, counts, cofs, offsets);
+    }
+    GSF_HIP(hipGetLastError());
+    unsigned long long* keys = (unsigned long long*)(w + o_key);         // arg-max key per trajectory: K2b leaves the winner's trial there (trial_info)
+    int32_t* decided = nullptr; int32_t* pinfo = nullptr; int32_t trial0 = 0;
+    if (!(ctx->ransac_early_exit != 0 && max_trials > 0)) GSF_HIP(hipMemsetAsync(keys, 0, nb * 16, ctx->stream));
+    if (ctx->ransac_early_exit != 0 && max_trials > 0) {
+        // growing rounds of drawn-and-scored trials per trajectory until one counts every row (ref :413), at most probe_trials of them ...
+        decided = (int32_t*)(w + o_dec); pinfo = (int32_t*)(w + o_pinfo);
+        trial0 = ctx->ransac_probe_trials < max_trials ? ctx->ransac_probe_trials : max_trials;
+        const int bytes = choice_lds_bytes(N);
+        hipLaunchKernelGGL(robust_probe_kernel, dim3((unsigned)B), dim3(64), (size_t)bytes, ctx->stream, mt_state, (const double*)src, (const double*)dst,
+                           (const int64_t*)cofs, (const int32_t*)counts, (int)max_trials, (int)trial0, (int)min_samples, residual_threshold, idx, bytes, keys,
+                           decided, pinfo, (int)min_inliers_needed, R, t, s, fit, mask_c, n_inliers);
+        GSF_HIP(hipGetLastError());
+        // ... then the wide kernels for the rest of the trials of the trajectories that are still undecided
+        if ((rc = launch_mt_choice_rest(ctx, mt_state, counts, B, max_trials, trial0, min_samples, idx, (int32_t)N, decided))) return rc;
+    } else if (max_trials > 0 && (rc = launch_mt_choice(ctx, mt_state, counts, B, max_trials, min_samples, idx, (int32_t)N))) return rc;
+    if ((rc = launch_sim3_ransac(ctx, src, dst, cofs, counts, B, idx, max_trials, min_samples, residual_threshold, min_inliers_needed, R, t, s, fit,
+                                 mask_c, n_inliers, (int64_t)P, trial0, keys, decided))) return rc;
+    hipLaunchKernelGGL(robust_init_pose_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, pos, quat, B, N, R, t, s, fit, ip, iq, fail, offsets);
+    GSF_HIP(hipGetLastError());
+    if ((rc = launch_ekf_wave(ctx, false, ts, pos, quat, gps, valid, ip, iq, cfg, B, N, nullptr, nullptr, nullptr, pos_out, quat_out, status, offsets))) return rc;
+    hipLaunchKernelGGL(robust_finish_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, N, fit, fail, (const int32_t*)rows_status, counts, rowmap, mask_c, inlier_mask, pos_out, quat_out, status,
+                       (const int32_t*)decided, (const unsigned long long*)keys, trial_info, (const int32_t*)pinfo, (int)max_trials, (int)min_samples, offsets);
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
+}
+}  // namespace gsf
+
 extern "C" int gsf_fuse_pipeline_robust_info_batch_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps,
                                                        const uint8_t* valid, const gsf_ekf_config* cfg, int64_t B, int64_t N, int32_t min_samples,
                                                        double residual_threshold, int32_t max_trials, int32_t min_inliers_needed, uint32_t* mt_state,
@@ -411,59 +492,8 @@ extern "C" int gsf_fuse_pipeline_robust_info_batch_dev(gsf_ctx* ctx, const doubl
     GSF_REQUIRE(N <= 28000, "N too large for the device-side draws (<= 28000 poses per trajectory)");
     GSF_REQUIRE(ts && pos && quat && gps && valid && mt_state && R && t && s && pos_out && quat_out && status && n_inliers, "NULL array");
     GSF_HIP(hipSetDevice(ctx->device));
-    const size_t P = (size_t)B * (size_t)N, nb = (size_t)B;
-    // workspace (context scratch, grow-only): point sets, row map, compact mask, counts/offsets, sample sets, fit status, initial poses
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off = align_up(off + bytes); return at; };
-    const size_t o_src = take(P * 24), o_dst = take(P * 24), o_map = take(P * 4), o_mask = take(P), o_cnt = take(nb * 4), o_off = take((nb + 1) * 8),
-                 o_idx = take(nb * (size_t)max_trials * (size_t)min_samples * 4 + 4), o_fit = take(nb * 4), o_fail = take(nb * 4), o_ip = take(nb * 24),
-                 o_iq = take(nb * 32), o_sel = take(P), o_rst = take(nb * 4), o_rn = take(nb * 4), o_key = take(nb * 16), o_dec = take(nb * 4),
-                 o_pinfo = take(nb * 8);
-    int rc = ensure_scratch(ctx, off);
-    if (rc) return rc;
-    char* w = (char*)ctx->scratch;
-    double* src = (double*)(w + o_src); double* dst = (double*)(w + o_dst); int32_t* rowmap = (int32_t*)(w + o_map); uint8_t* mask_c = (uint8_t*)(w + o_mask);
-    int32_t* counts = (int32_t*)(w + o_cnt); int64_t* offsets = (int64_t*)(w + o_off); int32_t* idx = (int32_t*)(w + o_idx);
-    int32_t* fit = (int32_t*)(w + o_fit); int32_t* fail = (int32_t*)(w + o_fail); double* ip = (double*)(w + o_ip); double* iq = (double*)(w + o_iq);
-    // the rows the fit may draw from: every valid row, or the reference's choice (ref :973-998)
-    uint8_t* rowsel = nullptr; int32_t* rows_status = nullptr;
-    if (ctx->fit_rows.mode != 0) {                                        // row choice and compaction in one launch
-        rowsel = (uint8_t*)(w + o_sel); rows_status = (int32_t*)(w + o_rst);
-        const RowsCompact cp{ pos, src, dst, rowmap, counts, offsets, B };
-        if (N <= 64 * ROWS_TILE)
-            hipLaunchKernelGGL(sim3_rows_kernel<true>, dim3((unsigned)B), dim3(64), 0, ctx->stream, ts, gps, valid, (const int64_t*)nullptr, N, ctx->fit_rows, rowsel,
-                               (int32_t*)(w + o_rn), rows_status, cp);
-        else
-            hipLaunchKernelGGL(sim3_rows_kernel<false>, dim3((unsigned)B), dim3(64), 0, ctx->stream, ts, gps, valid, (const int64_t*)nullptr, N, ctx->fit_rows, rowsel,
-                               (int32_t*)(w + o_rn), rows_status, cp);
-    } else {
-        hipLaunchKernelGGL(compact_valid_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, pos, gps, valid, (const uint8_t*)rowsel, B, N, src, dst, rowmap, counts, offsets);
-    }
-    GSF_HIP(hipGetLastError());
-    unsigned long long* keys = (unsigned long long*)(w + o_key);         // arg-max key per trajectory: K2b leaves the winner's trial there (trial_info)
-    int32_t* decided = nullptr; int32_t* pinfo = nullptr; int32_t trial0 = 0;
-    if (!(ctx->ransac_early_exit != 0 && max_trials > 0)) GSF_HIP(hipMemsetAsync(keys, 0, nb * 16, ctx->stream));
-    if (ctx->ransac_early_exit != 0 && max_trials > 0) {
-        // growing rounds of drawn-and-scored trials per trajectory until one counts every row (ref :413), at most probe_trials of them ...
-        decided = (int32_t*)(w + o_dec); pinfo = (int32_t*)(w + o_pinfo);
-        trial0 = ctx->ransac_probe_trials < max_trials ? ctx->ransac_probe_trials : max_trials;
-        const int bytes = choice_lds_bytes(N);
-        hipLaunchKernelGGL(robust_probe_kernel, dim3((unsigned)B), dim3(64), (size_t)bytes, ctx->stream, mt_state, (const double*)src, (const double*)dst,
-                           (const int64_t*)offsets, (const int32_t*)counts, (int)max_trials, (int)trial0, (int)min_samples, residual_threshold, idx, bytes, keys,
-                           decided, pinfo, (int)min_inliers_needed, R, t, s, fit, mask_c, n_inliers);
-        GSF_HIP(hipGetLastError());
-        // ... then the wide kernels for the rest of the trials of the trajectories that are still undecided
-        if ((rc = launch_mt_choice_rest(ctx, mt_state, counts, B, max_trials, trial0, min_samples, idx, (int32_t)N, decided))) return rc;
-    } else if (max_trials > 0 && (rc = launch_mt_choice(ctx, mt_state, counts, B, max_trials, min_samples, idx, (int32_t)N))) return rc;
-    if ((rc = launch_sim3_ransac(ctx, src, dst, offsets, counts, B, idx, max_trials, min_samples, residual_threshold, min_inliers_needed, R, t, s, fit,
-                                 mask_c, n_inliers, (int64_t)P, trial0, keys, decided))) return rc;
-    hipLaunchKernelGGL(robust_init_pose_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, pos, quat, B, N, R, t, s, fit, ip, iq, fail);
-    GSF_HIP(hipGetLastError());
-    if ((rc = launch_ekf_wave(ctx, false, ts, pos, quat, gps, valid, ip, iq, cfg, B, N, nullptr, nullptr, nullptr, pos_out, quat_out, status))) return rc;
-    hipLaunchKernelGGL(robust_finish_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, N, fit, fail, (const int32_t*)rows_status, counts, rowmap, mask_c, inlier_mask, pos_out, quat_out, status,
-                       (const int32_t*)decided, (const unsigned long long*)keys, trial_info, (const int32_t*)pinfo, (int)max_trials, (int)min_samples);
-    GSF_HIP(hipGetLastError());
-    return GSF_OK;
+    return robust_chain(ctx, ts, pos, quat, gps, valid, cfg, B, N, nullptr, 0, min_samples, residual_threshold, max_trials, min_inliers_needed, mt_state,
+                        R, t, s, pos_out, quat_out, status, n_inliers, inlier_mask, trial_info);
 }
 
 extern "C" int gsf_fuse_pipeline_robust_batch_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps,

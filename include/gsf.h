@@ -101,6 +101,11 @@ typedef struct {
                                           caller runs that track through the host route from its saved generator state */
 #define GSF_RUN_SIM3_FAILED 8          /* ValueError of the row choice (:975, :997) or RuntimeError of the failed fit (:1003): see status >> 8 */
 #define GSF_RUN_BAD_QUAT 16            /* a SLAM quaternion of the track cannot be normalised: SciPy raises in transform_trajectory (:466) */
+/* set only by gsf_run_fusion_ragged[_dev] (the optional ground-truth log of :962-966, the empty SLAM track of :967) */
+#define GSF_RUN_GT_EMPTY 32            /* no ground-truth row passes the lat/lon range mask: load_gps_data raises, the whole run fails (:264, :964) */
+#define GSF_RUN_GT_FEW 64              /* fewer than 2 ground-truth fixes left after its pre-filter: load_gps_data raises (:283; :966 is never reached) */
+#define GSF_RUN_GT_UNHANDLED 128       /* the device pre-filter does not cover the ground-truth log (as GSF_RUN_PREFILTER_UNHANDLED) */
+#define GSF_RUN_SLAM_EMPTY 256         /* a SLAM track with 0 poses: ValueError at :967, after both logs were loaded and filtered */
 
 /* status of a Sim3 fit: GSF_SIM3_NONE <=> the reference returned (None, None, None) */
 #define GSF_SIM3_OK 0
@@ -451,6 +456,41 @@ GSF_API int gsf_run_fusion_batch(gsf_ctx *ctx, const double *ts, const double *p
                                  double *t, double *s, double *pos_out, double *quat_out, int32_t *status, int32_t *n_inliers, int32_t *zone,
                                  int32_t *south, double *gps_utm, uint8_t *gps_keep, double *aligned, uint8_t *valid, double *sim3_pos,
                                  double *err_stats, int32_t *run_status, uint8_t *inlier_mask, int32_t *trial_info);
+
+/* ---- steps 1-6 of main_process_gui for B SLAM tracks of ANY lengths, with the optional ground-truth GNSS log (EKFGPSSLAM.py:959-1075) ----
+   The chain of gsf_run_fusion_batch_dev on ragged input: track b = rows slam_offsets[b]..slam_offsets[b+1] of ts[P], pos[P][3], quat[P][4]
+   (P = total_poses; max_poses >= the longest track, host-known: it sizes LDS and the draws' workspace); primary log b = fixes
+   gps_offsets[b]..gps_offsets[b+1] as in the dense entry; ground-truth log b = fixes gt_offsets[b]..gt_offsets[b+1] of gt_t / gt_llh
+   (gt_offsets == NULL: no track has one -- the gt_* outputs may then be NULL --; an empty range: that track has none).  gps_llh == NULL /
+   gt_llh == NULL: gps_utm / gt_utm are inputs holding the projected logs, as in the dense entry (zone / south resp. gt_zone / gt_south unused).
+   Per track, in the reference's order of draws and raises: primary log (mask, zone, UTM, pre-filter with cfg->gps_filter; a failure there
+   stops the run before any ground-truth draw) -> ground-truth log (its OWN zone, UTM, pre-filter with gt_filter = CONFIG['ground_truth_gps_
+   filtering'], :55-64) -> the empty-track check (:967) -> steps 2-5 as in the dense entry -> step 6 against the primary fixes and, with a
+   ground-truth log, against it after the same time alignment (:1035-1062).
+   Out, per-pose arrays flat over P rows: as gsf_run_fusion_batch_dev, plus gt_zone[B] / gt_south[B], gt_utm[gt_total][3], gt_keep[gt_total],
+   gt_aligned[P][3] / gt_valid[P]; err_stats[2][3][B][4] = { primary, ground truth } x { raw SLAM, Sim3, EKF } x { count, mean, median, RMSE }
+   (count 0 and NaN where a track has no ground truth); plot_ref[B] (may be NULL) = the error reference of the plot (:1064-1075): 2 ground
+   truth, 1 primary, 0 none; run_status[B] = GSF_RUN_* including the four bits above (a failed run: NaN outputs, count-0 rows, plot_ref 0).
+   Limits: at most 28 000 poses per track, at most 14 000 fixes per log (a longer log fails the call, as in the dense entry); one thread per
+   context at a time (the call swaps the context's Sim3 row rule for the duration, as the dense entry does). */
+GSF_API int gsf_run_fusion_ragged_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *slam_offsets, int64_t B,
+                                      int64_t total_poses, int32_t max_poses, const double *gps_t, const double *gps_llh, const int64_t *gps_offsets,
+                                      int64_t total_fixes, int32_t max_fixes, const double *gt_t, const double *gt_llh, const int64_t *gt_offsets,
+                                      int64_t gt_total, int32_t gt_max_fixes, const gsf_run_config *cfg, const gsf_prefilter_config *gt_filter,
+                                      uint32_t *mt_state, double *R, double *t, double *s, double *pos_out, double *quat_out, int32_t *status,
+                                      int32_t *n_inliers, int32_t *zone, int32_t *south, double *gps_utm, uint8_t *gps_keep, double *aligned,
+                                      uint8_t *valid, double *sim3_pos, int32_t *gt_zone, int32_t *gt_south, double *gt_utm, uint8_t *gt_keep,
+                                      double *gt_aligned, uint8_t *gt_valid, double *err_stats, int32_t *plot_ref, int32_t *run_status,
+                                      uint8_t *inlier_mask, int32_t *trial_info);
+/* the same with host arrays (gps_llh / gt_llh must be given): the sizes are read from the offsets, which are checked (non-decreasing, the
+   limits above) before any device work; then one staged upload, the chain, one download */
+GSF_API int gsf_run_fusion_ragged(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *slam_offsets, int64_t B,
+                                  const double *gps_t, const double *gps_llh, const int64_t *gps_offsets, const double *gt_t, const double *gt_llh,
+                                  const int64_t *gt_offsets, const gsf_run_config *cfg, const gsf_prefilter_config *gt_filter, uint32_t *mt_state,
+                                  double *R, double *t, double *s, double *pos_out, double *quat_out, int32_t *status, int32_t *n_inliers, int32_t *zone,
+                                  int32_t *south, double *gps_utm, uint8_t *gps_keep, double *aligned, uint8_t *valid, double *sim3_pos,
+                                  int32_t *gt_zone, int32_t *gt_south, double *gt_utm, uint8_t *gt_keep, double *gt_aligned, uint8_t *gt_valid,
+                                  double *err_stats, int32_t *plot_ref, int32_t *run_status, uint8_t *inlier_mask, int32_t *trial_info);
 
 /* ragged forms (trajectories of different lengths): flat [total][C] arrays, trajectory b = rows offsets[b]..offsets[b+1] */
 GSF_API int gsf_ekf_fuse_ragged_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
