@@ -212,7 +212,8 @@ def run_fusion_batch(gb, mt_state, config=None, early_exit=True, skip_seconds=5.
     mt_state (B, 625): every trajectory's NumPy legacy generator (mt19937_seed / mt19937_from_numpy), advanced by the pre-filter's and
     the fit's draws in the reference's order; early_exit as in fuse_pipeline_robust_batch (the pre-filter's draws are unaffected).
     projected=True: gb.gps_llh already holds (E, N, alt) rows -- what load_gps_data's projection returns -- and the chain starts at the
-    pre-filter.  Returns a RunResult."""
+    pre-filter.  The pre-filter covers logs of any rate (scikit-learn's sampler on its permutation and tracking-selection routes); a log is
+    flagged RUN_PREFILTER_UNHANDLED only for unsorted stamps in the sliding mode or more than max_windows windows.  Returns a RunResult."""
     g = config or CONFIG
     ctx = context()
     ctx.set_option("ransac_early_exit", 1 if early_exit else 0)
@@ -350,7 +351,9 @@ def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5
     already; zone / south / gt_zone / gt_south are then None.  The context's ransac_early_exit is restored afterwards.
     Returns a RunResult: per-pose fields flat over the P rows (fused.pos (P,3), fused.quat (P,4), aligned, valid, sim3_pos, inlier_mask,
     gt_aligned, gt_valid), slam_offsets / gps_offsets / gt_offsets, gt_utm / gt_keep, err_stats (2, 3, B, 4) = {primary, ground truth} x
-    {raw SLAM, Sim3, EKF} x {count, mean, median, RMSE}, plot_ref (B,) = 0 none / 1 primary / 2 ground truth (:1064-1075), run_status."""
+    {raw SLAM, Sim3, EKF} x {count, mean, median, RMSE}, plot_ref (B,) = 0 none / 1 primary / 2 ground truth (:1064-1075), run_status.
+    Both pre-filters cover logs of any rate; RUN_PREFILTER_UNHANDLED / RUN_GT_UNHANDLED flag only unsorted stamps in the sliding mode or
+    more than max_windows windows."""
     # the host-known sizes first, before any device work: below the longest track / log they would undersize the workspace
     for v, lo, name in zip((rb.max_poses, rb.max_fixes, rb.gt_max_fixes), rb._ranges, ("max_poses", "max_fixes", "gt_max_fixes")):
         if int(v) < lo:
@@ -480,6 +483,18 @@ def mt19937_choice_batch(state, n_population, trials, k):
     n = torch.as_tensor(n_population, dtype=torch.int32).to(state.device).contiguous()
     idx = torch.empty((B, trials, k), dtype=torch.int32, device=state.device)
     check(_lib.load().gsf_mt19937_choice_bounded_batch_dev(context().handle, _p(state), _p(n), n_max, B, int(trials), int(k), _p(idx)))
+    return idx
+
+
+def sample_without_replacement_batch(state, n_population, trials, k):
+    """sample_idx (B, trials, k) int32 = sklearn.utils.random.sample_without_replacement(n_population[b], k) called `trials` times on
+    stream b (method "auto": permutation for 0.01 < k/n < 0.99, tracking selection for k/n <= 0.01, rows 0..k-1 for n == k); `state`
+    (B, 625) is advanced in place exactly as NumPy's generator would be.  Streams with n_population[b] < k are left untouched and their
+    sets are zero."""
+    B = state.shape[0]
+    n = torch.as_tensor(n_population, dtype=torch.int32).to(state.device).contiguous()
+    idx = torch.empty((B, trials, k), dtype=torch.int32, device=state.device)
+    check(_lib.load().gsf_mt19937_sample_without_replacement_batch_dev(context().handle, _p(state), _p(n), B, int(trials), int(k), _p(idx)))
     return idx
 
 

@@ -378,7 +378,7 @@ __device__ __forceinline__ void score_trial(const double* __restrict__ tp, const
 // The WHOLE pre-filter of one GNSS log as one device chain (ref :183-247 sliding windows, :148-182 the single global window): for
 // every window (row range, found by the host from the stamps) and every coordinate axis in the reference's order -- draw max_trials
 // sample sets from the log's legacy MT19937 stream exactly like scikit-learn's sample_without_replacement (permutation(n)[:k] for
-// 0.01 < k/n < 0.99), score them, walk scikit-learn's acceptance rule, REWIND the stream to where n_trials_ draws leave it, and
+// 0.01 < k/n < 0.99, tracking selection for k/n <= 0.01, rows 0 .. k-1 for n == k), score them, walk scikit-learn's acceptance rule, REWIND the stream to where n_trials_ draws leave it, and
 // either AND the axis mask into the window mask or -- no consensus set: the reference's exception -- drop the window and skip its
 // remaining axes (they consume nothing).  keep[] = OR over the successful windows.  One wave per log.
 constexpr int CH_MAX_TRIALS = 1024;
@@ -447,13 +447,20 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
         const int n = r1 - r0;
         int wstat = 0;
         if (n < ms || r0 < 0 || r1 > n_log) return 2;                     // ref :209: too few rows, window not processed
-        // scikit-learn's sampler takes the permutation route only for 0.01 < k/n < 0.99.  Above that range it samples by reservoir: rows
-        // 0 .. k-1, then one randint per FURTHER row -- and with min_samples <= 16 a ratio >= 0.99 means n == k: no further row, no draw,
-        // every trial's sample is rows 0 .. k-1 (a window of exactly min_samples fixes: the tail of a log, a thinned log).  Below the range
-        // (tracking selection, n > 100 k) the log is flagged and left to the host-drawn path.
+        // scikit-learn's sampler (sklearn/utils/_random.pyx, method "auto") routes by the ratio k/n in double precision: permutation(n)[:k]
+        // for 0.01 < k/n < 0.99; tracking selection (one randint(n) per selection, duplicates drawn again) for k/n <= 0.01, i.e. n >= 100 k
+        // when k <= 16; reservoir sampling above 0.99 -- rows 0 .. k-1, then one randint per FURTHER row, and with min_samples <= 16 a
+        // ratio >= 0.99 means n == k: no further row, no draw, every trial's sample is rows 0 .. k-1 (a window of exactly min_samples
+        // fixes: the tail of a log, a thinned log).  Only permutation windows use jseq, sized for n < 100 k rows (chain_lds).
         const double ratio = (double)ms / (double)n;
         const bool identity = n == ms;
-        if (!identity && (!(ratio > 0.01 && ratio < 0.99) || n > jseq_elems)) { lstat = 2; return 3; }
+        const bool tracking = !identity && !(ratio > 0.01);
+        if (!identity && !tracking && (!(ratio < 0.99) || n > jseq_elems)) { lstat = 2; return 3; }   // (neither can happen for ms <= 16)
+        // the window's draws, one route for the whole window: both draw sites below go through here
+        auto draw = [&](const int cnt, int32_t* o, int32_t* e) {
+            if (tracking) mt_draw_tracking(mt, pos_mt, n, cnt, ms, o, e, lane);
+            else mt_draw_choice(mt, pos_mt, n, cnt, ms, jseq, jseq_elems, o, e, lane);
+        };
 #ifdef GSF_PF_TIMING
         const long long pf_w0 = clock64();
 #endif
@@ -490,7 +497,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
             PF_T0();
             for (int i = lane; i <= MT_N; i += 64) snap[i] = (i < MT_N) ? mt[i] : (uint32_t)pos_mt;
             __syncthreads();
-            mt_draw_choice(mt, pos_mt, n, na, ms, jseq, jseq_elems, sh_idx, sh_end, lane);
+            draw(na, sh_idx, sh_end);
             PF_ADD(12);
             const double* y0 = pos + (r_base + r0) * 3 + ax;
             if (lane < na) sh_model[lane] = fit_subset<true>(tp, y0 + lane, sh_idx + (size_t)lane * ms, ms, degree, 3);
@@ -564,15 +571,16 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
             int tbn0 = gen.first_batch;
             if (miss_batch > tbn0) tbn0 = miss_batch;
             miss_batch = 0;
-            for (int tbn = tbn0; (double)ntr < max_tr; tbn = tbn < 64 ? tbn * 2 : 64) {
-                const int nb = (max_trials - drawn < tbn) ? (max_trials - drawn) : tbn;
+            for (int tbn = tbn0; (double)ntr < max_tr; tbn = tbn * 2 < 64 ? tbn * 2 : 64) {
+                int nb = (max_trials - drawn < tbn) ? (max_trials - drawn) : tbn;
+                nb = nb < 64 ? nb : 64;                                   // sh_model holds 64 (first_batch / miss_batch may exceed it)
                 if (nb <= 0) break;
                 if (identity) {
                     for (int e = lane; e < nb * ms; e += 64) sh_idx[(size_t)drawn * ms + e] = e % ms;
                     for (int tau = lane; tau < nb; tau += 64) sh_end[drawn + tau] = 0;      // nothing consumed
                     __syncthreads();
                 } else {
-                    mt_draw_choice(mt, pos_mt, n, nb, ms, jseq, jseq_elems, sh_idx + (size_t)drawn * ms, sh_end + drawn, lane);
+                    draw(nb, sh_idx + (size_t)drawn * ms, sh_end + drawn);
                 }
                 PF_ADD(1);
                 // models: a lane per trial (at most 32 of them work); scores: the whole wave over the ROWS of one trial at a time -- a batch
@@ -824,7 +832,8 @@ int gsf_ransac_poly_batch_dev(gsf_ctx* ctx, const double* t, const double* y, co
 }
 
 // LDS of the chain kernel (40 KB dynamic next to 23 KB of static arrays): the sample sets of one window-axis, then the swap partners of as
-// many trials as the rest allows (at least one trial's worth)
+// many trials as the rest allows (at least one trial's worth).  Only permutation windows (0.01 < min_samples / n: n < 100 min_samples rows)
+// use the swap partners -- tracking selection draws without them -- so the buffer is sized by min(max_window_rows, 100 min_samples - 1).
 static int chain_lds(int32_t max_trials, int32_t min_samples, int32_t max_window_rows, int64_t B, int& jseq_elems, size_t& lds)
 {
     // per trial: score 8 + end 4 + nin 4 + idx 4 * min_samples bytes; then the swap partners of as many buffered trials as the budget allows
@@ -832,11 +841,12 @@ static int chain_lds(int32_t max_trials, int32_t min_samples, int32_t max_window
     // and keep a block under 20 KB, i.e. every SIMD of a CU busy with its own log; few logs: up to 64 trials / 40 KB as before.
     const size_t fixed = (size_t)max_trials * (16 + 4 * (size_t)min_samples);
     const size_t budget = 56 * 1024;
-    if (fixed + 2 * (size_t)max_window_rows + 8 > budget) return 1;
-    int tb = (int)((budget - fixed - 8) / 2 / (size_t)max_window_rows);
+    const int perm_rows = max_window_rows < 100 * min_samples - 1 ? max_window_rows : 100 * min_samples - 1;
+    if (fixed + 2 * (size_t)perm_rows + 8 > budget) return 1;
+    int tb = (int)((budget - fixed - 8) / 2 / (size_t)perm_rows);
     const int cap = B > 256 ? 16 : 64;
     if (tb > cap) tb = cap;
-    jseq_elems = tb * max_window_rows;
+    jseq_elems = tb * perm_rows;
     lds = fixed + (size_t)((jseq_elems + 3) & ~3) * 2;
     return 0;
 }

@@ -218,6 +218,43 @@ __device__ __forceinline__ void mt_draw_choice(uint32_t* mt, int& pos, const int
         __syncthreads();
     }
 }
+// `trials` consecutive trials of scikit-learn's tracking selection (sample_without_replacement for k/n <= 0.01): kk times
+// j = RandomState.randint(n), drawn again while j is already in the trial's set.  randint(n) is one raw output masked with
+// mask_for(n - 1) and rejected above n - 1 (NumPy's buffered_bounded_masked_uint32: no output carried between calls), so a trial is
+// the run of raw outputs up to its kk-th in-range, non-duplicate value.  Same contract as mt_draw_choice: out[trial * kk + p] in draw
+// order, end_raw[trial] (may be null) = raw outputs consumed since the call started up to and including the trial's last accepted one,
+// (mt, pos) left just after the last trial's last consumed output.  A chunk is up to 64 outputs (one per lane, never past the block);
+// its in-range candidates are walked in order, each tested against the trial's selections (lane p holds selection p: one compare and
+// one ballot).  n >= 2, kk <= 64.  One wave; block barriers only in mt_regenerate and one at the end (out / end_raw visible to all lanes).
+__device__ __forceinline__ void mt_draw_tracking(uint32_t* mt, int& pos, const int n, const int trials, const int kk, int32_t* out,
+                                                 int32_t* end_raw, const int lane)
+{
+    const uint32_t top = (uint32_t)(n - 1), mask = mask_for(top);     // randint(n): rng = n - 1, one mask for the whole call
+    int raw = 0, t = 0, got = 0;                                        // wave-uniform: trial, selections made in it
+    uint32_t sel = 0;                                                   // lane p < got: the trial's p-th selection
+    while (t < trials) {
+        if (pos >= MT_N) { mt_regenerate(mt, lane); pos = 0; }
+        const int avail = (MT_N - pos < 64) ? (MT_N - pos) : 64;
+        const bool have = lane < avail;
+        const uint32_t v = have ? (mt_temper(mt[pos + lane]) & mask) : 0u;
+        unsigned long long cand = __builtin_amdgcn_ballot_w64(have && v <= top);
+        int used = avail;                                               // outputs of this chunk consumed
+        while (cand != 0ull) {
+            const int l = __builtin_ctzll(cand);
+            cand &= cand - 1ull;
+            const uint32_t val = (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+            if (__builtin_amdgcn_ballot_w64(lane < got && sel == val) != 0ull) continue;   // already selected: draw again
+            if (lane == got) sel = val;
+            if (++got < kk) continue;
+            if (lane < kk) out[(size_t)t * kk + lane] = (int32_t)sel;
+            if (end_raw && lane == 0) end_raw[t] = raw + l + 1;
+            got = 0;
+            if (++t == trials) { used = l + 1; break; }                 // the stream stops right after this output
+        }
+        pos += used; raw += used;
+    }
+    __syncthreads();
+}
 // discard `k` raw outputs of the stream
 __device__ __forceinline__ void mt_skip(uint32_t* mt, int& pos, int k, const int lane)
 {

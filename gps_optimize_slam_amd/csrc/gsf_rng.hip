@@ -61,6 +61,40 @@ __global__ __launch_bounds__(64) void mt_choice_kernel(uint32_t* __restrict__ st
     if (lane == 0) st[MT_N] = (uint32_t)pos;
 }
 
+// sample_idx[b][trial][0..k) = scikit-learn's sample_without_replacement(n_b, k) (sklearn/utils/_random.pyx, method "auto") for `trials`
+// consecutive calls on stream b, routed per stream by the ratio k / n_b in double precision as scikit-learn routes it: permutation(n)[:k]
+// for 0.01 < k/n < 0.99 (mt_draw_choice), tracking selection for k/n <= 0.01 (mt_draw_tracking), reservoir sampling above -- which for
+// k <= 64 means n == k: rows 0 .. k-1, nothing drawn.  The device functions of the GPS pre-filter's chain (gsf_gpsfilter.hip).
+// n_b < k: scikit-learn raises; the stream is left untouched and its sets zero-filled.
+__global__ __launch_bounds__(64) void mt_sample_kernel(uint32_t* __restrict__ state, const int32_t* __restrict__ counts, int trials, int kk,
+                                                       int32_t* __restrict__ sample_idx, int jseq_bytes)
+{
+    __shared__ uint32_t mt[MT_N + 1];
+    extern __shared__ uint16_t jseq[];
+    const int lane = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int n = counts[b];
+    int32_t* out = sample_idx + (size_t)b * (size_t)trials * (size_t)kk;
+    const double ratio = n > 0 ? (double)kk / (double)n : 1.0;
+    const bool perm = ratio > 0.01 && ratio < 0.99;
+    if (n < kk || (perm && n > jseq_bytes / 2)) {                        // (the second cannot happen: perm means n < 100 k <= jseq_bytes / 2)
+        for (int i = lane; i < trials * kk; i += 64) out[i] = 0;
+        return;
+    }
+    if (!perm && ratio >= 0.99) {                                        // reservoir sampling with n == k
+        for (int i = lane; i < trials * kk; i += 64) out[i] = i % kk;
+        return;
+    }
+    uint32_t* st = state + b * MT_STATE_WORDS;
+    for (int i = lane; i < MT_N; i += 64) mt[i] = st[i];
+    int pos = (int)st[MT_N];
+    __syncthreads();
+    if (perm) mt_draw_choice(mt, pos, n, trials, kk, jseq, jseq_bytes / 2, out, nullptr, lane);
+    else mt_draw_tracking(mt, pos, n, trials, kk, out, nullptr, lane);
+    for (int i = lane; i < MT_N; i += 64) st[i] = mt[i];
+    if (lane == 0) st[MT_N] = (uint32_t)pos;
+}
+
 }  // namespace
 
 namespace gsf {
@@ -123,6 +157,21 @@ int gsf_mt19937_choice_bounded_batch_dev(gsf_ctx* ctx, uint32_t* state, const in
     GSF_REQUIRE(state && n_population && sample_idx, "NULL array");
     GSF_HIP(hipSetDevice(ctx->device));
     return launch_mt_choice(ctx, state, n_population, B, trials, k, sample_idx, n_max);
+}
+
+int gsf_mt19937_sample_without_replacement_batch_dev(gsf_ctx* ctx, uint32_t* state, const int32_t* n_population, int64_t B, int32_t trials,
+                                                     int32_t k, int32_t* sample_idx)
+{
+    GSF_REQUIRE(ctx && B >= 0 && B <= 0x7fffffff && trials >= 0 && k >= 1 && k <= 64, "bad arguments");
+    GSF_REQUIRE((int64_t)trials * k <= 0x7fffffff, "trials x k must fit in int32");
+    if (B == 0 || trials == 0) return GSF_OK;
+    GSF_REQUIRE(state && n_population && sample_idx, "NULL array");
+    GSF_HIP(hipSetDevice(ctx->device));
+    const int bytes = choice_lds_bytes(100 * (int64_t)k - 1);          // permutation streams have n < 100 k rows
+    hipLaunchKernelGGL(mt_sample_kernel, dim3((unsigned)B), dim3(64), (size_t)bytes, ctx->stream, state, n_population, (int)trials, (int)k, sample_idx,
+                       bytes);
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
 }
 
 }  // extern "C"

@@ -186,8 +186,9 @@ def filter_gps_outliers_ransac(times, positions, config):
     across windows -- rows never inside a fitted window are dropped.  The whole filter is ONE library call
     (gsf_gps_prefilter_chain): every window and axis in the reference's order, the sample sets drawn on the device from NumPy's
     global legacy generator exactly as scikit-learn's sampler draws them, the generator handed back where the reference leaves
-    it -- a seeded run keeps the same rows.  Logs the device sampler does not cover (unsorted stamps, min_samples/n outside
-    (0.01, 0.99)) take the window-by-window route with host-drawn sample sets (_ransac_axes_mask)."""
+    it -- a seeded run keeps the same rows.  The device sampler covers every ratio min_samples/n (permutation, tracking selection
+    for n >= 100 min_samples, n == min_samples); logs the chain does not cover (unsorted stamps in the sliding mode, more than 14 000
+    rows in a window, configurations beyond its limits) take the window-by-window route with host-drawn sample sets (_ransac_axes_mask)."""
     if not config.get("enabled", False):
         return times, positions
     n_points, need = len(times), config["min_samples"]
@@ -199,7 +200,8 @@ def filter_gps_outliers_ransac(times, positions, config):
     ranges, wins = _prefilter_windows(times, config, need)
     longest = max((b - a for a, b in ranges), default=0) if ranges is not None else 0
     chain_ok = (ranges is not None and positions.shape[1] == 3 and longest <= 14000 and 1 <= trials <= 1024 and need <= 16 and 1 <= degree <= 3
-                and trials * (16 + 4 * need) + 2 * longest + 8 <= 56 * 1024)    # gsf_gps_prefilter_chain's own limits (LDS budget of its sampler: chain_lds, csrc/gsf_gpsfilter.hip)
+                and trials * (16 + 4 * need) + 2 * min(longest, 100 * need - 1) + 8 <= 56 * 1024)    # gsf_gps_prefilter_chain's own limits (LDS budget of
+    # its sampler, chain_lds in csrc/gsf_gpsfilter.hip: only permutation windows, fewer than 100 min_samples rows, buffer swap partners)
     if chain_ok:
         if not ranges:
             return times[:0], positions[:0]                              # no window had enough rows: nothing is ever marked (ref :199-236)

@@ -96,9 +96,10 @@ typedef struct {
 #define GSF_RUN_OK 0
 #define GSF_RUN_GPS_EMPTY 1            /* no GNSS row passes the lat/lon range mask: load_gps_data raises ValueError (EKFGPSSLAM.py:264) */
 #define GSF_RUN_GPS_FEW 2              /* fewer than 2 fixes left after the pre-filter: ValueError (:283, :967) */
-#define GSF_RUN_PREFILTER_UNHANDLED 4  /* the device pre-filter does not cover this log (unsorted stamps, scikit-learn's sampler outside its
-                                          permutation range 0.01 < min_samples / n < 0.99, more than max_windows windows): NaN outputs; the
-                                          caller runs that track through the host route from its saved generator state */
+#define GSF_RUN_PREFILTER_UNHANDLED 4  /* the device pre-filter does not cover this log (unsorted stamps in the sliding-window mode, more than
+                                          max_windows windows): NaN outputs; the caller runs that track through the host route from its saved
+                                          generator state.  Every ratio min_samples / n of scikit-learn's sampler is covered (permutation,
+                                          tracking selection, n == min_samples) */
 #define GSF_RUN_SIM3_FAILED 8          /* ValueError of the row choice (:975, :997) or RuntimeError of the failed fit (:1003): see status >> 8 */
 #define GSF_RUN_BAD_QUAT 16            /* a SLAM quaternion of the track cannot be normalised: SciPy raises in transform_trajectory (:466) */
 /* set only by gsf_run_fusion_ragged[_dev] (the optional ground-truth log of :962-966, the empty SLAM track of :967) */
@@ -280,10 +281,11 @@ GSF_API int gsf_ransac_poly_batch(gsf_ctx *ctx, const double *t, const double *y
    in/out) exactly as scikit-learn's sample_without_replacement draws them, RANSACRegressor's acceptance walk, the stream rewound to
    where n_trials_ draws leave it; a failing axis drops its window and consumes nothing further for it (ref :228-229).
    keep[total] = OR over successful windows of the AND over axes; win_status[w] = 0 ok / 1 no consensus / 2 fewer rows than
-   min_samples (not processed) / 3 not handled; log_status[b] = 2 when a window's min_samples/n is 0.01 or less -- scikit-learn then
-   samples by tracking selection, which is not restated here -- and the caller has to take the fed-sample route
-   (gsf_ransac_poly_batch_dev) for that log from its saved generator state.  (A window of exactly min_samples rows, ratio 1, is handled:
-   scikit-learn's reservoir sampling then returns rows 0 .. min_samples-1 without a draw.)  max_trials <= 1024, min_samples <= 16, degree <= 3. */
+   min_samples (not processed) / 3 not handled; log_status[b] = 0 (2 is kept for a window the device sampler does not cover, which no
+   window of min_samples <= 16 is).  scikit-learn's sampler is restated on all its routes, chosen per window by min_samples / n in double
+   precision: permutation(n)[:k] for 0.01 < k/n < 0.99, tracking selection (one randint(n) per selection, duplicates drawn again) for
+   k/n <= 0.01, i.e. n >= 100 min_samples, and -- a window of exactly min_samples rows, ratio 1 -- reservoir sampling, which returns rows
+   0 .. min_samples-1 without a draw.  max_trials <= 1024, min_samples <= 16, degree <= 3, max_window_rows <= 14000. */
 GSF_API int gsf_gps_prefilter_chain_dev(gsf_ctx *ctx, const double *t, const double *pos, const int64_t *offsets, int64_t B,
                                         const int32_t *win_rows, const int64_t *win_offsets, int32_t max_window_rows, int32_t max_trials,
                                         int32_t min_samples, int32_t degree, double residual_threshold, double stop_probability,
@@ -295,8 +297,9 @@ GSF_API int gsf_gps_prefilter_chain(gsf_ctx *ctx, const double *t, const double 
 /* filter_gps_outliers_ransac AS A WHOLE for B logs (EKFGPSSLAM.py:136-247), no host step: the windows are found on the device from the
    stamps the way the reference walks them (:199-234: [w0, w0 + duration) advanced by duration x step_factor, one extra tail window, windows
    with fewer than min_samples rows skipped), or one global window (:148-182; a failing fit passes the log unfiltered), plus the
-   reference's early-outs (disabled, fewer rows than min_samples: everything kept, nothing drawn).  Sorted stamps only (log_status 3
-   otherwise); max_log_rows >= the longest log.  log_info[B][2] (may be NULL) = { windows fitted, windows that found a consensus }.
+   reference's early-outs (disabled, fewer rows than min_samples: everything kept, nothing drawn).  Sorted stamps only in the
+   sliding-window mode, and at most max_windows windows (log_status 3 otherwise: the log's generator is then not written back);
+   max_log_rows >= the longest log, <= 14000.  log_info[B][2] (may be NULL) = { windows fitted, windows that found a consensus }.
    Draws, acceptance walk, generator handling: as gsf_gps_prefilter_chain_dev. */
 GSF_API int gsf_gps_prefilter_auto_dev(gsf_ctx *ctx, const double *t, const double *pos, const int64_t *offsets, int64_t B, int32_t max_log_rows,
                                        const gsf_prefilter_config *filter, uint32_t *mt_state, uint8_t *keep, int32_t *log_status,
@@ -352,7 +355,7 @@ GSF_API int gsf_sim3_ransac_mt_batch(gsf_ctx *ctx, const double *src, const doub
    gsf_mt19937_seed_batch_dev: np.random.seed(seeds[b]) for every stream.
    gsf_mt19937_choice_batch_dev: sample_idx[b][trial][0..k) = RandomState.permutation(n_population[b])[:k] for `trials`
    consecutive trials of stream b (what np.random.choice(n, k, replace=False) draws; also scikit-learn's
-   sample_without_replacement for 0.01 < k/n < 0.99), the state advanced exactly as NumPy advances it.  Streams with
+   sample_without_replacement for 0.01 < k/n < 0.99 -- all ratios: gsf_mt19937_sample_without_replacement_batch_dev), the state advanced exactly as NumPy advances it.  Streams with
    n_population[b] < k are left untouched (the reference returns before drawing, :395-397).  n_population[b] <= 28000, k <= 64.
    gsf_mt19937_choice_bounded_batch_dev: the same, with n_max >= every n_population[b] known to the HOST (0 = unknown).  The
    populations live in device memory, so only with this bound can the library size the workspace of the chip-wide route
@@ -364,6 +367,15 @@ GSF_API int gsf_mt19937_choice_batch_dev(gsf_ctx *ctx, uint32_t *state, const in
                                          int32_t k, int32_t *sample_idx);
 GSF_API int gsf_mt19937_choice_bounded_batch_dev(gsf_ctx *ctx, uint32_t *state, const int32_t *n_population, int32_t n_max, int64_t B,
                                                  int32_t trials, int32_t k, int32_t *sample_idx);
+/* scikit-learn's sample_without_replacement(n_population[b], k) (method "auto", the sampler of RANSACRegressor and of the GPS
+   pre-filter) for `trials` consecutive calls on stream b: sample_idx[b][trial][0..k), in the order scikit-learn returns them.  Routed per
+   stream by k / n in double precision as scikit-learn routes it: RandomState.permutation(n)[:k] for 0.01 < k/n < 0.99; tracking selection
+   for k/n <= 0.01 (k times randint(n), a value already in the set drawn again); reservoir sampling above 0.99, which for k <= 64 means
+   n == k: rows 0 .. k-1, nothing drawn.  The state is advanced exactly as NumPy advances it.  Streams with n_population[b] < k (scikit-
+   learn raises) are left untouched and their sets zero-filled.  k <= 64, n_population[b] <= 2^31 - 1.  The sets feed
+   gsf_ransac_poly_batch_dev at any ratio. */
+GSF_API int gsf_mt19937_sample_without_replacement_batch_dev(gsf_ctx *ctx, uint32_t *state, const int32_t *n_population, int64_t B,
+                                                             int32_t trials, int32_t k, int32_t *sample_idx);
 
 /* ---- K3: apply Sim3 (transform_trajectory, EKFGPSSLAM.py:461-467) -------------------------- */
 /* pos[total][3], quat[total][4]; per-trajectory R[B][9], t[B][3], s[B].  A zero-norm quaternion (SciPy raises
