@@ -78,6 +78,8 @@ class RunConfig(C.Structure):
 RUN_GPS_EMPTY, RUN_GPS_FEW, RUN_PREFILTER_UNHANDLED, RUN_SIM3_FAILED, RUN_BAD_QUAT = 1, 2, 4, 8, 16      # run_status bits of gsf_run_fusion_batch_dev
 RUN_GT_EMPTY, RUN_GT_FEW, RUN_GT_UNHANDLED, RUN_SLAM_EMPTY = 32, 64, 128, 256                          # ... and of gsf_run_fusion_ragged_dev only
 SIM3_FLAG_SATURATED = 256
+TUM_UTM, TUM_WGS84 = 0, 1                                     # formats of gsf_tum_text_dev
+TEXT_DEVICE, TEXT_SKIPPED, TEXT_HOST = 0, 1, 2                  # its track_state values
 
 
 def library_path():
@@ -158,6 +160,8 @@ SIGNATURES = {
     "gsf_ekf_fuse_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp]),
     "gsf_fuse_pipeline_ragged_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsf_fuse_pipeline_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gsf_utm_to_wgs84_rows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gsf_tum_text_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "gsf_time_align_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
     "gsf_time_align_loaded_rows_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
     "gsf_time_align_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp]),

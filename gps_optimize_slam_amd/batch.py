@@ -399,6 +399,161 @@ def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5
     return r
 
 
+# ---------------------------------------------------------------------------- step 7 (EKFGPSSLAM.py:1085-1104) for ragged runs
+TEXT_GROUP_BYTES = 256 << 20        # save_fusion_ragged: text of one group of tracks = one device buffer and one copy into pinned memory
+_TUM_FORMATS = {"utm": _lib.TUM_UTM, "wgs84": _lib.TUM_WGS84}
+
+
+def corrected_utm_name(slam_path):
+    """The default name main_process_gui offers for the corrected track (ref :1087-1088): the SLAM file's base name with '.txt' ->
+    '_corrected_utm.txt', or '_corrected_utm.txt' appended."""
+    base = str(slam_path).split("/")[-1].split("\\")[-1]
+    return base.replace(".txt", "_corrected_utm.txt") if ".txt" in base else base + "_corrected_utm.txt"
+
+
+def _offsets_chk(offsets):
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or not offsets.is_cuda or offsets.numel() < 1:
+        raise ValueError("offsets: expected a contiguous cuda int64 tensor of B+1 values")
+    return int(offsets.numel()) - 1
+
+
+def utm_to_wgs84_ragged(pos, offsets, zone, south, run_status=None):
+    """utm_to_wgs84(corrected_pos, projector) (ref :1097, :291-296) for ragged tracks: pos (P, 3) rows [E, N, alt], offsets (B+1,) int64, zone /
+    south (B,) int32 = the primary log's projector (RunResult.zone / .south).  Returns (P, 3) rows [lon, lat, alt]; lon / lat are bit for bit
+    what the drop-in's UtmProjector(zone, south)(E, N, inverse=True) returns.  run_status (B,) int32 or None: tracks with run_status != 0 get
+    NaN rows (their zone / south are not read)."""
+    B = _offsets_chk(offsets)
+    P = int(pos.shape[0]) if pos.dim() == 2 else -1
+    _chk(pos, torch.float64, (P, 3), "pos")
+    if zone is None or south is None:
+        raise ValueError("utm_to_wgs84_ragged: zone / south are None (projected input has no projector, ref :1096)")
+    _chk(zone, torch.int32, (B,), "zone"); _chk(south, torch.int32, (B,), "south")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    out = torch.empty((P, 3), dtype=torch.float64, device=pos.device)
+    check(_lib.load().gsf_utm_to_wgs84_rows_dev(context().handle, _p(pos), _p(offsets), _p(zone), _p(south), _p(run_status), B, _p(out)))
+    return out
+
+
+def _text_args(ts, xyz, quat, offsets, run_status):
+    B = _offsets_chk(offsets)
+    P = int(ts.numel())
+    _chk(ts, torch.float64, (P,), "ts"); _chk(xyz, torch.float64, (P, 3), "xyz"); _chk(quat, torch.float64, (P, 4), "quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    return B, P
+
+
+def _text_sizes(form, ts, xyz, quat, offsets, run_status, B, P):
+    """the size call of gsf_tum_text_dev: (text_offsets (B+1,) int64, track_state (B,) int32) on the device"""
+    text_offsets = torch.empty((B + 1,), dtype=torch.int64, device=ts.device)
+    state = torch.empty((max(B, 1),), dtype=torch.int32, device=ts.device)
+    check(_lib.load().gsf_tum_text_dev(context().handle, form, _p(ts), _p(xyz), _p(quat), _p(offsets), _p(run_status), B, P, _p(text_offsets),
+                                       _p(state), None))
+    return text_offsets, state[:B]
+
+
+def _savetxt_track(form, path, ts, xyz, quat, lo, hi):
+    """the drop-in's writer on one track's rows (tracks whose values the device does not cover, track_state 2)"""
+    from . import ekfgpsslam as E
+    writer = E.save_tum_utm if form == _lib.TUM_UTM else E.save_tum_wgs84
+    writer(path, ts[lo:hi].cpu().numpy(), xyz[lo:hi].cpu().numpy(), quat[lo:hi].cpu().numpy())
+
+
+def tum_text_ragged(ts, xyz, quat, offsets, fmt="utm", run_status=None):
+    """The bytes np.savetxt writes for each track (ref :1091-1092 for fmt="utm", :1098-1101 for fmt="wgs84", xyz = utm_to_wgs84_ragged rows),
+    formatted on the device (gsf_tum_text_dev).  ts (P,), xyz (P, 3), quat (P, 4), offsets (B+1,) int64, run_status (B,) int32 or None.
+    Returns (texts, track_state): texts = B bytes objects (None for a track with run_status != 0); track_state (B,) numpy int32 = 0 formatted on
+    the device, 1 skipped, 2 holds a finite |x| >= 2^63 and was written here through np.savetxt."""
+    import io
+    import numpy as np
+    if fmt not in _TUM_FORMATS:
+        raise ValueError(f"fmt must be 'utm' or 'wgs84', got {fmt!r}")
+    form = _TUM_FORMATS[fmt]
+    B, P = _text_args(ts, xyz, quat, offsets, run_status)
+    text_offsets, state = _text_sizes(form, ts, xyz, quat, offsets, run_status, B, P)
+    toff = text_offsets.cpu().numpy()
+    total = int(toff[-1])
+    text = torch.empty((max(total, 1),), dtype=torch.uint8, device=ts.device)
+    check(_lib.load().gsf_tum_text_dev(context().handle, form, _p(ts), _p(xyz), _p(quat), _p(offsets), _p(run_status), B, P, _p(text_offsets),
+                                       _p(state), _p(text)))
+    host = text[:total].cpu().numpy().tobytes()
+    st = state.cpu().numpy()
+    offs = offsets.cpu().numpy()
+    texts = []
+    for b in range(B):
+        if st[b] == _lib.TEXT_SKIPPED:
+            texts.append(None)
+        elif st[b] == _lib.TEXT_HOST:
+            f = io.BytesIO()
+            _savetxt_track(form, f, ts, xyz, quat, int(offs[b]), int(offs[b + 1]))
+            texts.append(f.getvalue())
+        else:
+            texts.append(host[toff[b]:toff[b + 1]])
+    return texts, st
+
+
+def save_fusion_ragged(rb, r, utm_paths):
+    """Step 7 of main_process_gui (ref :1085-1104) for a run_fusion_ragged result: per track b, utm_paths[b] (None: not saved, the dialog of
+    :1086-1090) gets the corrected track as *_corrected_utm.txt (:1091-1092) and, when the run has a projector (r.zone is not None, :1096), its
+    WGS84 file named by the drop-in's rule (ekfgpsslam.wgs84_path, :1099-1100) -- byte for byte what np.savetxt writes for the same rows.
+    Tracks with run_status != 0 get no file (the reference raised before step 7).  The text is formatted on the device (gsf_tum_text_dev)
+    in groups of tracks of at most TEXT_GROUP_BYTES bytes (a longer track is a group of its own): one copy per group into pinned memory,
+    one write per file.  Returns, per track, the tuple of the paths written."""
+    import numpy as np
+    from . import ekfgpsslam as E
+    B = rb.B
+    if len(utm_paths) != B:
+        raise ValueError(f"save_fusion_ragged: {len(utm_paths)} paths for {B} tracks")
+    status = r.run_status.cpu().numpy()
+    want = np.array([p is not None and int(status[b]) == 0 for b, p in enumerate(utm_paths)], dtype=bool)
+    written = [[] for _ in range(B)]
+    if not want.any():
+        return [tuple(w) for w in written]
+    dev = rb.ts.device
+    skip = torch.as_tensor((~want).astype(np.int32), device=dev)      # run_status of the text calls: every track not to be saved
+    ts, pos, quat, so = rb.ts, r.fused.pos, r.fused.quat, rb.slam_offsets
+    _, P = _text_args(ts, pos, quat, so, skip)
+    jobs = [(_lib.TUM_UTM, pos, [str(p) if w else None for p, w in zip(utm_paths, want)])]
+    if r.zone is not None:
+        lla = utm_to_wgs84_ragged(pos, so, r.zone, r.south, skip)
+        jobs.append((_lib.TUM_WGS84, lla, [E.wgs84_path(str(p)) if w else None for p, w in zip(utm_paths, want)]))
+    offs = so.cpu().numpy()
+    L, h = _lib.load(), context().handle
+    dbuf = hbuf = None
+    for form, xyz, paths in jobs:
+        text_offsets, state = _text_sizes(form, ts, xyz, quat, so, skip, B, P)
+        toff, st = text_offsets.cpu().numpy(), state.cpu().numpy()
+        groups, b = [], 0
+        while b < B:                                                    # consecutive tracks whose text fits the budget
+            e = b + 1
+            while e < B and toff[e + 1] - toff[b] <= TEXT_GROUP_BYTES:
+                e += 1
+            groups.append((b, e))
+            b = e
+        need = max(int(toff[e] - toff[b]) for b, e in groups)
+        if need and (dbuf is None or dbuf.numel() < need):
+            dbuf = torch.empty((need,), dtype=torch.uint8, device=dev)
+            hbuf = torch.empty((need,), dtype=torch.uint8, pin_memory=True)
+        for b, e in groups:
+            n = int(toff[e] - toff[b])
+            if n:
+                rel = text_offsets[b:e + 1] - text_offsets[b]
+                check(L.gsf_tum_text_dev(h, form, _p(ts), _p(xyz), _p(quat), _p(so[b:]), _p(skip[b:]), e - b, P, _p(rel), _p(state[b:]), _p(dbuf)))
+                hbuf[:n].copy_(dbuf[:n])
+                mv = memoryview(hbuf.numpy())
+                for k in range(b, e):
+                    if st[k] == _lib.TEXT_DEVICE:
+                        with open(paths[k], "wb") as fh:
+                            fh.write(mv[toff[k] - toff[b]:toff[k + 1] - toff[b]])
+                        written[k].append(paths[k])
+            for k in range(b, e):
+                if st[k] == _lib.TEXT_HOST:
+                    _savetxt_track(form, paths[k], ts, xyz, quat, int(offs[k]), int(offs[k + 1]))
+                    written[k].append(paths[k])
+    return [tuple(w) for w in written]
+
+
 class FusedPoses:
     """Fused poses of a batch.  pos and quat are views of ONE allocation `buf` = [pos | quat] (7 doubles per pose), so the
     multi-GPU collect is a single all-gather of `buf`.  `buf` may be a caller-provided slice of a larger arena."""

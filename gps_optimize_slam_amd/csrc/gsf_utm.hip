@@ -44,28 +44,40 @@ __global__ __launch_bounds__(256) void utm_zone_kernel(const double* __restrict_
 #define GSF_UTM_OCC 3
 #endif
 // (three waves per SIMD: 168 registers.  Left alone the compiler takes 170 for the geodesy slice -- allocated as 176, i.e. two waves)
+// in / out rows are strided (1: SoA columns, 3: the rows [E, N, alt] of gsf_utm_to_wgs84_rows_dev); run_status (may be NULL): a track with
+// run_status != 0 gets NaN rows and its zone / south are not read; c3 / o3 (may be NULL): a third column copied through unchanged
 template <bool INVERSE>
-__global__ __launch_bounds__(256, GSF_UTM_OCC) void utm_kernel(const double* __restrict__ a, const double* __restrict__ bb,
-                                                  const int64_t* __restrict__ offsets, const int32_t* __restrict__ zone,
-                                                  const int32_t* __restrict__ south, double* __restrict__ o1, double* __restrict__ o2)
+__global__ __launch_bounds__(256, GSF_UTM_OCC) void utm_kernel(const double* __restrict__ a, const double* __restrict__ bb, const double* __restrict__ c3,
+                                                  int64_t in_stride, const int64_t* __restrict__ offsets, const int32_t* __restrict__ zone,
+                                                  const int32_t* __restrict__ south, const int32_t* __restrict__ run_status, double* __restrict__ o1,
+                                                  double* __restrict__ o2, double* __restrict__ o3, int64_t out_stride)
 {
     const int64_t b = blockIdx.x;
     const int64_t i0 = offsets[b], i1 = offsets[b + 1];
+    if (run_status && run_status[b] != 0) {
+        for (int64_t i = i0 + blockIdx.y * blockDim.x + threadIdx.x; i < i1; i += (int64_t)blockDim.x * gridDim.y) {
+            o1[i * out_stride] = NAN; o2[i * out_stride] = NAN;
+            if (o3) o3[i * out_stride] = NAN;
+        }
+        return;
+    }
     const double lon0 = 6.0 * (double)zone[b] - 183.0;
     const double fn = south[b] ? 10000000.0 : 0.0;
     const TmConsts c = tm_consts();
     for (int64_t i = i0 + blockIdx.y * blockDim.x + threadIdx.x; i < i1; i += (int64_t)blockDim.x * gridDim.y) {
         double r1, r2;
+        const double ai = a[i * in_stride], bi = bb[i * in_stride];
         if (!INVERSE) {
-            const double la = a[i], lo = bb[i];
+            const double la = ai, lo = bi;
             // validity mask of ref :259 -- rows the reference drops come back as NaN
             const bool ok = (fabs(la) <= 90.0) && (fabs(lo) <= 180.0) && (la != 0.0) && (lo != 0.0);
             utm_forward_point(c, la, lo, lon0, fn, r1, r2);
             if (!ok) { r1 = NAN; r2 = NAN; }
         } else {
-            utm_inverse_point(c, a[i], bb[i], lon0, fn, r1, r2);
+            utm_inverse_point(c, ai, bi, lon0, fn, r1, r2);
         }
-        o1[i] = r1; o2[i] = r2;
+        o1[i * out_stride] = r1; o2[i * out_stride] = r2;
+        if (o3) o3[i * out_stride] = c3[i * in_stride];
     }
 }
 
@@ -171,7 +183,8 @@ int gsf_utm_forward_batch_dev(gsf_ctx* ctx, const double* lat, const double* lon
     GSF_REQUIRE(B >= 0 && B <= 0x7fffffff, "bad B");
     if (B == 0) return GSF_OK;
     GSF_HIP(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(utm_kernel<false>, dim3((unsigned)B, blocks_per_traj(B)), dim3(256), 0, ctx->stream, lat, lon, offsets, zone, south, easting, northing);
+    hipLaunchKernelGGL(utm_kernel<false>, dim3((unsigned)B, blocks_per_traj(B)), dim3(256), 0, ctx->stream, lat, lon, nullptr, (int64_t)1, offsets, zone,
+                       south, nullptr, easting, northing, nullptr, (int64_t)1);
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }
@@ -183,7 +196,24 @@ int gsf_utm_inverse_batch_dev(gsf_ctx* ctx, const double* easting, const double*
     GSF_REQUIRE(B >= 0 && B <= 0x7fffffff, "bad B");
     if (B == 0) return GSF_OK;
     GSF_HIP(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(utm_kernel<true>, dim3((unsigned)B, blocks_per_traj(B)), dim3(256), 0, ctx->stream, easting, northing, offsets, zone, south, lat, lon);
+    hipLaunchKernelGGL(utm_kernel<true>, dim3((unsigned)B, blocks_per_traj(B)), dim3(256), 0, ctx->stream, easting, northing, nullptr, (int64_t)1, offsets, zone,
+                       south, nullptr, lat, lon, nullptr, (int64_t)1);
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
+}
+
+// step 7's numeric part (ref :1097, utm_to_wgs84 :291-296) for ragged tracks: rows [E, N, alt] -> [lon, lat, alt] with the SAME kernel as
+// gsf_utm_inverse_batch_dev / the drop-in's UtmProjector (one code object, so the bits agree), strided over the rows
+int gsf_utm_to_wgs84_rows_dev(gsf_ctx* ctx, const double* pos, const int64_t* offsets, const int32_t* zone, const int32_t* south,
+                              const int32_t* run_status, int64_t B, double* lonlatalt)
+{
+    GSF_REQUIRE(ctx && offsets && zone && south, "NULL argument");
+    GSF_REQUIRE(B >= 0 && B <= 0x7fffffff, "bad B");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(pos && lonlatalt, "NULL rows");
+    GSF_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(utm_kernel<true>, dim3((unsigned)B, blocks_per_traj(B)), dim3(256), 0, ctx->stream, pos, pos + 1, pos + 2, (int64_t)3, offsets,
+                       zone, south, run_status, lonlatalt + 1, lonlatalt, lonlatalt + 2, (int64_t)3);
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }

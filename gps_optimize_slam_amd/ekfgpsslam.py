@@ -88,6 +88,14 @@ def save_tum_wgs84(path, timestamps, lonlatalt, quaternions):
     np.savetxt(path, out, fmt=["%.6f"] + ["%.8f", "%.8f", "%.3f"] + ["%.8f"] * 4, header="timestamp lon lat alt qx qy qz qw (WGS84)", comments="")
 
 
+def wgs84_path(out_path_utm):
+    """The WGS84 file next to a UTM one (ref :1099-1100): '_utm.txt' -> '_wgs84.txt', else '.txt' -> '_wgs84.txt', else + '_wgs84.txt'."""
+    out = out_path_utm.replace("_utm.txt", "_wgs84.txt")
+    if out == out_path_utm:
+        out = out_path_utm.replace(".txt", "_wgs84.txt") if ".txt" in out_path_utm else out_path_utm + "_wgs84.txt"
+    return out
+
+
 # ---------------------------------------------------------------------------- geodesy (EKFGPSSLAM.py:127-134, :249-296)
 def auto_utm_projection(lons, lats):
     """(zone:int, hemisphere:str) from mean lon / mean lat (ref :127-134)."""
@@ -683,10 +691,7 @@ def run_fusion(slam_path, gps_path, out_path_utm=None, config=None, gt_gps_path=
     if out_path_utm:                                                                             # step 7
         save_tum_utm(out_path_utm, slam["timestamps"], pos, quat)
         wgs = utm_to_wgs84(pos, gps["projector"])
-        out_wgs = out_path_utm.replace("_utm.txt", "_wgs84.txt")
-        if out_wgs == out_path_utm:
-            out_wgs = out_path_utm.replace(".txt", "_wgs84.txt") if ".txt" in out_path_utm else out_path_utm + "_wgs84.txt"
-        save_tum_wgs84(out_wgs, slam["timestamps"], wgs, quat)
+        save_tum_wgs84(wgs84_path(out_path_utm), slam["timestamps"], wgs, quat)
     return {"slam": slam, "gps": gps, "ground_truth_gps": gt, "aligned": aligned, "valid": valid, "sim3_idx": idx, "R": R, "t": t, "s": s,
             "sim3_pos": sim3_pos, "sim3_quat": sim3_quat, "pos": pos, "quat": quat,
             "errors": {"primary": e_primary, "ground_truth": e_gt}, "plot_error_ref": plot_ref,

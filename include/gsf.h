@@ -519,6 +519,34 @@ GSF_API int gsf_fuse_pipeline_ragged(gsf_ctx *ctx, const double *ts, const doubl
                                      const uint8_t *valid, const int64_t *offsets, const gsf_ekf_config *cfg, int64_t B, double *R,
                                      double *t, double *s, double *pos_out, double *quat_out, int32_t *status);
 
+/* ---- step 7 of main_process_gui (EKFGPSSLAM.py:1085-1104): the corrected track as WGS84 rows and as the bytes of its TUM files ------------
+   Rows are flat over P poses with offsets int64[B+1], as in gsf_run_fusion_ragged_dev; any offsets work (a dense batch: b * N). */
+/* Rows [E, N, alt] (pos[P][3]) -> rows [lon deg, lat deg, alt] (lonlatalt[P][3]): utm_to_wgs84(corrected_pos, projector) (:1097, :291-296),
+   with projector = the primary log's zone / hemisphere (zone[B], south[B]; :266-283).  lon / lat are bit for bit what
+   gsf_utm_inverse_batch_dev (and the host form gsf_utm_inverse) returns for the same E, N -- the same kernel runs; alt is copied (:296).
+   run_status (may be NULL): a track with run_status[b] != 0 gets NaN rows and its zone / south are not read. */
+GSF_API int gsf_utm_to_wgs84_rows_dev(gsf_ctx *ctx, const double *pos, const int64_t *offsets, const int32_t *zone, const int32_t *south,
+                                      const int32_t *run_status, int64_t B, double *lonlatalt);
+/* the two np.savetxt formats of step 7 (comments='', fields joined by ' ', every line ends in '\n') */
+#define GSF_TUM_UTM 0      /* *_corrected_utm.txt (:1091-1092): fmt ['%.6f'] + ['%.6f']*3 + ['%.8f']*4, header "timestamp x y z qx qy qz qw (UTM)" */
+#define GSF_TUM_WGS84 1    /* *_corrected_wgs84.txt (:1098-1101): fmt ['%.6f'] + ['%.8f','%.8f','%.3f'] + ['%.8f']*4,
+                              header "timestamp lon lat alt qx qy qz qw (WGS84)" */
+#define GSF_TEXT_DEVICE 0  /* track_state: the track's file image was formatted on the device */
+#define GSF_TEXT_SKIPPED 1 /* run_status[b] != 0: no file (the reference raised before step 7), 0 bytes */
+#define GSF_TEXT_HOST 2    /* a finite value with |x| >= 2^63: 0 bytes here, the caller writes this track with np.savetxt */
+/* Byte-exact TUM files of tracks [0, B) of `offsets` (pass offsets + b0 to work in chunks): rows ts[P], xyz[P][3], quat[P][4] (for
+   GSF_TUM_WGS84, xyz = the rows of gsf_utm_to_wgs84_rows_dev).  Every field equals Python's '%.{p}f' of the float64 value (what np.savetxt
+   writes): the exact binary value rounded half to even, '-0.000000' for -0.0 and negatives that round to zero, 'nan' for a NaN of either
+   sign, 'inf' / '-inf'.  Two calls:
+   - SIZE (text == NULL): writes text_offsets[B+1] (byte ranges of each track's whole file image: header line, then one line per row; a 0-row
+     track gets the header alone) and track_state[B] (GSF_TEXT_*).  run_status may be NULL.
+   - WRITE (text != NULL, text_offsets[B] bytes, text_offsets / track_state of the size call with the same rows): writes every byte of those
+     ranges and nothing outside [0, text_offsets[B]).
+   Both calls derive a row's length from the same routine; the write pass places rows with a wave-wide scan recomputed per 64 rows (no
+   workspace).  Offsets must be non-decreasing within [0, P]; reads are clamped into [0, P) whatever they hold. */
+GSF_API int gsf_tum_text_dev(gsf_ctx *ctx, int32_t format, const double *ts, const double *xyz, const double *quat, const int64_t *offsets,
+                             const int32_t *run_status, int64_t B, int64_t P, int64_t *text_offsets, int32_t *track_state, uint8_t *text);
+
 /* ---- time alignment (dynamic_time_alignment, EKFGPSSLAM.py:325-387) ------------------------------ */
 /* B trajectories: SLAM stamps slam_t[slam_offsets[b]..), GNSS fixes gps_t / gps_p[.][3] at gps_offsets (any order, duplicates
    allowed: stable sort + first-of-equal-stamps).  Per gap-free segment (gap > max_gps_gap_threshold splits): not-a-knot cubic
