@@ -7,8 +7,8 @@
 //   * positions        p_i = (1-k_i)(p_{i-1}+u_i) + k_i z_i  -> prefix composition of affine maps
 //   * outage structure (start / recovery / sharp-turn gate)  -> 64-bit ballots + bit scans
 //   * per-outage RTS   x_s[k] = x_f[k] + (P_f[k]/P_p[r]) (x_f[r]-x_p[r])   (the product of the gains A_j telescopes)
-// so a wave takes 64 consecutive poses per iteration (lane = pose), runs log2(64) = 6 shuffle stages per scan and
-// carries ~30 scalars to the next 64 poses.  All loads/stores of a chunk are contiguous (the natural
+// so a wave takes 64 consecutive poses per iteration (lane = pose), runs log2(64) = 6 shuffle stages per scan (4 or 5 for a last
+// chunk of at most 16 / 32 poses: the cross-row stages cannot reach its lanes) and carries ~30 scalars to the next 64 poses.  All loads/stores of a chunk are contiguous (the natural
 // trajectory-major layout of stacked TUM files), B trajectories give B independent waves, and a 271-pose track costs
 // 5 iterations instead of 270 dependent steps: this is the low-latency / small-batch path (configs C1, C2); the
 // lane-per-trajectory kernel of gsf_ekf.hip is the streaming path for huge batches.
@@ -32,6 +32,24 @@ __global__ __launch_bounds__(64, 1) void ekf_wave_kernel(WaveArgs a, EkfConfig c
     static_assert(SMALLBATCH, "big-batch instantiations belong to gsf_ekf_wave_big.hip");
     wave_serial_body<PIPELINE, false, SMALLBATCH, 1, AXMODE>(a, cfg, (int64_t)blockIdx.x, (int)threadIdx.x);
 }
+// The builds for tracks whose last chunk ends below lane 16 | 32 (TAILNS 4 | 5): every chunk before the last is a full one, known at
+// compile time, and the last one runs its scans without the cross-row stages that cannot reach its lanes (wave_serial_chunks,
+// GSF_SCAN_STAGES_N; same bits as the kernel above) -- and the build for tracks of a multiple of 64 poses (WAVE_TAIL_FULL: full chunks
+// only).  The launcher picks the build from N.  They are OVERLOADS of the kernel above
+// -- the build travels in the argument's type -- and not a fourth template argument, so that a profile, bench.py and the tools keep
+// finding the kernel of a workload under the one name ekf_wave_kernel<PIPELINE, SMALLBATCH, AXMODE>.
+template <int TAILNS> struct WaveArgsTail { WaveArgs a; };
+#define GSF_WAVE_TAIL_KERNEL(T_)                                                                                                      \
+    template <bool PIPELINE, bool SMALLBATCH, int AXMODE>                                                                             \
+    __global__ __launch_bounds__(64, 1) void ekf_wave_kernel(WaveArgsTail<T_> w, EkfConfig cfg)                                       \
+    {                                                                                                                                 \
+        static_assert(SMALLBATCH, "big-batch instantiations belong to gsf_ekf_wave_big.hip");                                         \
+        wave_serial_body<PIPELINE, false, SMALLBATCH, 1, AXMODE, T_>(w.a, cfg, (int64_t)blockIdx.x, (int)threadIdx.x);                \
+    }
+GSF_WAVE_TAIL_KERNEL(4)
+GSF_WAVE_TAIL_KERNEL(5)
+GSF_WAVE_TAIL_KERNEL(WAVE_TAIL_FULL)
+#undef GSF_WAVE_TAIL_KERNEL
 
 
 // Two waves per trajectory for SMALL batches of the fused pipeline (one wave per SIMD, every wave in the same phase at the same
@@ -42,8 +60,8 @@ __global__ __launch_bounds__(64, 1) void ekf_wave_kernel(WaveArgs a, EkfConfig c
 #ifndef GSF_DUO_ROLE_SHIFT
 #define GSF_DUO_ROLE_SHIFT 2        // measured best of 0..3 at 1 000 tracks (22.6 vs 23.1-23.2 us; 23.6 us without the helper)
 #endif
-template <bool PIPELINE, int AXMODE>
-__global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgs a, EkfConfig cfg, int pv_stride)
+template <bool PIPELINE, int AXMODE, int TAILNS>
+__device__ __forceinline__ void wave_duo_body(const WaveArgs& a, const EkfConfig& cfg, const int pv_stride)
 {
     extern __shared__ double gsf_pv[];
     const int lane = threadIdx.x & 63;
@@ -53,12 +71,21 @@ __global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgs a, EkfConfig
     const bool helper = ((threadIdx.x >> 6) ^ ((blockIdx.x >> GSF_DUO_ROLE_SHIFT) & 1u)) != 0u;
     if (a.N <= 0) { if (!helper && lane == 0 && a.status) a.status[b] = 0; return; }   // empty tracks: both waves leave before any barrier
     if (helper) {
-        wave_variance_helper(a, cfg, b, lane, gsf_pv, pv_stride);
+        wave_variance_helper<TAILNS>(a, cfg, b, lane, gsf_pv, pv_stride);
         __syncthreads();
         return;
     }
-    wave_serial_body<PIPELINE, true, true, 1, AXMODE>(a, cfg, b, lane, gsf_pv, pv_stride);
+    wave_serial_body<PIPELINE, true, true, 1, AXMODE, TAILNS>(a, cfg, b, lane, gsf_pv, pv_stride);
 }
+template <bool PIPELINE, int AXMODE>
+__global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgs a, EkfConfig cfg, int pv_stride) { wave_duo_body<PIPELINE, AXMODE, 6>(a, cfg, pv_stride); }
+// (the builds with the last chunk's scans sized, as overloads under the same name: see ekf_wave_kernel)
+template <bool PIPELINE, int AXMODE>
+__global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgsTail<4> w, EkfConfig cfg, int pv_stride) { wave_duo_body<PIPELINE, AXMODE, 4>(w.a, cfg, pv_stride); }
+template <bool PIPELINE, int AXMODE>
+__global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgsTail<5> w, EkfConfig cfg, int pv_stride) { wave_duo_body<PIPELINE, AXMODE, 5>(w.a, cfg, pv_stride); }
+template <bool PIPELINE, int AXMODE>
+__global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgsTail<WAVE_TAIL_FULL> w, EkfConfig cfg, int pv_stride) { wave_duo_body<PIPELINE, AXMODE, WAVE_TAIL_FULL>(w.a, cfg, pv_stride); }
 
 }  // namespace
 
@@ -78,6 +105,11 @@ int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double*
         return launch_ekf_block(ctx, pipeline, ts, pos, quat, gps, valid, init_pos, init_quat, cfg, B, N, R, t, s, pos_out, quat_out, status);
     WaveArgs a{ ts, pos, quat, gps, valid, init_pos, init_quat, R, t, s, pos_out, quat_out, status, B, N, offsets, pipeline ? ctx->fit_rows : FitRows{ 0, 0, 0.0, 0.0 } };
     const EkfConfig k = to_core(cfg);
+    // the build whose last chunk runs only the scan stages that reach its lanes, or that knows every chunk to be full (gsf_set_option
+    // "tail_scan_stages").  Uniform track
+    // length only: a ragged batch has no single last-chunk length, and the big-batch build has no registers for a second instance of the
+    // chunk body (it would spill at three waves per SIMD).  Same bits from every build, so the choice breaks no shard invariance.
+    const int tail = (ctx->tail_scan_stages != 0 && !offsets) ? wave_tail_stages(N) : 6;
     // x and y share their (P0, Q, R) and z does not (the default CONFIG): the build with that choice of scans compiled in
     const bool xy = k.P0[1] == k.P0[0] && k.Qps[1] == k.Qps[0] && k.Rm[1] == k.Rm[0] &&
                     !(k.P0[2] == k.P0[0] && k.Qps[2] == k.Qps[0] && k.Rm[2] == k.Rm[0]);
@@ -89,8 +121,11 @@ int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double*
     // one SIMD) lost its edge with the shorter fit (20.2 vs 19.5 us at 1 000) and lives in tools/experiments/ now.
     if (pipeline && !offsets && ctx->duo_kernel != 0 && N > 64 && N <= 640 && (ctx->duo_kernel == 1 || (ctx->duo_kernel == -1 && B <= 256))) {
         const int stride = (int)((N + 1) & ~(int64_t)1);
-        if (xy) hipLaunchKernelGGL((ekf_wave_duo_kernel<true, 1>), dim3((unsigned)B), dim3(128), (size_t)stride * 9 * sizeof(double), ctx->stream, a, k, stride);
-        else hipLaunchKernelGGL((ekf_wave_duo_kernel<true, 0>), dim3((unsigned)B), dim3(128), (size_t)stride * 9 * sizeof(double), ctx->stream, a, k, stride);
+#define GSF_LAUNCH_DUO_A(X_, A_) hipLaunchKernelGGL((ekf_wave_duo_kernel<true, X_>), dim3((unsigned)B), dim3(128), (size_t)stride * 9 * sizeof(double), ctx->stream, A_, k, stride)
+#define GSF_LAUNCH_DUO(X_) do { if (tail == 4) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<4>{ a }); else if (tail == 5) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<5>{ a }); else if (tail == WAVE_TAIL_FULL) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<WAVE_TAIL_FULL>{ a }); else GSF_LAUNCH_DUO_A(X_, a); } while (0)
+        if (xy) GSF_LAUNCH_DUO(1); else GSF_LAUNCH_DUO(0);
+#undef GSF_LAUNCH_DUO
+#undef GSF_LAUNCH_DUO_A
         GSF_HIP(hipGetLastError());
         return GSF_OK;
     }
@@ -99,10 +134,12 @@ int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double*
         const bool small = B <= 2048;
         if (!small)
             return launch_ekf_wave_big(ctx, pipeline, xy, ts, pos, quat, gps, valid, init_pos, init_quat, cfg, B, N, R, t, s, pos_out, quat_out, status, offsets);
-#define GSF_LAUNCH_WAVE(P_, X_) hipLaunchKernelGGL((ekf_wave_kernel<P_, true, X_>), dim3((unsigned)B), dim3(64), 0, ctx->stream, a, k)
+#define GSF_LAUNCH_WAVE_A(P_, X_, A_) hipLaunchKernelGGL((ekf_wave_kernel<P_, true, X_>), dim3((unsigned)B), dim3(64), 0, ctx->stream, A_, k)
+#define GSF_LAUNCH_WAVE(P_, X_) do { if (tail == 4) GSF_LAUNCH_WAVE_A(P_, X_, WaveArgsTail<4>{ a }); else if (tail == 5) GSF_LAUNCH_WAVE_A(P_, X_, WaveArgsTail<5>{ a }); else if (tail == WAVE_TAIL_FULL) GSF_LAUNCH_WAVE_A(P_, X_, WaveArgsTail<WAVE_TAIL_FULL>{ a }); else GSF_LAUNCH_WAVE_A(P_, X_, a); } while (0)
         if (pipeline) { if (xy) GSF_LAUNCH_WAVE(true, 1); else GSF_LAUNCH_WAVE(true, 0); }
         else { if (xy) GSF_LAUNCH_WAVE(false, 1); else GSF_LAUNCH_WAVE(false, 0); }
 #undef GSF_LAUNCH_WAVE
+#undef GSF_LAUNCH_WAVE_A
     }
     GSF_HIP(hipGetLastError());
     return GSF_OK;

@@ -42,6 +42,7 @@ struct gsf_ctx {
     int prefilter_first_batch; // trials the pre-filter chain draws and scores before its first look at scikit-learn's stopping rule (gsf_set_option "prefilter_first_batch")
     int ransac_probe_trials; // ... trials the early-exit probe draws and scores itself before the wide kernels take the rest (gsf_set_option "ransac_probe_trials")
     int duo_kernel;        // two-wave pipeline kernel for small batches (gsf_set_option "duo_kernel"): -1 automatic, 0 never, 1 always
+    int tail_scan_stages;  // wave kernels: scans of a short last chunk sized by its last active lane (gsf_set_option "tail_scan_stages"): 1 default, 0 always six stages (same bits)
     gsf::FitRows fit_rows; // rows of the fused chains' Sim3 fit (gsf_set_sim3_rows); mode 0 = all valid rows
     int64_t lane_min_traj; // time-major batches with fewer trajectories are transposed and run by the wave kernel (gsf_set_option "lane_min_traj")
 };

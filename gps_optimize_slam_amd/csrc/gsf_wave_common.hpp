@@ -15,10 +15,14 @@ typedef unsigned long long u64;
 // monoid, so every stage is an unconditional "other o mine".  ds_bpermute (__shfl) is kept only for per-lane indices.
 constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114, DPP_ROW_SHR8 = 0x118;
 constexpr int DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143, DPP_WAVE_SHR1 = 0x138;
+// not a DPP control: "no lane has a source", i.e. every lane keeps `old` -- what a stage is for the rows its row mask leaves out
+// (GSF_SCAN_STAGES_N below).  Nothing is moved; `old` stays a compile-time constant.
+constexpr int DPP_NO_SOURCE = -1;
 
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp(double old, double v)
 {
+    if (CTRL == DPP_NO_SOURCE) return old;
     // `old` is tied to the destination: materialise it as ONE 64-bit register pair (a single v_mov_b64) instead of two
     // 32-bit constant moves -- the empty asm pins the value in a VGPR pair before it is split into halves
     double oo = old;
@@ -33,6 +37,7 @@ __device__ __forceinline__ double dpp(double old, double v)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp0(double v)
 {
+    if (CTRL == DPP_NO_SOURCE) return 0.0;
     if (ROW_MASK != 0xf) return dpp<CTRL, ROW_MASK>(0.0, v);
     const long long x = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
@@ -59,6 +64,27 @@ __device__ __forceinline__ Vec3 lane_bcast(const Vec3& v, int s) { return Vec3{ 
 __device__ __forceinline__ double shidx(double v, int src) { return __shfl(v, src, 64); }          // per-lane source index
 #define GSF_SCAN_STAGES(STAGE) STAGE(DPP_ROW_SHR1, 0xf) STAGE(DPP_ROW_SHR2, 0xf) STAGE(DPP_ROW_SHR4, 0xf) STAGE(DPP_ROW_SHR8, 0xf) \
                                STAGE(DPP_ROW_BCAST15, 0xa) STAGE(DPP_ROW_BCAST31, 0xc)
+// The same scan for a chunk whose last active lane is below 16 (NS = 4) or below 32 (NS = 5): the two row_bcast stages only ever change
+// lanes 16-63 (row_bcast:15) and 32-63 (row_bcast:31), so a short tail chunk does not run them -- they are the expensive stages (a
+// cross-row move costs 7.75 cycles against 4.46 for row_shr).  For the lanes that ARE read (row 0, rows 0-1) such a stage is "other o
+// mine" with the identity as `other`; that is not always a no-op on the bits (al * 0.0 + be turns a -0.0 into +0.0 and a non-finite
+// factor into NaN), so each stage left out is replaced by exactly that expression with the identity as a constant: a handful of
+// multiply-adds, no cross-lane move, the same bits as the six-stage scan in every lane up to the last active one.  NS = 6 is
+// GSF_SCAN_STAGES itself.  (Lanes past the last active one hold values the six-stage scan would not give them; nothing reads them.)
+#define GSF_SCAN_STAGES_N(NS, STAGE) STAGE(DPP_ROW_SHR1, 0xf) STAGE(DPP_ROW_SHR2, 0xf) STAGE(DPP_ROW_SHR4, 0xf) STAGE(DPP_ROW_SHR8, 0xf) \
+                               if constexpr ((NS) >= 5) STAGE(DPP_ROW_BCAST15, 0xa) else STAGE(DPP_NO_SOURCE, 0x0)                      \
+                               if constexpr ((NS) >= 6) STAGE(DPP_ROW_BCAST31, 0xc) else STAGE(DPP_NO_SOURCE, 0x0)
+template <int V> struct ScanStages { static constexpr int value = V; };
+// TAILNS of a kernel instance: the stages the scans of the track's LAST chunk run.  The launcher picks the instance from the track
+// length (wave_tail_stages), so the kernel itself carries no test: TAILNS = 6 is the kernel without sized scans, for any length;
+// WAVE_TAIL_FULL says that the length is a multiple of 64, i.e. that EVERY chunk is a full one (six stages, no partial chunk at all).
+constexpr int WAVE_TAIL_FULL = 7;
+__host__ __device__ inline int wave_tail_stages(const int64_t N)
+{
+    if (N <= 0) return 6;
+    const int last = (int)((N - 1) & 63);                                 // last active lane of the last chunk
+    return last == 63 ? WAVE_TAIL_FULL : (last < 16 ? 4 : (last < 32 ? 5 : 6));
+}
 // sum over the wave: inclusive DPP scan, total read from lane 63 (wave-uniform result)
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -717,6 +743,7 @@ struct AxisVar { double Pf, Pm, kg; };
 // the scan on its own (identity carry): lane i holds the composition of the maps of poses first..i of the chunk; lanes that do not
 // step hold the identity, so lane 63 always holds the chunk's total
 struct Moebius { double A, B, C, D; };
+template <int NS = 6>
 __device__ __forceinline__ Moebius variance_scan(const double q, const double rr, const double dt, const bool stepping, const bool avail)
 {
     const double b0 = q * dt;
@@ -727,7 +754,7 @@ __device__ __forceinline__ Moebius variance_scan(const double q, const double rr
         const double oA = dpp<CTRL, RM>(1.0, A), oB = dpp0<CTRL, RM>(Bm), oC = dpp0<CTRL, RM>(Cm), oD = dpp<CTRL, RM>(1.0, Dm); \
         const double nA = A * oA + Bm * oC, nB = A * oB + Bm * oD, nC = Cm * oA + Dm * oC, nD = Cm * oB + Dm * oD;                  \
         A = nA; Bm = nB; Cm = nC; Dm = nD; }
-    GSF_SCAN_STAGES(GSF_MSTAGE)
+    GSF_SCAN_STAGES_N(NS, GSF_MSTAGE)
 #undef GSF_MSTAGE
     return Moebius{ A, Bm, Cm, Dm };
 }
@@ -741,23 +768,27 @@ __device__ __forceinline__ AxisVar variance_finish(const Moebius& m, const doubl
     v.kg = v.Pm * fast_rcp(v.Pm + rr);                                   // Kalman gain if the fix is used
     return v;
 }
+template <int NS = 6>
 __device__ __forceinline__ AxisVar variance_axis(const double q, const double rr, const double dt, const bool stepping, const bool avail, const double cPc)
 {
-    return variance_finish(variance_scan(q, rr, dt, stepping, avail), q, rr, dt, cPc);
+    return variance_finish(variance_scan<NS>(q, rr, dt, stepping, avail), q, rr, dt, cPc);
 }
 // (scalar arguments and constant indices only: a helper that indexes its caller's arrays dynamically puts them into scratch)
+// NS: scan stages the chunk needs (GSF_SCAN_STAGES_N) -- same bits for every NS that covers the chunk's last active lane
+template <int NS = 6>
 __device__ __forceinline__ void variance_chunk(const EkfConfig& cfg, const int same1, const int same2, const double dt, const bool stepping,
                                                const bool avail, const double cP0, const double cP1, const double cP2,
                                                AxisVar& v0, AxisVar& v1, AxisVar& v2)
 {
-    v0 = variance_axis(cfg.Qps[0], cfg.Rm[0], dt, stepping, avail, cP0);
-    if (same1 == 0) v1 = v0; else v1 = variance_axis(cfg.Qps[1], cfg.Rm[1], dt, stepping, avail, cP1);
-    if (same2 == 0) v2 = v0; else if (same2 == 1) v2 = v1; else v2 = variance_axis(cfg.Qps[2], cfg.Rm[2], dt, stepping, avail, cP2);
+    v0 = variance_axis<NS>(cfg.Qps[0], cfg.Rm[0], dt, stepping, avail, cP0);
+    if (same1 == 0) v1 = v0; else v1 = variance_axis<NS>(cfg.Qps[1], cfg.Rm[1], dt, stepping, avail, cP1);
+    if (same2 == 0) v2 = v0; else if (same2 == 1) v2 = v1; else v2 = variance_axis<NS>(cfg.Qps[2], cfg.Rm[2], dt, stepping, avail, cP2);
 }
 
 // The helper wave of the two-wave kernel: variances of EVERY chunk of the track, written to LDS (pv[(axis*3 + {Pf,Pm,kg}) * stride
 // + pose]) while the main wave is busy with the fit.  It reads only what the variance recursion depends on: stamps, mask, NaN-ness
 // of the fixes.  Same flags, same dt, same variance_chunk() as the chunked body.
+template <int TAILNS = 6>
 __device__ __forceinline__ void wave_variance_helper(const WaveArgs& a, const EkfConfig& cfg, const int64_t b, const int lane, double* pv, const int pv_stride)
 {
     int64_t base, N; traj_span(a, b, base, N);
@@ -789,7 +820,9 @@ __device__ __forceinline__ void wave_variance_helper(const WaveArgs& a, const Ek
         const double dt = fmax(1e-6, t - prev_lane(c_t, t));             // ref :865
         const bool avail = stepping && vraw && !(isnan(z0) || isnan(z1) || isnan(z2));   // ref :867-869
         AxisVar v0, v1, v2;
-        variance_chunk(cfg, same_axis[1], same_axis[2], dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
+        // (the last chunk's scans sized as in wave_serial_chunks: the same bits either way)
+        if (TAILNS < 6 && c0 + 64 >= N) variance_chunk<(TAILNS < 6 ? TAILNS : 6)>(cfg, same_axis[1], same_axis[2], dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
+        else variance_chunk<6>(cfg, same_axis[1], same_axis[2], dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
         const double Pf[3] = { v0.Pf, v1.Pf, v2.Pf }, Pm[3] = { v0.Pm, v1.Pm, v2.Pm }, kg[3] = { v0.kg, v1.kg, v2.kg };
         if (active) {
 #pragma unroll
@@ -821,7 +854,10 @@ template <> struct RingStore<0> {
 // AXMODE 1: the caller has checked on the host that axes x and y share (P0, Q, R) and z does not -- the default CONFIG -- so the
 // choice of scans is compiled in and the variance scans, the orientation and the x/y and z position scans sit in straight-line
 // code that the scheduler can interleave (a lone wave issues dependent FP64 / DPP work every 6-7 cycles, independent work every 4.5).
-template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0>
+// TAILNS (4 | 5): the caller guarantees that the track's last chunk ends below lane 16 | 32 (wave_tail_stages); that chunk then runs
+// its scans with 4 | 5 stages (GSF_SCAN_STAGES_N: same bits).  TAILNS = 6: every chunk runs the six-stage body.  WAVE_TAIL_FULL: the caller
+// guarantees that N is a multiple of 64.
+template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6>
 __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfConfig& cfg, const int64_t b, const int lane, const int64_t base,
                                                    const int64_t N, const Vec3& p0, const Quat& q0, const int32_t fit,
                                                    typename NextChunk<GSF_WIDE(SMALLBATCH)>::type nxt,
@@ -875,9 +911,11 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
     const Quat cq0 = cq;
     Quat Cq = lane_bcast(quat_mul(cq, quat_conj(c_r)), 0);
     bool cq_fresh = true;
-    for (int64_t c0 = 0; c0 < N; c0 += 64) {
+    // One chunk: 64 poses starting at c0, L = last active lane.  NS (ScanStages<4 | 5 | 6>) = scan stages compiled into this instance of the
+    // body: 6 is the full chunk; 4 and 5 serve a short last chunk (GSF_SCAN_STAGES_N).
+    auto chunk_body = [&](auto ns_tag, const int64_t c0, const int L) __attribute__((always_inline)) {
+        constexpr int NS = decltype(ns_tag)::value;
         const int64_t i = c0 + lane;
-        const int L = (int)((N - c0 < 64) ? (N - c0 - 1) : 63);          // last active lane of this chunk
         // Lane predicates that depend on the lane index alone are formed as 64-bit masks on the SCALAR unit and handed to the lanes with
         // inverse_ballot (a register copy): no compare / select / shift of the vector unit is spent on the outage structure.
         const u64 act_mask = (L >= 63) ? ~0ull : ((2ull << L) - 1ull);   // lanes 0..L
@@ -983,7 +1021,7 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
             for (int c = 0; c < 3; ++c) { Pf[c] = pv[(c * 3 + 0) * pv_stride + il]; Pm[c] = pv[(c * 3 + 1) * pv_stride + il]; kg[c] = pv[(c * 3 + 2) * pv_stride + il]; }
         } else {
             AxisVar v0, v1, v2;
-            variance_chunk(cfg, same_axis[1], same_axis[2], dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
+            variance_chunk<NS>(cfg, same_axis[1], same_axis[2], dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
             Pf[0] = v0.Pf; Pf[1] = v1.Pf; Pf[2] = v2.Pf; Pm[0] = v0.Pm; Pm[1] = v1.Pm; Pm[2] = v2.Pm; kg[0] = v0.kg; kg[1] = v1.kg; kg[2] = v2.kg;
         }
 
@@ -1002,7 +1040,7 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
             Quat D = dq;
             const Quat QID{ 0.0, 0.0, 0.0, 1.0 };
 #define GSF_QSTAGE(CTRL, RM) { const Quat o = dpp<CTRL, RM>(QID, D); D = quat_mul(o, D); }
-            GSF_SCAN_STAGES(GSF_QSTAGE)
+            GSF_SCAN_STAGES_N(NS, GSF_QSTAGE)
 #undef GSF_QSTAGE
             qi = ekf_normalize(quat_mul(cq, D));                         // one normalisation per chunk
             const Quat q_prev = prev_lane(cq, qi);
@@ -1026,9 +1064,9 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         // x and y share the gain in the default CONFIG, hence the multiplicative part: one joint scan of (al; be_x, be_y)
 #define GSF_ASTAGE_XY(CTRL, RM) { const double oa = dpp<CTRL, RM>(1.0, al[0]), ob0 = dpp0<CTRL, RM>(be[0]), ob1 = dpp0<CTRL, RM>(be[1]); \
                                   be[0] = al[0] * ob0 + be[0]; be[1] = al[0] * ob1 + be[1]; al[0] = al[0] * oa; }
-        if (same_axis[1] == 0) { GSF_SCAN_STAGES(GSF_ASTAGE_XY) }
-        else { GSF_SCAN_STAGES(GSF_ASTAGE_X) GSF_SCAN_STAGES(GSF_ASTAGE_Y) }
-        GSF_SCAN_STAGES(GSF_ASTAGE_Z)
+        if (same_axis[1] == 0) { GSF_SCAN_STAGES_N(NS, GSF_ASTAGE_XY) }
+        else { GSF_SCAN_STAGES_N(NS, GSF_ASTAGE_X) GSF_SCAN_STAGES_N(NS, GSF_ASTAGE_Y) }
+        GSF_SCAN_STAGES_N(NS, GSF_ASTAGE_Z)
 #undef GSF_ASTAGE_XY
 #undef GSF_ASTAGE_Z
 #undef GSF_ASTAGE_Y
@@ -1162,12 +1200,26 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
             __builtin_nontemporal_store(qi.z, &qob[i * 4 + 2]); __builtin_nontemporal_store(qi.w, &qob[i * 4 + 3]);
         }
         GSF_STAMP(8 + (int)(c0 / 64));
+    };
+    // Only the last chunk of a track can be a short one: every chunk before it runs the six-stage instance, which is the whole loop
+    // of a TAILNS = 6 kernel; the sized instance follows the loop, without a test (the launcher chose the kernel by the track length).
+    // In a sized kernel the loop's chunks are FULL ones by construction, so L = 63 is a constant there and the lane masks built from it
+    // fold away -- measured, that is worth as much as the stages the last chunk skips (HISTORY.md, "Sized scans for a short last chunk").
+    // (Three instances side by side in ONE loop, chosen per iteration, were measured first: the full chunk lost 130 cycles to them.)
+    if constexpr (TAILNS == 6) {
+        for (int64_t c0 = 0; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, c0, (int)((N - c0 < 64) ? (N - c0 - 1) : 63));
+    } else if constexpr (TAILNS == WAVE_TAIL_FULL) {
+        for (int64_t c0 = 0; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, c0, 63);
+    } else {
+        int64_t c0 = 0;
+        for (; c0 + 64 < N; c0 += 64) chunk_body(ScanStages<6>{}, c0, 63);
+        chunk_body(ScanStages<TAILNS>{}, c0, (int)(N - c0 - 1));
     }
     GSF_STAMP_FLUSH();
     if (lane == 0 && GSF_STATUS_PTR(a)) a.status[b] = (status | (c_prev_avail ? 0 : ST_ENDED_IN_OUTAGE)) | (PIPELINE ? (fit << 8) : 0);
 }
 
-template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0>
+template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6>
 __device__ __forceinline__ void wave_serial_body(const WaveArgs& a, const EkfConfig& cfg, const int64_t b, const int lane,
                                                  const double* pv = nullptr, const int pv_stride = 0, const int ring_slot = 0)
 {
@@ -1193,7 +1245,7 @@ __device__ __forceinline__ void wave_serial_body(const WaveArgs& a, const EkfCon
     GSF_STAMP(6);
     if (PREVAR) __syncthreads();                                         // the helper wave has written every chunk's variances
 
-    wave_serial_chunks<PIPELINE, PREVAR, SMALLBATCH, RINGS, AXMODE>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, pv, pv_stride, ring_slot);
+    wave_serial_chunks<PIPELINE, PREVAR, SMALLBATCH, RINGS, AXMODE, TAILNS>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, pv, pv_stride, ring_slot);
 }
 
 
