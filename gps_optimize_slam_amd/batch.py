@@ -212,7 +212,7 @@ def run_fusion_batch(gb, mt_state, config=None, early_exit=True, skip_seconds=5.
     mt_state (B, 625): every trajectory's NumPy legacy generator (mt19937_seed / mt19937_from_numpy), advanced by the pre-filter's and
     the fit's draws in the reference's order; early_exit as in fuse_pipeline_robust_batch (the pre-filter's draws are unaffected).
     projected=True: gb.gps_llh already holds (E, N, alt) rows -- what load_gps_data's projection returns -- and the chain starts at the
-    pre-filter.  The pre-filter covers logs of any rate (scikit-learn's sampler on its permutation and tracking-selection routes); a log is
+    pre-filter; zone / south are then None (there is no projector, as in run_fusion_ragged).  The pre-filter covers logs of any rate (scikit-learn's sampler on its permutation and tracking-selection routes); a log is
     flagged RUN_PREFILTER_UNHANDLED only for unsorted stamps in the sliding mode or more than max_windows windows.  Returns a RunResult."""
     g = config or CONFIG
     ctx = context()
@@ -224,7 +224,8 @@ def run_fusion_batch(gb, mt_state, config=None, early_exit=True, skip_seconds=5.
     total = int(gb.gps_t.numel())
     out = FusedPoses(LAYOUT_TRAJ_MAJOR, B, N, dev)
     r = RunResult(fused=out, R=torch.empty((B, 9), **f), t=torch.empty((B, 3), **f), s=torch.empty((B,), **f), n_inliers=torch.empty((B,), **i32),
-                  zone=torch.empty((B,), **i32), south=torch.empty((B,), **i32), gps_utm=gb.gps_llh.clone() if projected else torch.empty((total, 3), **f),
+                  zone=None if projected else torch.empty((B,), **i32), south=None if projected else torch.empty((B,), **i32),
+                  gps_utm=gb.gps_llh.clone() if projected else torch.empty((total, 3), **f),
                   gps_keep=torch.empty((total,), dtype=torch.uint8, device=dev), aligned=torch.empty((B, N, 3), **f),
                   valid=torch.empty((B, N), dtype=torch.uint8, device=dev), sim3_pos=torch.empty((B, N, 3), **f), err_stats=torch.empty((3, B, 4), **f),
                   run_status=torch.empty((B,), **i32), inlier_mask=torch.empty((B, N), dtype=torch.uint8, device=dev) if want_mask else None,
@@ -371,9 +372,8 @@ def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5
     f = dict(dtype=torch.float64, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
     u8 = dict(dtype=torch.uint8, device=dev)
-    out = FusedPoses(LAYOUT_TRAJ_MAJOR, 1, P, dev)
+    out = FusedPoses(LAYOUT_TRAJ_MAJOR, 1, P, dev, status=torch.empty((B,), **i32))
     out.pos, out.quat = out.pos.view(P, 3), out.quat.view(P, 4)
-    out.status = torch.empty((B,), **i32)
     r = RunResult(fused=out, R=torch.empty((B, 9), **f), t=torch.empty((B, 3), **f), s=torch.empty((B,), **f), n_inliers=torch.empty((B,), **i32),
                   zone=None if projected else torch.empty((B,), **i32), south=None if projected else torch.empty((B,), **i32),
                   gps_utm=rb.gps_llh.clone() if projected else torch.empty((T, 3), **f), gps_keep=torch.empty((T,), **u8),
@@ -556,9 +556,10 @@ def save_fusion_ragged(rb, r, utm_paths):
 
 class FusedPoses:
     """Fused poses of a batch.  pos and quat are views of ONE allocation `buf` = [pos | quat] (7 doubles per pose), so the
-    multi-GPU collect is a single all-gather of `buf`.  `buf` may be a caller-provided slice of a larger arena."""
+    multi-GPU collect is a single all-gather of `buf`.  `buf` may be a caller-provided slice of a larger arena; `status` a
+    caller-provided int32 tensor (the ragged whole run has one word per track, not per row of its flat pose array)."""
 
-    def __init__(self, layout, B, N, device="cuda", buf=None):
+    def __init__(self, layout, B, N, device="cuda", buf=None, status=None):
         _, s_pos, s_quat, _, _ = shapes(layout, B, N)
         self.layout, self.B, self.N = layout, B, N
         P = B * N
@@ -569,7 +570,7 @@ class FusedPoses:
         self.buf = buf.view(-1)
         self.pos = self.buf[: P * 3].view(s_pos)
         self.quat = self.buf[P * 3:].view(s_quat)
-        self.status = torch.empty((B,), dtype=torch.int32, device=self.buf.device)
+        self.status = torch.empty((B,), dtype=torch.int32, device=self.buf.device) if status is None else status
 
     def host_traj_major(self):
         """-> (pos (B,N,3), quat (B,N,4), status (B,)) numpy"""

@@ -37,6 +37,7 @@ int ensure_scratch(gsf_ctx* ctx, size_t bytes)
     }
     GSF_HIP(hipMalloc(&ctx->scratch, bytes));
     ctx->scratch_bytes = bytes;
+    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->scratch, ctx->scratch_bytes, (uint64_t)ctx->poison);
     return GSF_OK;
 }
 
@@ -50,6 +51,7 @@ int ensure_rng_scratch(gsf_ctx* ctx, size_t bytes)
     }
     GSF_HIP(hipMalloc(&ctx->rng_scratch, bytes + bytes / 4));
     ctx->rng_scratch_bytes = bytes + bytes / 4;
+    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->rng_scratch, ctx->rng_scratch_bytes, (uint64_t)ctx->poison);
     return GSF_OK;
 }
 
@@ -63,6 +65,7 @@ int ensure_k2b_scratch(gsf_ctx* ctx, size_t bytes)
     }
     GSF_HIP(hipMalloc(&ctx->k2b_scratch, bytes + bytes / 4));
     ctx->k2b_scratch_bytes = bytes + bytes / 4;
+    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->k2b_scratch, ctx->k2b_scratch_bytes, (uint64_t)ctx->poison);
     return GSF_OK;
 }
 
@@ -76,6 +79,7 @@ int ensure_run_scratch(gsf_ctx* ctx, size_t bytes)
     }
     GSF_HIP(hipMalloc(&ctx->run_scratch, bytes + bytes / 4));
     ctx->run_scratch_bytes = bytes + bytes / 4;
+    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->run_scratch, ctx->run_scratch_bytes, (uint64_t)ctx->poison);
     return GSF_OK;
 }
 
@@ -89,6 +93,7 @@ int ensure_rows_scratch(gsf_ctx* ctx, size_t bytes)
     }
     GSF_HIP(hipMalloc(&ctx->rows_scratch, bytes + bytes / 4));
     ctx->rows_scratch_bytes = bytes + bytes / 4;
+    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->rows_scratch, ctx->rows_scratch_bytes, (uint64_t)ctx->poison);
     return GSF_OK;
 }
 
@@ -109,15 +114,25 @@ static int ensure_arena(void** p, size_t* have, size_t bytes, bool pinned, hipSt
     return GSF_OK;
 }
 
+static void fill_words_host(void* p, size_t bytes, uint64_t word)
+{
+    for (size_t i = 0; i < bytes; ++i) ((unsigned char*)p)[i] = (unsigned char)(word >> (8 * (i & 7)));
+}
+
 Staging::Staging(gsf_ctx* ctx, size_t payload_bytes, int n_arrays) : ctx_(ctx)
 {
     cap_ = payload_bytes + (size_t)256 * (size_t)(n_arrays + 1);
     direct_ = cap_ > PINNED_MAX;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) { rc_ = fail_hip(e, "hipSetDevice"); return; }
+    const void* const stage0 = ctx->stage; const void* const pinned0 = ctx->pinned;
     rc_ = ensure_arena(&ctx->stage, &ctx->stage_bytes, cap_, false, ctx->stream);
     if (rc_ == GSF_OK && !direct_) rc_ = ensure_arena(&ctx->pinned, &ctx->pinned_bytes, cap_, true, ctx->stream);
     d_ = (char*)ctx->stage; h_ = (char*)ctx->pinned;
+    if (ctx->poison >= 0 && rc_ == GSF_OK) {                              // an arena that has just grown is dirtied like the others
+        if (ctx->stage != stage0) rc_ = launch_fill_words(ctx, ctx->stage, ctx->stage_bytes, (uint64_t)ctx->poison);
+        if (ctx->pinned && ctx->pinned != pinned0) fill_words_host(ctx->pinned, ctx->pinned_bytes, (uint64_t)ctx->poison);
+    }
 }
 
 void* Staging::take(size_t bytes, size_t& at)
@@ -226,7 +241,7 @@ static int create_common(int device_id, hipStream_t stream, bool owns, gsf_ctx**
     gsf_ctx* c = new gsf_ctx();
     c->device = device_id; c->stream = stream; c->owns_stream = owns; c->scratch = nullptr; c->scratch_bytes = 0; c->stage = nullptr; c->stage_bytes = 0; c->pinned = nullptr; c->pinned_bytes = 0;
     c->rng_scratch = nullptr; c->rng_scratch_bytes = 0; c->rows_scratch = nullptr; c->rows_scratch_bytes = 0; c->run_scratch = nullptr; c->run_scratch_bytes = 0; c->tape_draws = -1; c->small_scratch = nullptr; c->k2b_screen = 1; c->k2b_scratch = nullptr; c->k2b_scratch_bytes = 0;
-    c->ekf_variant = 0; c->synth_variant = 0; c->block_kernel = -1; c->duo_kernel = -1; c->lane_min_traj = 32768; c->tail_scan_stages = 1;
+    c->ekf_variant = 0; c->synth_variant = 0; c->block_kernel = -1; c->duo_kernel = -1; c->lane_min_traj = 32768; c->poison = -1; c->tail_scan_stages = 1;
     c->ransac_early_exit = 0; c->ransac_probe_trials = 64; c->prefilter_first_batch = 1; c->prefilter_speculate = 1; c->prefilter_miss_batch = 4;
     // the fused chains fit the rows main_process_gui hands to its fit (ref :973-998) under the reference's CONFIG defaults (:34, :53, :37)
     // unless the caller says otherwise (gsf_set_sim3_rows): a raw C caller of gsf_fuse_pipeline_* gets steps 3-5 as the reference runs them
@@ -347,6 +362,20 @@ int gsf_set_option(gsf_ctx* ctx, const char* key, int64_t value)
     if (strcmp(key, "lane_min_traj") == 0) {
         if (value < 0) { set_error("gsf_set_option: lane_min_traj must be >= 0"); return GSF_ERR_INVALID_ARG; }
         ctx->lane_min_traj = value; return GSF_OK;
+    }
+    if (strcmp(key, "poison_workspaces") == 0) {
+        if (value < -1 || value > 255) { set_error("gsf_set_option: poison_workspaces must be -1 (off) or a fill word in [0, 255]"); return GSF_ERR_INVALID_ARG; }
+        ctx->poison = value;
+        if (value < 0) return GSF_OK;
+        // every call fills what the context holds now; the pinned mirror is idle between calls (the host-pointer entries synchronise)
+        GSF_HIP(hipSetDevice(ctx->device));
+        GSF_HIP(hipStreamSynchronize(ctx->stream));
+        if (ctx->pinned) fill_words_host(ctx->pinned, ctx->pinned_bytes, (uint64_t)value);
+        void* const ws[7] = { ctx->scratch, ctx->rng_scratch, ctx->k2b_scratch, ctx->rows_scratch, ctx->run_scratch, ctx->stage, ctx->small_scratch };
+        const size_t nb[7] = { ctx->scratch_bytes, ctx->rng_scratch_bytes, ctx->k2b_scratch_bytes, ctx->rows_scratch_bytes, ctx->run_scratch_bytes, ctx->stage_bytes, 512 };
+        for (int k = 0; k < 7; ++k)
+            if (ws[k]) { const int rc = launch_fill_words(ctx, ws[k], nb[k], (uint64_t)value); if (rc != GSF_OK) return rc; }
+        return GSF_OK;
     }
     set_error("gsf_set_option: unknown key '%s'", key);
     return GSF_ERR_INVALID_ARG;

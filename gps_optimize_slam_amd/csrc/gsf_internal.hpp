@@ -44,6 +44,7 @@ struct gsf_ctx {
     int duo_kernel;        // two-wave pipeline kernel for small batches (gsf_set_option "duo_kernel"): -1 automatic, 0 never, 1 always
     int tail_scan_stages;  // wave kernels: scans of a short last chunk sized by its last active lane (gsf_set_option "tail_scan_stages"): 1 default, 0 always six stages (same bits)
     gsf::FitRows fit_rows; // rows of the fused chains' Sim3 fit (gsf_set_sim3_rows); mode 0 = all valid rows
+    int64_t poison;        // tests: every workspace is filled with this 64-bit word when the option is set and after it grows (gsf_set_option "poison_workspaces"); -1 = off
     int64_t lane_min_traj; // time-major batches with fewer trajectories are transposed and run by the wave kernel (gsf_set_option "lane_min_traj")
 };
 
@@ -91,6 +92,8 @@ int ensure_rng_scratch(gsf_ctx* ctx, size_t bytes);
 int ensure_k2b_scratch(gsf_ctx* ctx, size_t bytes);
 int ensure_rows_scratch(gsf_ctx* ctx, size_t bytes);
 int ensure_run_scratch(gsf_ctx* ctx, size_t bytes);
+// `bytes` at p (device memory, 8-byte aligned) <- the 64-bit word repeated, on the context's stream (gsf_util.hip)
+int launch_fill_words(gsf_ctx* ctx, void* p, size_t bytes, uint64_t word);
 
 // wave-per-trajectory K4 / fused pipeline for the trajectory-major layout (gsf_ekf_wave.hip)
 int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double* pos, const double* quat, const double* gps,

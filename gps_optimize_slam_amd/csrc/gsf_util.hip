@@ -90,8 +90,26 @@ int launch_transpose(gsf_ctx* ctx, const void* src, void* dst, int64_t B, int64_
     return GSF_OK;
 }
 
+// tests (gsf_set_option "poison_workspaces"): a workspace <- one 64-bit word repeated, so that it reads as a small number through every type
+__global__ __launch_bounds__(256) void fill_words_kernel(uint64_t* __restrict__ p, size_t bytes, uint64_t word)
+{
+    const size_t words = bytes / 8, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) p[i] = word;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (size_t i = words * 8; i < bytes; ++i) ((uint8_t*)p)[i] = (uint8_t)(word >> (8 * (i & 7)));
+}
+
 }  // namespace
 namespace gsf {
+int launch_fill_words(gsf_ctx* ctx, void* p, size_t bytes, uint64_t word)
+{
+    if (!p || bytes == 0) return GSF_OK;
+    GSF_HIP(hipSetDevice(ctx->device));
+    const size_t blocks = (bytes / 8 + 255) / 256;
+    hipLaunchKernelGGL(fill_words_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks > 4096 ? 4096 : blocks)), dim3(256), 0, ctx->stream, (uint64_t*)p, bytes, word);
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
+}
 // n arrays ([B][N][C_k] <-> [N][C_k][B]) in one launch; elem_bytes[k] is 8 or 1
 int launch_transpose_set(gsf_ctx* ctx, bool to_time, int n, const void* const* src, void* const* dst, const int* C, const int* elem_bytes, int64_t B, int64_t N)
 {

@@ -1225,7 +1225,16 @@ __device__ __forceinline__ void wave_serial_body(const WaveArgs& a, const EkfCon
 {
     GSF_STAMP(0);
     int64_t base, N; traj_span(a, b, base, N);
-    if (N <= 0) { if (lane == 0 && GSF_STATUS_PTR(a)) a.status[b] = 0; return; }              // empty track (ref :835)
+    if (N <= 0) {                                                                             // empty track (ref :835): status 0, and no fit
+        if (lane == 0) {
+            if (GSF_STATUS_PTR(a)) a.status[b] = 0;
+            if constexpr (PIPELINE) {
+                for (int k = 0; k < 9; ++k) a.R[b * 9 + k] = NAN;
+                a.t[b * 3] = a.t[b * 3 + 1] = a.t[b * 3 + 2] = NAN; a.s[b] = NAN;
+            }
+        }
+        return;
+    }
     const double* __restrict__ tsb = a.ts + base;
     const double* __restrict__ posb = a.pos + base * 3;
     const double* __restrict__ quatb = a.quat + base * 4;

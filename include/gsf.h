@@ -194,6 +194,13 @@ GSF_API int gsf_trim(gsf_ctx *ctx);
      "prefilter_first_batch"  (default 1, 1..64) trials the sequential walk draws and scores before its first look at scikit-learn's
                       stopping rule (the batches then double); any value gives the same words, clean logs are fastest with 1
      "synth_variant"  workload of gsf_synth_batch: 0 white SLAM noise (default), 1 random-walk drift
+     "poison_workspaces"  tests only.  -1 (default): off, no cost anywhere / v in [0, 255]: EVERY call of the option (also with the value it
+                      has) fills every workspace the context holds at that moment -- kernel, RNG, K2b, rows and run workspaces, the
+                      staging arena (device, on the context's stream) and its pinned mirror (on the host, after synchronising the
+                      stream) -- with the 64-bit word v repeated, and while it is on a workspace that grows is filled the same way right
+                      after its allocation.  No call keeps state in a workspace from one call to the next, so results must not depend on
+                      it (tests/test_buffer_hygiene.py).  The word reads as a small number through every type, so a kernel that
+                      does read a count or an offset nobody wrote gives a wrong value, not a wild address
      "ekf_variant"    reserved (0) */
 GSF_API int gsf_set_option(gsf_ctx *ctx, const char *key, int64_t value);
 /* Which rows feed the Sim3 fit of the fused chains (gsf_fuse_pipeline_*, gsf_fuse_pipeline_robust_*, gsf_run_fusion_batch_*) on this context
@@ -359,7 +366,7 @@ GSF_API int gsf_sim3_ransac_mt_batch(gsf_ctx *ctx, const double *src, const doub
    gsf_mt19937_choice_batch_dev: sample_idx[b][trial][0..k) = RandomState.permutation(n_population[b])[:k] for `trials`
    consecutive trials of stream b (what np.random.choice(n, k, replace=False) draws; also scikit-learn's
    sample_without_replacement for 0.01 < k/n < 0.99 -- all ratios: gsf_mt19937_sample_without_replacement_batch_dev), the state advanced exactly as NumPy advances it.  Streams with
-   n_population[b] < k are left untouched (the reference returns before drawing, :395-397).  n_population[b] <= 28000, k <= 64.
+   n_population[b] < k are left untouched and their sets zero-filled (the reference returns before drawing, :395-397).  n_population[b] <= 28000, k <= 64.
    gsf_mt19937_choice_bounded_batch_dev: the same, with n_max >= every n_population[b] known to the HOST (0 = unknown).  The
    populations live in device memory, so only with this bound can the library size the workspace of the chip-wide route
    (csrc/gsf_rng_tape.hip): up to 16 streams of n_max <= 2040 are then drawn by thousands of waves instead of one wave per stream
@@ -507,7 +514,9 @@ GSF_API int gsf_run_fusion_ragged(gsf_ctx *ctx, const double *ts, const double *
                                   int32_t *gt_zone, int32_t *gt_south, double *gt_utm, uint8_t *gt_keep, double *gt_aligned, uint8_t *gt_valid,
                                   double *err_stats, int32_t *plot_ref, int32_t *run_status, uint8_t *inlier_mask, int32_t *trial_info);
 
-/* ragged forms (trajectories of different lengths): flat [total][C] arrays, trajectory b = rows offsets[b]..offsets[b+1] */
+/* ragged forms (trajectories of different lengths): flat [total][C] arrays, trajectory b = rows offsets[b]..offsets[b+1].
+   An empty trajectory (offsets[b] == offsets[b+1], apply_ekf_correction's early return, :835) gets status[b] = 0 and has no rows; the
+   pipeline form writes NaN into its R[b], t[b] and s[b] (there is no fit). */
 GSF_API int gsf_ekf_fuse_ragged_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
                                     const uint8_t *valid, const int64_t *offsets, const double *init_pos, const double *init_quat,
                                     const gsf_ekf_config *cfg, int64_t B, double *pos_out, double *quat_out, int32_t *status);
