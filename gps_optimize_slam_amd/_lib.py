@@ -15,6 +15,7 @@ LAYOUT_TIME_MAJOR = 1
 SIM3_NONE = 1
 SIM3_FLAG_FEW_ROWS, SIM3_FLAG_ROWS_ALL, SIM3_FLAG_ROWS_SEGMENT = 32, 64, 128      # row choice of the fused chains (gsf_set_sim3_rows mode 1)
 ST_HAD_OUTAGE, ST_RTS_APPLIED, ST_SHARP_TURN, ST_ENDED_IN_OUTAGE, ST_BAD_QUAT = 1, 2, 4, 8, 16
+POSE_GNSS_USED, POSE_IN_OUTAGE, POSE_SMOOTHED, POSE_SHARP_TURN = 1, 2, 4, 8          # per-pose flags of gsf_ekf_cov_ragged_dev
 
 
 class GsfError(RuntimeError):
@@ -160,6 +161,8 @@ SIGNATURES = {
     "gsf_ekf_fuse_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp]),
     "gsf_fuse_pipeline_ragged_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsf_fuse_pipeline_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gsf_ekf_cov_ragged_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _vp]),
+    "gsf_ekf_cov_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _vp]),
     "gsf_utm_to_wgs84_rows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gsf_tum_text_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "gsf_time_align_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),

@@ -205,7 +205,7 @@ class RunResult:
         self.__dict__.update(kw)
 
 
-def run_fusion_batch(gb, mt_state, config=None, early_exit=True, skip_seconds=5.0, max_windows=0, want_mask=True, projected=False):
+def run_fusion_batch(gb, mt_state, config=None, early_exit=True, skip_seconds=5.0, max_windows=0, want_mask=True, projected=False, want_cov=False):
     """Steps 1-6 of main_process_gui (EKFGPSSLAM.py:959-1033) for the B trajectories of a GeodeticBatch as ONE device chain on torch's
     current stream: load-side geodesy (:258-271) -> GPS RANSAC pre-filter with its windows walked on the device (:275, :136-247) ->
     time alignment (:971) -> row choice (:973-998) -> robust Sim3 (:1002) -> apply (:1006) -> EKF + RTS (:1010) -> error metric (:1013-1033).
@@ -234,6 +234,9 @@ def run_fusion_batch(gb, mt_state, config=None, early_exit=True, skip_seconds=5.
                                                int(gb.max_fixes), C.byref(rc), _p(mt_state), _p(r.R), _p(r.t), _p(r.s), _p(out.pos), _p(out.quat), _p(out.status),
                                                _p(r.n_inliers), _p(r.zone), _p(r.south), _p(r.gps_utm), _p(r.gps_keep), _p(r.aligned), _p(r.valid), _p(r.sim3_pos),
                                                _p(r.err_stats), _p(r.run_status), _p(r.inlier_mask), _p(r.trial_info)))
+    if want_cov:                                                         # one more launch after the chain; r.cov = FusedCovariance over the B * N rows
+        r.cov = ekf_covariance_ragged(gb.ts.view(B * N), gb.quat.view(B * N, 4), r.aligned.view(B * N, 3), r.valid.view(B * N), gb.slam_offsets,
+                                      config=g, run_status=r.run_status)
     return r
 
 
@@ -344,7 +347,7 @@ class RaggedGeodeticBatch:
         return cls.from_host(tracks, logs, gts, device=device)
 
 
-def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5.0, max_windows=0, want_mask=True, projected=False):
+def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5.0, max_windows=0, want_mask=True, projected=False, want_cov=False):
     """Steps 1-6 of main_process_gui (EKFGPSSLAM.py:959-1075) for the tracks of a RaggedGeodeticBatch as ONE device chain
     (gsf_run_fusion_ragged_dev): the chain of run_fusion_batch on tracks of different lengths, plus the optional ground-truth log --
     loaded with config['ground_truth_gps_filtering'] (:964) between the primary pre-filter and the fit, so its draws come between theirs --
@@ -396,6 +399,8 @@ def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5
             _p(r.inlier_mask), _p(r.trial_info)))
     finally:
         ctx.set_option("ransac_early_exit", saved)
+    if want_cov:                                                         # one more launch after the chain; r.cov = FusedCovariance over the P rows
+        r.cov = ekf_covariance_ragged(rb.ts, rb.quat, r.aligned, r.valid, rb.slam_offsets, config=g, run_status=r.run_status)
     return r
 
 
@@ -813,3 +818,50 @@ def eval_errors_batch(ts, traj_pos, gps, valid, skip_seconds=0.0):
     err = torch.empty((Bn, N), dtype=torch.float64, device=ts.device)
     check(_lib.load().gsf_eval_errors_batch_dev(context().handle, _p(ts), _p(traj_pos), _p(gps), _p(valid), Bn, N, float(skip_seconds), _p(stats), _p(err)))
     return stats, err
+
+
+class FusedCovariance:
+    """Per-pose covariance of fused tracks (ekf_covariance_ragged), flat over the P rows of the batch: filtered (P,7) or None = the diagonal
+    of the reference's ekf_covs_filt_hist; cov (P,7) = the covariance of the pose the fuse entries return (smoothed on POSE_SMOOTHED rows,
+    filtered elsewhere); flags (P,) uint8 of _lib.POSE_* bits; status (B,) int32 = ST_HAD_OUTAGE | ST_RTS_APPLIED | ST_SHARP_TURN |
+    ST_ENDED_IN_OUTAGE; offsets (B+1,).  Rows are [x y z qx qy qz qw]; the reference's matrices are exactly diagonal."""
+
+    def __init__(self, filtered, cov, flags, status, offsets):
+        self.filtered, self.cov, self.flags, self.status, self.offsets = filtered, cov, flags, status, offsets
+
+    def dense(self, which="cov"):
+        """(P,7,7) matrices, the shape the reference's lists hold (which="filtered": ekf_covs_filt_hist)"""
+        d = self.filtered if which == "filtered" else self.cov
+        return torch.diag_embed(d)
+
+
+def ekf_covariance_ragged(ts, quat, gps, valid, offsets, config=None, run_status=None, want_filtered=True):
+    """The covariances apply_ekf_correction computes and drops (EKFGPSSLAM.py:852-853, :902-903, :917), for ragged tracks: ts (P,), quat (P,4)
+    = the original SLAM quaternions, gps (P,3) / valid (P,) uint8 = the time-aligned fixes, offsets (B+1,) int64.  run_status (B,) int32 or
+    None: tracks with run_status != 0 get NaN rows, zero flags and status 0.  One launch on torch's current stream; returns a FusedCovariance."""
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(quat, torch.float64, (P, 4), "quat"); _chk(gps, torch.float64, (P, 3), "gps")
+    _chk(valid, torch.uint8, (P,), "valid")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    cfg = EkfConfig.from_config(config or CONFIG)
+    f = dict(dtype=torch.float64, device=ts.device)
+    filt = torch.empty((P, 7), **f) if want_filtered else None
+    cov = torch.empty((P, 7), **f)
+    flags = torch.empty((P,), dtype=torch.uint8, device=ts.device)
+    st = torch.empty((B,), dtype=torch.int32, device=ts.device)
+    check(_lib.load().gsf_ekf_cov_ragged_dev(context().handle, _p(ts), _p(quat), _p(gps), _p(valid), _p(offsets), _p(run_status), C.byref(cfg), B,
+                                             _p(filt), _p(cov), _p(flags), _p(st)))
+    return FusedCovariance(filt, cov, flags, st, offsets)
+
+
+def ekf_covariance_batch(batch, config=None, want_filtered=True):
+    """ekf_covariance_ragged for a trajectory-major TrajectoryBatch: the same memory with offsets = arange(B+1) * N (rows b*N .. b*N+N-1
+    belong to track b).  A time-major batch raises ValueError (convert it with to_layout first)."""
+    if batch.layout != LAYOUT_TRAJ_MAJOR:
+        raise ValueError("ekf_covariance_batch: trajectory-major batches only")
+    P = batch.B * batch.N
+    offsets = torch.arange(batch.B + 1, dtype=torch.int64, device=batch.ts.device) * batch.N
+    return ekf_covariance_ragged(batch.ts.view(P), batch.quat.view(P, 4), batch.gps.view(P, 3), batch.valid.view(P), offsets, config=config,
+                                 want_filtered=want_filtered)

@@ -639,6 +639,25 @@ int gsf_fuse_pipeline_ragged(gsf_ctx* ctx, const double* ts, const double* pos, 
     ST_RUN(gsf_fuse_pipeline_ragged_dev(ctx, dts, dpos, dquat, dgps, dval, doff, cfg, B, dR, dt, ds, dpo, dqo, dst_));
 }
 
+// per-pose covariance and flags of the fused tracks, host arrays (the outputs that are NULL are neither staged nor computed)
+int gsf_ekf_cov_ragged(gsf_ctx* ctx, const double* ts, const double* quat, const double* gps, const uint8_t* valid, const int64_t* offsets,
+                       const int32_t* run_status, const gsf_ekf_config* cfg, int64_t B, double* cov_filt, double* cov_out, uint8_t* pose_flags,
+                       int32_t* status)
+{
+    GSF_REQUIRE(ctx && cfg && offsets && B >= 0, "bad arguments");
+    if (B == 0) return GSF_OK;
+    const int64_t total = offsets[B];
+    GSF_REQUIRE(total >= 0 && (total == 0 || (ts && quat && gps && valid && cov_out)), "bad offsets / NULL arrays");
+    const size_t P = (size_t)total;
+    ST_BEGIN(P * (65 + 113) + (size_t)(B + 1) * 8 + (size_t)B * 8, 10);
+    const double* dts = st.in(ts, P); const double* dquat = st.in(quat, P * 4); const double* dgps = st.in(gps, P * 3);
+    const uint8_t* dval = st.in(valid, P); const int64_t* doff = st.in(offsets, (size_t)B + 1);
+    const int32_t* drs = run_status ? st.in(run_status, (size_t)B) : nullptr;
+    double* dcf = cov_filt ? st.out(cov_filt, P * 7) : nullptr; double* dco = st.out(cov_out, P * 7);
+    uint8_t* dfl = pose_flags ? st.out(pose_flags, P) : nullptr; int32_t* dst_ = status ? st.out(status, (size_t)B) : nullptr;
+    ST_RUN(gsf_ekf_cov_ragged_dev(ctx, dts, dquat, dgps, dval, doff, drs, cfg, B, dcf, dco, dfl, dst_));
+}
+
 // B equal-size windows of W point pairs (sliding-window re-alignment) held by the host
 int gsf_sim3_umeyama_windows(gsf_ctx* ctx, const double* src, const double* dst, const uint8_t* mask, int64_t B, int32_t W, double* R, double* t,
                              double* s, int32_t* status)

@@ -466,6 +466,34 @@ def ekf_fuse_aligned(timestamps, positions, quaternions, aligned_gps, valid_mask
     return po, qo, int(st[0])
 
 
+def ekf_covariances(slam_data_in, gps_data_in, global_config):
+    """The covariances apply_ekf_correction computes and drops, for one trajectory (host arrays): {"filtered": (n,7,7) = ekf_covs_filt_hist
+    (ref :852, :902), "smoothed": (n,7,7) = the covariance of the pose apply_ekf_correction returns -- rts_smoother_segment's (ref :777-803)
+    on the rows it rewrote, the filtered one elsewhere --, "flags": (n,) uint8 of GSF_POSE_* bits}.  Same alignment call as
+    apply_ekf_correction (ref :847); the matrices are exactly diagonal in the reference, and so they are here."""
+    n = len(slam_data_in["timestamps"])
+    if n == 0:
+        return {"filtered": np.empty((0, 7, 7)), "smoothed": np.empty((0, 7, 7)), "flags": np.empty((0,), dtype=np.uint8)}
+    aligned, valid = dynamic_time_alignment(slam_data_in, gps_data_in, global_config["time_alignment"])     # ref :847
+    filt, cov, flags, _ = ekf_cov_aligned(slam_data_in["timestamps"], slam_data_in["quaternions"], aligned, valid, global_config)
+    eye = np.eye(7)
+    return {"filtered": filt[:, :, None] * eye, "smoothed": cov[:, :, None] * eye, "flags": flags}
+
+
+def ekf_cov_aligned(timestamps, quaternions, aligned_gps, valid_mask, global_config=None):
+    """ekf_covariances after the alignment call: -> (filtered (n,7), cov (n,7), flags (n,) uint8, status bits) through gsf_ekf_cov_ragged."""
+    cfg = EkfConfig.from_config(global_config or CONFIG)
+    ts = f64(timestamps).ravel()
+    n = ts.size
+    quat, gps = f64(quaternions, (n, 4)), f64(aligned_gps, (n, 3))
+    valid = np.ascontiguousarray(valid_mask, dtype=np.uint8).reshape(n)
+    offsets = np.array([0, n], dtype=np.int64)
+    filt, cov, flags, st = np.empty((n, 7)), np.empty((n, 7)), np.empty((n,), dtype=np.uint8), np.zeros(1, dtype=np.int32)
+    check(_lib.load().gsf_ekf_cov_ragged(_ctx().handle, hptr(ts), hptr(quat), hptr(gps), hptr(valid), hptr(offsets), None, C.byref(cfg), 1,
+                                         hptr(filt), hptr(cov), hptr(flags), hptr(st)))
+    return filt, cov, flags, int(st[0])
+
+
 # ---------------------------------------------------------------------------- helpers of the EKF surface (EKFGPSSLAM.py:77-105, :679-826)
 def calculate_relative_pose(pose1_pos, pose1_quat, pose2_pos, pose2_quat):
     """Relative motion pose1 -> pose2 in pose1's frame: (delta_pos_local (3,), delta_quat (4,)); an invalid (zero-norm)

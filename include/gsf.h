@@ -531,6 +531,38 @@ GSF_API int gsf_fuse_pipeline_ragged(gsf_ctx *ctx, const double *ts, const doubl
                                      const uint8_t *valid, const int64_t *offsets, const gsf_ekf_config *cfg, int64_t B, double *R,
                                      double *t, double *s, double *pos_out, double *quat_out, int32_t *status);
 
+/* ---- per-pose covariance and smoothing flags of the fused track ------------------------------------------------------------------------
+   What apply_ekf_correction computes and drops: process_step returns the filtered and the predicted covariance of every pose (kept in
+   ekf_covs_filt_hist / ekf_covs_pred_hist, EKFGPSSLAM.py:852-853, :902-903) and rts_smoother_segment the smoothed covariance of every
+   segment it rewrites (:777-803; bound to `_` at :917).  Every one of these matrices is exactly diagonal (P0, Q, R come from np.diag,
+   H = [I3 0], the Joseph form :731 keeps the diagonal), so a row of 7 doubles [x y z qx qy qz qw] is the whole matrix.
+   For a track of N poses, dt[i] = max(1e-6, ts[i] - ts[i-1]) (:865), avail[i] = valid[i] && fix i free of NaN for i >= 1 (:867-869):
+   - filtered: Pf[0] = P0; Pp[i] = Pf[i-1] + Q dt[i] (:712-714); on axes 0-2 with avail[i]: Pf[i] = (1-k) Pp (1-k) + k R k, k = Pp / (Pp + R)
+     (:723-731); otherwise Pf[i] = Pp[i].  A sharp-turn recovery blends the state, not the covariance (:767).
+   - outages, recoveries and the RTS decision: as in gsf_ekf_fuse_ragged_dev (:848-928).  The initial outage state is the raw valid[0] (:848);
+     the sharp-turn test runs over the pose pairs inside the outage, and only for an outage of >= 2 poses (:882-889).
+   - smoothed, for a segment [a..b] handed to the smoother (a = outage start, b = the recovery, no sharp turn): Ps[b] = Pf[b] (:783);
+     Ps[k] = Pf[k] + A^2 (Ps[k+1] - Pp[k+1]), A = Pf[k] / Pp[k+1] for k < b (:786-801).  Poses a..b-1 take no update, so this equals
+     Ps[k] = Pf[k] + (Pf[k] / Pp[b])^2 (Pf[b] - Pp[b]); axes 3-6 have Pf[b] = Pp[b] and stay as filtered. */
+#define GSF_POSE_GNSS_USED 1   /* a GNSS update was applied at this pose (never pose 0) */
+#define GSF_POSE_IN_OUTAGE 2   /* pose without a usable fix: rows a..b-1 of an outage, or an outage still open at the end; pose 0 by valid[0] (:848) */
+#define GSF_POSE_SMOOTHED  4   /* pose rewritten by rts_smoother_segment: rows a..b-1 of a smoothed segment (the recovery b keeps its filtered state, :783) */
+#define GSF_POSE_SHARP_TURN 8  /* row of an outage whose recovery was judged a sharp turn: left unsmoothed (:886-889) */
+/* Ragged device form: ts[P], quat[P][4] (the ORIGINAL SLAM quaternions; read only inside outages), gps[P][3] / valid[P] = the time-aligned
+   fixes and their mask, offsets int64[B+1].  Out: cov_filt[P][7] (may be NULL) = the diagonal of ekf_covs_filt_hist; cov_out[P][7] = the
+   covariance that belongs to the pose the fuse entries return: smoothed on GSF_POSE_SMOOTHED rows, filtered elsewhere; pose_flags[P]
+   (may be NULL) = GSF_POSE_* bits; status[B] (may be NULL) = GSF_ST_HAD_OUTAGE | _RTS_APPLIED | _SHARP_TURN | _ENDED_IN_OUTAGE with the
+   meaning they have in gsf_ekf_fuse_ragged_dev (GSF_ST_BAD_QUAT is never set here: quaternions outside outages are not read).
+   An empty track has no rows and gets status 0.  run_status (may be NULL): a track with run_status[b] != 0 gets NaN rows, zero flags
+   and status 0, and its inputs are not read.  One wave per track, no workspace, any track length. */
+GSF_API int gsf_ekf_cov_ragged_dev(gsf_ctx *ctx, const double *ts, const double *quat, const double *gps, const uint8_t *valid,
+                                   const int64_t *offsets, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
+                                   double *cov_filt, double *cov_out, uint8_t *pose_flags, int32_t *status);
+/* the same with host arrays: staged upload, kernel, download */
+GSF_API int gsf_ekf_cov_ragged(gsf_ctx *ctx, const double *ts, const double *quat, const double *gps, const uint8_t *valid,
+                               const int64_t *offsets, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
+                               double *cov_filt, double *cov_out, uint8_t *pose_flags, int32_t *status);
+
 /* ---- step 7 of main_process_gui (EKFGPSSLAM.py:1085-1104): the corrected track as WGS84 rows and as the bytes of its TUM files ------------
    Rows are flat over P poses with offsets int64[B+1], as in gsf_run_fusion_ragged_dev; any offsets work (a dense batch: b * N). */
 /* Rows [E, N, alt] (pos[P][3]) -> rows [lon deg, lat deg, alt] (lonlatalt[P][3]): utm_to_wgs84(corrected_pos, projector) (:1097, :291-296),

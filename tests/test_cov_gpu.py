@@ -1,0 +1,439 @@
+"""GPU tier of the per-pose covariance entry (gsf_ekf_cov_ragged_dev / batch.ekf_covariance_ragged): the kernel against the reference's
+own covariances (tests/golden/ekf_cov_tracks.npz), against the NumPy restatement that tests/test_cov_host.py pins to the reference, against
+the decisions of the pose kernel behind ekf_fuse_ragged, inside the whole-run entries (want_cov=True), and under dirty buffers, a side
+stream and NULL optional outputs.
+
+Tolerance of every variance comparison: 1e-10 relative.  Derived, not tuned: the rounding of a 64-stage Moebius composition plus the carries
+is about 1e-14, and the smallest real mistake -- one dt off by a pose, a missed update, a wrong carry-in, a smoothing range off by one --
+moves a variance by more than 1e-3 relative.  Flags, status words and everything called "the same" are compared exactly."""
+import copy
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import hygiene
+from test_cov_host import GNSS_USED, IN_OUTAGE, SHARP_TURN, SMOOTHED, golden_tracks, rel_err, restate
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-10
+LENGTHS = [1, 2, 3, 63, 64, 65, 128, 129, 200]
+PER_LENGTH = 16
+
+
+@pytest.fixture(scope="module")
+def B():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from gps_optimize_slam_amd import batch
+    return batch
+
+
+def dev(a, dtype=None):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
+
+
+def flat(tracks, with_empty_at=None):
+    """tracks [(ts, quat, aligned, valid)] -> flat host arrays + offsets (an empty track inserted before index with_empty_at)"""
+    lens = [len(t[0]) for t in tracks]
+    if with_empty_at is not None:
+        lens.insert(with_empty_at, 0)
+    offs = np.zeros(len(lens) + 1, np.int64); offs[1:] = np.cumsum(lens)
+    cat = lambda k, shape: np.concatenate([np.asarray(t[k], np.float64).reshape(shape) for t in tracks])
+    return cat(0, (-1,)), cat(1, (-1, 4)), cat(2, (-1, 3)), np.concatenate([np.asarray(t[3]).astype(np.uint8) for t in tracks]), offs
+
+
+def run_cov(B, ts, quat, aligned, valid, offs, cfg, **kw):
+    import torch
+    r = B.ekf_covariance_ragged(dev(ts), dev(quat), dev(aligned), dev(valid), dev(offs), config=cfg, **kw)
+    torch.cuda.synchronize()
+    return r
+
+
+def full_cfg(B, part):
+    from gps_optimize_slam_amd import ekfgpsslam as E
+    cfg = copy.deepcopy(E.CONFIG)
+    for sec, kv in part.items():
+        cfg[sec].update(kv)
+    return cfg
+
+
+AXES_DIFFER = {"ekf": {"initial_cov_diag": [0.1, 0.25, 0.05, 0.01, 0.02, 0.03, 0.04], "process_noise_diag": [0.1, 0.3, 0.7, 0.01, 0.02, 0.005, 0.03],
+                       "meas_noise_diag": [0.2, 0.05, 0.6]}, "rts_decision": {"default_ekf_transition_steps_on_sharp_turn": 5}}
+
+
+# ------------------------------------------------------------------------------------------------ 1. the reference's covariances
+def test_golden_parity(B, golden):
+    """all 83 golden tracks as ragged batches in file order (one call per config: the default one carries an empty track)"""
+    tracks, g = golden_tracks(golden)
+    off = g["offsets"]
+    worst = {"filtered": 0.0, "cov": 0.0}
+    for ci in sorted(set(int(c) for c in g["cfg_index"])):
+        ids = [t for t in range(len(tracks)) if int(g["cfg_index"][t]) == ci]
+        cfg = full_cfg(B, tracks[ids[0]][5])
+        empty_at = 5 if ci == 0 else None
+        ts, quat, al, va, offs = flat([tracks[t][1:5] for t in ids], empty_at)
+        r = run_cov(B, ts, quat, al, va, offs, cfg)
+        filt, cov, flags, status = (x.cpu().numpy() for x in (r.filtered, r.cov, r.flags, r.status))
+        slot = [k for k in range(len(offs) - 1) if k != empty_at]
+        if empty_at is not None:
+            assert status[empty_at] == 0
+        for k, t in zip(slot, ids):
+            name = tracks[t][0]
+            sl, gl = slice(offs[k], offs[k + 1]), slice(off[t], off[t + 1])
+            ef, es = rel_err(filt[sl], g["filt"][gl]), rel_err(cov[sl], g["smooth"][gl])
+            worst["filtered"], worst["cov"] = max(worst["filtered"], ef), max(worst["cov"], es)
+            assert ef < TOL and es < TOL, (name, ef, es)
+            want = restate(*tracks[t][1:6])                             # (pinned to the reference's segments by the CPU tier)
+            np.testing.assert_array_equal(flags[sl], want["flags"], err_msg=name)
+            assert status[k] == want["status"], name
+            sm = np.zeros(len(want["flags"]), bool)
+            for tt, a, b in g["segments"]:
+                if tt == t:
+                    sm[a:b] = True
+            np.testing.assert_array_equal((flags[sl] & SMOOTHED) != 0, sm, err_msg=name)
+    print(f"largest deviation from the reference: filtered {worst['filtered']:.2e}, cov {worst['cov']:.2e} (relative)")
+
+
+# ------------------------------------------------------------------------------------------------ 2. the smallest shapes that can go wrong
+def planted_cov_tracks(N, seed, with_pos=False):
+    """16 host-made tracks of N poses, one kind each (what does not fit a short track shrinks to what does).  Yaw: 2 deg/s, and 140 deg/s
+    on the pairs of a sharp outage -- far from the 45 deg/s threshold on either side."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for kind in range(PER_LENGTH):
+        dt = rng.uniform(0.08, 0.12, N); dt[0] = 0.0
+        valid = np.ones(N, bool)
+        sharp, nan_rows, repeat = [], [], []
+        c = lambda i: int(min(max(i, 0), N))                            # clip an index into the track
+
+        def outage(a, b, is_sharp=False):
+            a, b = c(a), c(b)
+            if b > a:
+                valid[a:b] = False
+                if is_sharp:
+                    sharp.append((a, b))
+        if kind == 1:
+            outage(0, 1 + int(rng.integers(0, 6)))                      # from pose 0
+        elif kind == 2:
+            nan_rows.append((0, 1))                                     # valid[0] = 1 with a NaN fix at pose 0
+        elif kind == 3:
+            outage(N - 1 - int(rng.integers(0, 9)), N)                  # to the end
+        elif kind == 4:
+            outage(30 if N > 129 else 1, 130 + int(rng.integers(0, 30)) if N > 160 else N - 1)   # chunk 0 -> chunk 2: two boundaries
+        elif kind == 5:
+            r = 128 if N > 128 else (64 if N > 64 else N - 1)           # recovery at lane 0 of a chunk
+            outage(r - 1 - int(rng.integers(0, 70)), r)
+        elif kind == 6:
+            r = 127 if N > 127 else (63 if N > 63 else N - 1)           # recovery at lane 63
+            outage(r - 1 - int(rng.integers(0, 70)), r)
+        elif kind == 7:
+            outage(N - 2 - int(rng.integers(0, 70)), N - 1)             # recovery at the last pose
+        elif kind == 8:
+            outage(N // 2, N // 2 + 1)                                  # one pose
+            outage(1, 2)
+        elif kind == 9:
+            outage(5, 6); outage(10, 20, True); outage(30, 45); outage(50, 58, True)    # sharp and gentle in one chunk
+        elif kind == 10:
+            outage(N // 2, N // 2 + 2, True)                            # sharp turn, exactly two poses
+            outage(N - 3, N - 1, True)
+        elif kind == 11:
+            outage(20, 30); repeat += [k for k in (1, 10, 24, 25, 50, N - 1) if 0 < k < N]   # repeated stamps: dt = 1e-6
+        elif kind == 12:
+            nan_rows += [(k, int(rng.integers(0, 3))) for k in (1, 12, 40, 41, N - 1) if 0 < k < N]   # NaN component, mask set
+            outage(30, 33)
+        elif kind == 13:
+            outage(40, 100, True); sharp[:] = [(max(a, 80), b) for a, b in sharp if b > 80] or sharp   # turns sharp late in a carried outage
+        elif kind == 14:
+            outage(1, N - 1, True)                                      # the whole track but its ends, sharp at once
+        elif kind == 15:
+            for _ in range(int(rng.integers(1, 5))):
+                L = int(rng.choice([1, 2, 3, 7, 20, 64, 65])); s = int(rng.integers(0, max(1, N - L)))
+                valid[s:s + L] = False
+        for k in repeat:
+            dt[k] = 0.0
+        ts = 500.0 + np.cumsum(dt)
+        rate = np.full(N, np.deg2rad(2.0)) * rng.choice([-1.0, 1.0])
+        for a, b in sharp:
+            rate[a + 1:min(b, a + 4)] = np.deg2rad(140.0)
+        yaw = np.cumsum(rate * dt)
+        quat = np.stack([np.zeros(N), np.zeros(N), np.sin(yaw / 2), np.cos(yaw / 2)], -1) * rng.uniform(0.5, 2.0, (N, 1)) * rng.choice([-1.0, 1.0], (N, 1))
+        pos = np.cumsum(np.c_[np.cos(yaw), np.sin(yaw), 0.01 + 0 * yaw] * 0.8 * (dt[:, None] / 0.1), axis=0)
+        aligned = pos * 1.03 + np.array([4.5e5, 5.4e6, 110.0]) + rng.normal(0, 0.3, (N, 3))
+        aligned[~valid] = np.nan
+        for k, col in nan_rows:
+            aligned[k, col] = np.nan
+        out.append((ts, quat, aligned, valid, pos) if with_pos else (ts, quat, aligned, valid))
+    return out
+
+
+@pytest.fixture(scope="module")
+def planted():
+    """the 9 x 16 planted tracks and their restatements under both configs, made once"""
+    from gps_optimize_slam_amd import ekfgpsslam as E
+    tracks = [t for N in LENGTHS for t in planted_cov_tracks(N, 100 + N, with_pos=True)]
+    cfgs = {"default": copy.deepcopy(E.CONFIG), "axes-differ": copy.deepcopy(E.CONFIG)}
+    for sec, kv in AXES_DIFFER.items():
+        cfgs["axes-differ"][sec].update(kv)
+    want = {name: [restate(*t[:4], cfg) for t in tracks] for name, cfg in cfgs.items()}
+    for w in want["default"]:
+        for rate, thr in w["rates"]:
+            assert not (0.9 * thr <= rate <= 1.1 * thr)                 # no planted decision hangs on an ulp
+    return tracks, cfgs, want
+
+
+@pytest.mark.parametrize("config", ["default", "axes-differ"])
+def test_planted_shapes_against_the_restatement(B, planted, config):
+    tracks, cfgs, want = planted
+    ts, quat, al, va, offs = flat([t[:4] for t in tracks], with_empty_at=40)
+    r = run_cov(B, ts, quat, al, va, offs, cfgs[config])
+    filt, cov, flags, status = (x.cpu().numpy() for x in (r.filtered, r.cov, r.flags, r.status))
+    assert status[40] == 0
+    slot = [k for k in range(len(offs) - 1) if k != 40]
+    seen = set()
+    worst = 0.0
+    for k, t, w in zip(slot, tracks, want[config]):
+        sl = slice(offs[k], offs[k + 1])
+        what = (config, len(t[0]), (k - (k > 40)) % PER_LENGTH)
+        np.testing.assert_array_equal(flags[sl], w["flags"], err_msg=str(what))
+        assert status[k] == w["status"], what
+        ef, es = rel_err(filt[sl], w["filt"]), rel_err(cov[sl], w["cov"])
+        worst = max(worst, ef, es)
+        assert ef < TOL and es < TOL, (what, ef, es)
+        # smoothed rows really are smoothed (smaller position variances), everything else is the filtered value bit for bit
+        sm = (flags[sl] & SMOOTHED) != 0
+        assert (cov[sl][sm, :3] < filt[sl][sm, :3]).all() and (cov[sl][sm, 3:] == filt[sl][sm, 3:]).all(), what
+        assert (cov[sl][~sm] == filt[sl][~sm]).all(), what
+        seen |= {int(v) for v in np.unique(flags[sl])}
+        for a, b in w["segments"]:
+            seen.add(("crossing", b // 64 - a // 64)); seen.add(("rec-lane", b % 64))
+        for a, b in w["sharp"]:
+            seen.add(("sharp-crossing", b // 64 - a // 64)); seen.add(("sharp-len", b - a))
+    print(f"{config}: largest deviation from the restatement {worst:.2e} (relative)")
+    assert {0, GNSS_USED, IN_OUTAGE, IN_OUTAGE | SMOOTHED, IN_OUTAGE | SHARP_TURN} <= seen
+    assert {("crossing", 0), ("crossing", 1), ("crossing", 2), ("rec-lane", 0), ("rec-lane", 63), ("sharp-crossing", 1), ("sharp-len", 2)} <= seen
+
+
+# ------------------------------------------------------------------------------------------------ 3. the pose kernel's decisions
+def random_tracks(nb, N, seed):
+    """random 120-pose tracks in the manner of the golden generator's: 0-3 outages of 1-40 poses (some at the start / end), yaw bursts of
+    60-200 deg/s in some of them, NaN fixes with the mask set, a repeated stamp"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(nb):
+        dt = rng.uniform(0.098, 0.11, N); dt[0] = 0.0
+        valid = np.ones(N, bool)
+        rate = np.full(N, np.deg2rad(rng.uniform(-4, 4)))
+        for _ in range(int(rng.integers(0, 4))):
+            L = int(rng.choice([1, 2, 3, 8, 25, 40])); s0 = int(rng.integers(0, N - L))
+            valid[s0:s0 + L] = False
+            if L >= 8 and rng.random() < 0.6:
+                a = s0 + 1 + int(rng.integers(0, L - 4))
+                rate[a:a + 3] = np.deg2rad(rng.choice([-1, 1]) * rng.uniform(60.0, 200.0))
+        if rng.random() < 0.15:
+            valid[:int(rng.integers(1, 30))] = False
+        if rng.random() < 0.15:
+            valid[N - int(rng.integers(1, 30)):] = False
+        if rng.random() < 0.3:
+            dt[int(rng.integers(2, N - 2))] = 0.0
+        ts = np.cumsum(dt)
+        yaw = np.cumsum(rate * dt)
+        quat = np.stack([np.zeros(N), np.zeros(N), np.sin(yaw / 2), np.cos(yaw / 2)], -1) * rng.uniform(0.98, 1.02, (N, 1))
+        pos = np.cumsum(np.c_[np.cos(yaw), np.sin(yaw), 0.002 + 0 * yaw] * 1.45 * (dt[:, None] / 0.104), axis=0)
+        aligned = pos + np.array([4.58e5, 5.43e6, 112.0]) + rng.normal(0, 0.45, (N, 3))
+        aligned[~valid] = np.nan
+        aligned[(rng.random(N) < 0.02) & valid, int(rng.integers(0, 3))] = np.nan
+        out.append((ts, quat, aligned, valid, pos))
+    return out
+
+
+def test_decisions_are_the_pose_kernels(B, planted):
+    """status & 15 == ekf_fuse_ragged's; the rows whose fused position changes when RTS is made impossible (a negative threshold makes every
+    outage of >= 2 poses sharp) all carry GSF_POSE_SMOOTHED"""
+    import torch
+    tracks = planted[0] + random_tracks(256, 120, 77)
+    cfg = planted[1]["default"]
+    ts, quat, al, va, offs = flat([t[:4] for t in tracks])
+    pos = np.concatenate([t[4] for t in tracks])
+    first = offs[:-1]
+    ip = np.where(np.isnan(al[first]).any(axis=1, keepdims=True), pos[first] + np.array([4.5e5, 5.4e6, 110.0]), al[first])
+    iq = quat[first] / np.linalg.norm(quat[first], axis=1, keepdims=True)
+    d = [dev(x) for x in (ts, pos, quat, al, va, offs)]
+    r = B.ekf_covariance_ragged(d[0], d[2], d[3], d[4], d[5], config=cfg)
+    p1, _, st1 = B.ekf_fuse_ragged(*d, dev(ip), dev(iq), config=cfg)
+    never = copy.deepcopy(cfg)
+    never["rts_decision"]["sharp_turn_yaw_rate_threshold_deg_per_sec"] = -1.0
+    p2, _, st2 = B.ekf_fuse_ragged(*d, dev(ip), dev(iq), config=never)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(r.status.cpu().numpy() & 15, st1.cpu().numpy() & 15)
+    assert (st1.cpu().numpy() & 16 == 0).all()
+    changed = (p1 != p2).any(dim=1).cpu().numpy()
+    smoothed = (r.flags.cpu().numpy() & SMOOTHED) != 0
+    assert changed.sum() > 1000                                          # the comparison is not empty ...
+    assert not (changed & ~smoothed).any()                               # ... and no row outside the smoothed ones moved
+    assert (st2.cpu().numpy() & 2 != 0).any()                            # (one-pose outages are smoothed under any threshold, :893-894)
+
+
+# ------------------------------------------------------------------------------------------------ 4. the whole-run entries
+def file_batch(B, golden, tmp_path):
+    """SLAM / GNSS / ground-truth file triples of different lengths from the bundled track, as tests/test_run_ragged.py builds them, plus
+    one track whose GNSS log has two fixes (its run stops before the filter)"""
+    g, k, s6 = golden("c1_combined.npz"), golden("kat_bundled.npz"), golden("step6_gt.npz")
+    prim = np.column_stack((g["gps_t_raw"], g["lat"], g["lon"], g["alt"]))
+    grnd = np.column_stack((s6["gt_t_raw"], s6["gt_lat"], s6["gt_lon"], s6["gt_alt"]))
+    slam_p, gps_p, gt_p = [], [], []
+    for j, cut in enumerate((271, 200, 130, 160)):
+        sf, gf, tf = tmp_path / f"traj{j}.txt", tmp_path / f"gps{j}.txt", tmp_path / f"gt{j}.txt"
+        np.savetxt(sf, np.column_stack((k["ts"], k["pos"], k["quat"]))[:cut], fmt="%.18e")
+        np.savetxt(gf, prim[:2] if j == 2 else prim[:min(len(prim), cut + 8 - j)], fmt="%.18e", delimiter="," if j % 2 else " ")
+        np.savetxt(tf, grnd[:min(len(grnd), cut - 10 + 3 * j)], fmt="%.18e")
+        slam_p.append(str(sf)); gps_p.append(str(gf)); gt_p.append(str(tf))
+    return B.RaggedGeodeticBatch.from_files(slam_p, gps_p, gt_p)
+
+
+def words(x):
+    import torch
+    x = x.contiguous()
+    return x.view(torch.int64) if x.dtype == torch.float64 else x
+
+
+def test_whole_run_with_covariance(B, golden, tmp_path):
+    import torch
+    from gps_optimize_slam_amd import ekfgpsslam as E
+    rb = file_batch(B, golden, tmp_path)
+    seeds = [3, 4, 5, 6]
+    r = B.run_fusion_ragged(rb, B.mt19937_seed(seeds), E.CONFIG, want_cov=True)
+    q = B.run_fusion_ragged(rb, B.mt19937_seed(seeds), E.CONFIG)
+    direct = B.ekf_covariance_ragged(rb.ts, rb.quat, r.aligned, r.valid, rb.slam_offsets, config=E.CONFIG, run_status=r.run_status)
+    torch.cuda.synchronize()
+    assert not hasattr(q, "cov") and isinstance(r.cov, B.FusedCovariance)
+    for name in ("filtered", "cov", "flags", "status"):
+        assert torch.equal(words(getattr(r.cov, name)), words(getattr(direct, name))), name
+    for name, v in q.__dict__.items():                                  # everything else: the same words with and without the extra launch
+        w = getattr(r, name)
+        if torch.is_tensor(v):
+            assert torch.equal(words(v), words(w)), name
+        elif name == "fused":
+            assert torch.equal(words(v.buf), words(w.buf)) and torch.equal(v.status, w.status)
+        else:
+            assert v is None and w is None, name
+    rs, so = r.run_status.cpu().numpy(), rb.slam_offsets.cpu().numpy()
+    assert rs[2] != 0 and (rs[[0, 1, 3]] == 0).all(), rs
+    cov, filt, flags = r.cov.cov.cpu().numpy(), r.cov.filtered.cpu().numpy(), r.cov.flags.cpu().numpy()
+    for b in range(4):
+        sl = slice(so[b], so[b + 1])
+        if rs[b] != 0:
+            assert np.isnan(cov[sl]).all() and np.isnan(filt[sl]).all() and (flags[sl] == 0).all() and int(r.cov.status[b]) == 0
+        else:
+            assert np.isfinite(cov[sl]).all() and (cov[sl] > 0).all() and (flags[sl][1:] != 0).all()
+            assert int(r.cov.status[b]) == int(r.fused.status[b]) & 15
+
+
+def test_dense_run_with_covariance(B):
+    import torch
+    from gps_optimize_slam_amd import ekfgpsslam as E
+    gb = B.GeodeticBatch.synthetic(12, 100)
+    r = B.run_fusion_batch(gb, B.mt19937_seed(np.arange(12) + 40), E.CONFIG, want_cov=True)
+    q = B.run_fusion_batch(gb, B.mt19937_seed(np.arange(12) + 40), E.CONFIG)
+    # the same rows as a trajectory-major TrajectoryBatch: ekf_covariance_batch sees the same memory layout
+    tb = B.TrajectoryBatch(B.LAYOUT_TRAJ_MAJOR, gb.B, gb.N)
+    tb.ts, tb.quat, tb.gps, tb.valid = gb.ts, gb.quat, r.aligned, r.valid
+    viab = B.ekf_covariance_batch(tb, E.CONFIG)
+    torch.cuda.synchronize()
+    assert not hasattr(q, "cov")
+    assert torch.equal(words(q.fused.buf), words(r.fused.buf)) and torch.equal(words(q.aligned), words(r.aligned))
+    ok = (r.run_status == 0).cpu().numpy()
+    assert ok.sum() >= 10
+    rows = torch.as_tensor(np.repeat(ok, gb.N)).cuda()
+    assert torch.equal(words(viab.cov)[rows], words(r.cov.cov)[rows]) and torch.equal(viab.flags[rows], r.cov.flags[rows])
+    assert tuple(r.cov.dense().shape) == (gb.B * gb.N, 7, 7)
+    with pytest.raises(ValueError):
+        B.ekf_covariance_batch(B.TrajectoryBatch(B.LAYOUT_TIME_MAJOR, 2, 3))
+
+
+# ------------------------------------------------------------------------------------------------ 5. hygiene
+@pytest.fixture(scope="module")
+def hygiene_inputs(planted):
+    tracks, cfgs, want = planted
+    ts, quat, al, va, offs = flat([t[:4] for t in tracks], with_empty_at=7)
+    return ts, quat, al, va, offs, cfgs["default"]
+
+
+def small_dirt(B):
+    """another, larger call on the same context: a pose batch through the device entries and a host-pointer call through the staging arena"""
+    from gps_optimize_slam_amd import _lib
+    big = B.TrajectoryBatch.synthetic(64, 700, layout=0, seed=5)
+    e, n = np.random.default_rng(3).uniform(3e5, 7e5, 200000), np.random.default_rng(4).uniform(1e6, 8e6, 200000)
+
+    def dirty():
+        B.fuse_pipeline_batch(big)
+        lat, lon = np.empty_like(e), np.empty_like(e)
+        _lib.check(_lib.load().gsf_utm_inverse(B.context().handle, _lib.hptr(e), _lib.hptr(n), e.size, 32, 0, _lib.hptr(lat), _lib.hptr(lon)))
+    return dirty
+
+
+def test_outputs_do_not_depend_on_stale_buffers(B, monkeypatch, hygiene_inputs):
+    """outputs prefilled with two byte patterns, workspaces poisoned and not: the same bytes, so every row of every non-empty track is written"""
+    ts, quat, al, va, offs, cfg = hygiene_inputs
+    d = [dev(x) for x in (ts, quat, al, va, offs)]
+    res = hygiene.same_bytes_under_dirt(monkeypatch, B.context(), lambda: B.ekf_covariance_ragged(*d, config=cfg), small_dirt(B), rows_of=offs)
+    assert np.isfinite(res.cov.cpu().numpy()).all() and res.cov.shape[0] == offs[-1]
+
+
+def test_host_entry_and_null_outputs(B, monkeypatch, hygiene_inputs):
+    """gsf_ekf_cov_ragged (host arrays) under dirty staging; the same bytes as the device entry; cov_filt = NULL and pose_flags = NULL leave
+    cov_out unchanged"""
+    import torch
+    from gps_optimize_slam_amd import _lib
+    ts, quat, al, va, offs, cfg = hygiene_inputs
+    L, hp, ctx = _lib.load(), _lib.hptr, B.context()
+    c = _lib.EkfConfig.from_config(cfg)
+    P, nb = int(offs[-1]), len(offs) - 1
+
+    def host(alloc):
+        filt, cov, fl, st = alloc.new((P, 7), np.float64), alloc.new((P, 7), np.float64), alloc.new(P, np.uint8), alloc.new(nb, np.int32)
+        _lib.check(L.gsf_ekf_cov_ragged(ctx.handle, hp(ts), hp(quat), hp(al), hp(va), hp(offs), None, C.byref(c), nb, hp(filt), hp(cov), hp(fl), hp(st)))
+        return filt, cov, fl, st
+    filt, cov, fl, st = hygiene.same_bytes_under_dirt(monkeypatch, ctx, host, small_dirt(B), host=True, rows_of=offs)
+    d = [dev(x) for x in (ts, quat, al, va, offs)]
+    r = B.ekf_covariance_ragged(*d, config=cfg)
+    nofilt = B.ekf_covariance_ragged(*d, config=cfg, want_filtered=False)
+    only = torch.full((P, 7), float("nan"), dtype=torch.float64, device="cuda")
+    _lib.check(L.gsf_ekf_cov_ragged_dev(ctx.handle, *[C.c_void_p(x.data_ptr()) for x in d], None, C.byref(c), nb, None, C.c_void_p(only.data_ptr()), None, None))
+    torch.cuda.synchronize()
+    same = lambda a, b: np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+    assert same(r.filtered.cpu().numpy(), filt) and same(r.cov.cpu().numpy(), cov) and same(r.flags.cpu().numpy(), fl) and same(r.status.cpu().numpy(), st)
+    assert nofilt.filtered is None and same(nofilt.cov.cpu().numpy(), cov) and same(nofilt.flags.cpu().numpy(), fl)
+    assert same(only.cpu().numpy(), cov)
+    # a failed track among them: NaN rows, zero flags, status 0, the others untouched
+    rs = np.zeros(nb, np.int32); rs[3] = 8
+    failed = B.ekf_covariance_ragged(*d, config=cfg, run_status=dev(rs))
+    torch.cuda.synchronize()
+    fc, ff, fs = failed.cov.cpu().numpy(), failed.flags.cpu().numpy(), failed.status.cpu().numpy()
+    sl = slice(offs[3], offs[4])
+    assert np.isnan(fc[sl]).all() and np.isnan(failed.filtered.cpu().numpy()[sl]).all() and (ff[sl] == 0).all() and fs[3] == 0
+    keep = np.ones(P, bool); keep[sl] = False
+    assert same(fc[keep], cov[keep]) and same(ff[keep], fl[keep]) and (np.delete(fs, 3) == np.delete(st, 3)).all()
+
+
+def test_side_stream_gives_the_same_bytes(B, hygiene_inputs):
+    import torch
+    ts, quat, al, va, offs, cfg = hygiene_inputs
+    d = [dev(x) for x in (ts, quat, al, va, offs)]
+    want = B.ekf_covariance_ragged(*d, config=cfg)
+    torch.cuda.synchronize()
+    ctx0 = B.context()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        a = torch.ones((4096, 4096), dtype=torch.float32, device="cuda")
+        busy = a @ a                                                    # keeps the stream busy while the inputs and the call are queued behind it
+        d2 = [torch.as_tensor(np.ascontiguousarray(x)).pin_memory().to("cuda", non_blocking=True) for x in (ts, quat, al, va, offs)]
+        assert B.context() is not ctx0
+        got = B.ekf_covariance_ragged(*d2, config=cfg)
+        s.synchronize()
+    for name in ("filtered", "cov", "flags", "status"):
+        assert torch.equal(words(getattr(want, name)), words(getattr(got, name))), name
+    del busy
