@@ -81,6 +81,7 @@ RUN_GT_EMPTY, RUN_GT_FEW, RUN_GT_UNHANDLED, RUN_SLAM_EMPTY = 32, 64, 128, 256   
 SIM3_FLAG_SATURATED = 256
 TUM_UTM, TUM_WGS84 = 0, 1                                     # formats of gsf_tum_text_dev
 TEXT_DEVICE, TEXT_SKIPPED, TEXT_HOST = 0, 1, 2                  # its track_state values
+CLK_NONE, CLK_AT_EDGE, CLK_FLAT = 1, 2, 4                       # clk_status bits of gsf_clock_offset_search_dev
 
 
 def library_path():
@@ -168,6 +169,8 @@ SIGNATURES = {
     "gsf_time_align_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
     "gsf_time_align_loaded_rows_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),
     "gsf_time_align_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp]),
+    "gsf_clock_offset_search_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _f64, _i32, _f64, _i32, _f64] + [_vp] * 9),
+    "gsf_clock_offset_search": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f64, _i32, _f64, _i32, _f64] + [_vp] * 9),
     "gsf_eval_errors_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f64, _vp, _vp]),
     "gsf_eval_errors_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f64, _vp, _vp]),
     "gsf_relative_pose_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),

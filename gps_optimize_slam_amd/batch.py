@@ -116,6 +116,18 @@ class TrajectoryBatch:
         return {k: getattr(t, k).cpu().numpy() for k in ("ts", "pos", "quat", "gps", "valid", "init_pos", "init_quat")}
 
 
+def _shift_stamps(t, offsets, tau, name):
+    """t + tau[b] on every fix of log b (one double addition per fix, as dynamic_time_alignment's adjusted_gps_times, EKFGPSSLAM.py:338)"""
+    B = int(offsets.numel()) - 1
+    tau = torch.as_tensor(tau, dtype=torch.float64).to(t.device).reshape(-1)
+    if tau.numel() == 1:
+        tau = tau.expand(B)
+    if tau.numel() != B:
+        raise ValueError(f"{name}: expected one offset per track ({B}), got {tau.numel()}")
+    counts = (offsets[1:] - offsets[:-1]).to(t.device)
+    return t + torch.repeat_interleave(tau.contiguous(), counts)
+
+
 class GeodeticBatch:
     """B trajectories x N poses whose GNSS side is still what the reference's loader reads (load_gps_data, EKFGPSSLAM.py:258):
     a ragged log of fixes with their own stamps, rows (lat deg, lon deg, alt m).  Input of fuse_from_geodetic()."""
@@ -164,6 +176,13 @@ class GeodeticBatch:
         llh = self.gps_llh.clone()
         llh[:, 0] += hit.double() * (float(metres) / 111320.0)
         return GeodeticBatch(self.B, self.N, self.ts, self.pos, self.quat, self.gps_offsets, self.gps_t, llh, self.max_fixes)
+
+
+    def with_clock_offset(self, tau):
+        """A copy of the batch whose GNSS stamps carry + tau[b] on every fix of log b (tau: (B,) or a scalar) -- the reference's way of
+        applying a clock offset: GPSmerge.py:73-80 writes it into the stamps of the GNSS file.  SLAM side and fixes shared, stamps new."""
+        return GeodeticBatch(self.B, self.N, self.ts, self.pos, self.quat, self.gps_offsets, _shift_stamps(self.gps_t, self.gps_offsets, tau, "tau"),
+                             self.gps_llh, self.max_fixes)
 
 
 FIT_ROWS_DEFAULT = "reference"
@@ -347,6 +366,20 @@ class RaggedGeodeticBatch:
         return cls.from_host(tracks, logs, gts, device=device)
 
 
+    def with_clock_offset(self, tau, gt_tau=None):
+        """A copy of the batch whose primary GNSS stamps carry + tau[b] on every fix of log b (tau: (B,) or a scalar) and, with gt_tau, whose
+        ground-truth stamps carry + gt_tau[b] (None: the ground-truth log keeps its stamps -- it is another receiver's file) -- the reference's
+        way of applying a clock offset: GPSmerge.py:73-80 writes it into the stamps of the GNSS file.  estimate_clock_offset ->
+        with_clock_offset -> run_fusion_ragged is the whole workflow.  Everything but the stamps is shared with this batch."""
+        gt_t = self.gt_t
+        if gt_tau is not None:
+            if self.gt_offsets is None:
+                raise ValueError("with_clock_offset: gt_tau given, but the batch has no ground-truth log")
+            gt_t = _shift_stamps(self.gt_t, self.gt_offsets, gt_tau, "gt_tau")
+        return RaggedGeodeticBatch(self.ts, self.pos, self.quat, self.slam_offsets, _shift_stamps(self.gps_t, self.gps_offsets, tau, "tau"), self.gps_llh,
+                                   self.gps_offsets, gt_t, self.gt_llh, self.gt_offsets, self.max_poses, self.max_fixes, self.gt_max_fixes)
+
+
 def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5.0, max_windows=0, want_mask=True, projected=False, want_cov=False):
     """Steps 1-6 of main_process_gui (EKFGPSSLAM.py:959-1075) for the tracks of a RaggedGeodeticBatch as ONE device chain
     (gsf_run_fusion_ragged_dev): the chain of run_fusion_batch on tracks of different lengths, plus the optional ground-truth log --
@@ -401,6 +434,79 @@ def run_fusion_ragged(rb, mt_state, config=None, early_exit=True, skip_seconds=5
         ctx.set_option("ransac_early_exit", saved)
     if want_cov:                                                         # one more launch after the chain; r.cov = FusedCovariance over the P rows
         r.cov = ekf_covariance_ragged(rb.ts, rb.quat, r.aligned, r.valid, rb.slam_offsets, config=g, run_status=r.run_status)
+    return r
+
+
+class ClockOffset:
+    """Result of estimate_clock_offset for B tracks x K candidates: J (B, K) = RMSE in metres of the Sim3 fit with the GNSS clock shifted by
+    tau (B, K) (NaN: no fit), n_rows (B, K) int32 = rows of that fit, best_k (B,) int32 = first arg-min of J (-1: none), tau_best (B,) =
+    tau[b, best_k], tau_refined (B,) = vertex of the parabola through J^2 at best_k and its neighbours (tau_best where that does not apply),
+    R (B, 9) / t (B, 3) / s (B,) = the fit of best_k, status (B,) int32 = _lib.CLK_NONE | CLK_AT_EDGE (widen the grid) | CLK_FLAT (the offset
+    is not observable on this track)."""
+
+    def __init__(self, J, n_rows, best_k, tau_best, tau_refined, R, t, s, status, tau):
+        self.J, self.n_rows, self.best_k, self.tau_best, self.tau_refined = J, n_rows, best_k, tau_best, tau_refined
+        self.R, self.t, self.s, self.status, self.tau = R, t, s, status, tau
+
+
+def estimate_clock_offset(rb_or_arrays, tau0=None, dtau=0.05, K=41, config=None, run=None, min_rows=0, flat_threshold=0.0, fit_rows=FIT_ROWS_DEFAULT):
+    """The offset between the SLAM clock and the GNSS clock of B tracks, searched on the device (gsf_clock_offset_search_dev): for every
+    candidate tau[b, k] = tau0[b] + k * dtau the fixes are re-stamped t + tau (dynamic_time_alignment's adjusted_gps_times,
+    EKFGPSSLAM.py:337-338), aligned to the SLAM stamps (:325-387), the rows of main_process_gui's fit are picked (:973-998; fit_rows="all":
+    every valid row) and compute_sim3_transform (:428-459) is scored by its RMSE.  The reference itself has no such step: its
+    estimate_time_offset is identically 0 and the number is typed in (GPSmerge.py:73-80).
+    rb_or_arrays: a RaggedGeodeticBatch / GeodeticBatch, or device tensors (ts (P,), pos (P,3), slam_offsets (B+1,), gps_t (T,),
+    gps_utm (T,3) = (E, N, alt) rows with NaN easting and northing on dropped fixes, gps_offsets (B+1,)[, gps_keep (T,) uint8]).
+    run: the RunResult of a whole run of that batch at offset 0 -- its gps_utm / gps_keep are used, i.e. the fixes its pre-filter kept;
+    without it a batch is projected here (gsf_gps_rows_to_utm_batch_dev) and every fix the loader keeps is used.
+    tau0 (B,) / scalar / None = 0; min_rows <= 0: the row rule's min_samples; flat_threshold in metres (<= 0: CLK_FLAT is never set).
+    Asynchronous on torch's current stream.  Returns a ClockOffset."""
+    g = config or CONFIG
+    ctx = context()
+    L = _lib.load()
+    keep = None
+    if isinstance(rb_or_arrays, (tuple, list)):
+        ts, pos, so, gps_t, utm, go = rb_or_arrays[:6]
+        keep = rb_or_arrays[6] if len(rb_or_arrays) > 6 else None
+        max_fixes = None
+    else:
+        b = rb_or_arrays
+        ts, pos, so, gps_t, go, max_fixes = b.ts.reshape(-1), b.pos.reshape(-1, 3), b.slam_offsets, b.gps_t, b.gps_offsets, int(b.max_fixes)
+        utm = None if run is not None else b.gps_llh
+    B = _offsets_chk(so)
+    if _offsets_chk(go) != B:
+        raise ValueError("estimate_clock_offset: slam_offsets and gps_offsets must describe the same number of tracks")
+    dev = ts.device
+    if run is not None:
+        utm, keep = run.gps_utm, run.gps_keep
+    elif not isinstance(rb_or_arrays, (tuple, list)):
+        llh, utm = utm, torch.empty_like(utm)
+        zone, south = torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev)
+        check(L.gsf_gps_rows_to_utm_batch_dev(ctx.handle, _p(llh), _p(go), B, _p(utm), _p(zone), _p(south)))
+    P, T = int(ts.numel()), int(gps_t.numel())
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos")
+    _chk(gps_t, torch.float64, (T,), "gps_t"); _chk(utm, torch.float64, (T, 3), "gps_utm")
+    if keep is not None:
+        _chk(keep, torch.uint8, (T,), "gps_keep")
+    if max_fixes is None:
+        max_fixes = int((go[1:] - go[:-1]).max().item()) if B else 0          # sizing of the staging (a host value, once per call)
+    K = int(K)
+    if not 1 <= K <= 4096:
+        raise ValueError(f"estimate_clock_offset: K must be in 1..4096, got {K}")
+    f = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    if tau0 is not None:
+        tau0 = torch.as_tensor(tau0, dtype=torch.float64).to(dev).reshape(-1)
+        tau0 = (tau0.expand(B) if tau0.numel() == 1 else tau0).contiguous()
+        _chk(tau0, torch.float64, (B,), "tau0")
+    ctx.set_sim3_rows(fit_rows, g)
+    r = ClockOffset(J=torch.empty((B, K), **f), n_rows=torch.empty((B, K), **i32), best_k=torch.empty((B,), **i32), tau_best=torch.empty((B,), **f),
+                    tau_refined=torch.empty((B,), **f), R=torch.empty((B, 9), **f), t=torch.empty((B, 3), **f), s=torch.empty((B,), **f),
+                    status=torch.empty((B,), **i32),
+                    tau=(torch.zeros((B, 1), **f) if tau0 is None else tau0[:, None]) + torch.arange(K, **f)[None, :] * float(dtau))
+    check(L.gsf_clock_offset_search_dev(ctx.handle, _p(ts), _p(pos), _p(so), _p(gps_t), _p(utm), _p(keep), _p(go), B, max_fixes, _p(tau0), float(dtau), K,
+                                        float(g["time_alignment"]["max_gps_gap_threshold"]), int(min_rows), float(flat_threshold), _p(r.J), _p(r.n_rows),
+                                        _p(r.best_k), _p(r.tau_best), _p(r.tau_refined), _p(r.R), _p(r.t), _p(r.s), _p(r.status)))
     return r
 
 

@@ -306,6 +306,36 @@ def estimate_time_offset(slam_times, gps_times, max_samples):
     return 0.0
 
 
+def search_time_offset(slam_data, gps_data, tau_min, tau_max, dtau, config=None):
+    """The SLAM <-> GNSS clock offset the reference leaves to the keyboard (GPSmerge.py:73-80), searched: for every tau on the grid
+    tau_min, tau_min + dtau, ... <= tau_max the fixes are re-stamped t + tau (ref :338), aligned (:325-387), the rows of main_process_gui's
+    fit are picked (:973-998) and compute_sim3_transform (:428-459) is scored by the RMSE of its residuals (gsf_clock_offset_search, one
+    workgroup per candidate).  slam_data / gps_data: the dicts of load_slam_trajectory / load_gps_data.  Returns (tau_refined, curve):
+    the parabola-refined minimum (None when no candidate has a fit) and curve = {'tau', 'rmse', 'n_rows' (K,), 'best_k', 'tau_best',
+    'status' (CLK_* bits of _lib: 2 = the minimum sits on the grid's edge)}.  estimate_time_offset keeps the reference's behaviour."""
+    g = config or CONFIG
+    dtau, tau_min = float(dtau), float(tau_min)
+    if not dtau > 0.0 or not float(tau_max) >= tau_min:
+        raise ValueError("search_time_offset: needs dtau > 0 and tau_max >= tau_min")
+    K = int(np.floor((float(tau_max) - tau_min) / dtau + 1e-9)) + 1
+    if K > 4096:
+        raise ValueError(f"search_time_offset: {K} candidates, at most 4096 per call (search coarse to fine)")
+    ts, pos = f64(slam_data["timestamps"]).ravel(), f64(slam_data["positions"]).reshape(-1, 3)
+    gt, gp = f64(gps_data["timestamps"]).ravel(), f64(gps_data["positions"]).reshape(-1, 3)
+    so, go = np.array([0, len(ts)], dtype=np.int64), np.array([0, len(gt)], dtype=np.int64)
+    tau0 = np.array([tau_min])
+    J, nr = np.empty((1, K)), np.zeros((1, K), dtype=np.int32)
+    bk, st = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    tb, tr = np.empty(1), np.empty(1)
+    ctx = _ctx()
+    ctx.set_sim3_rows("reference", g)
+    check(_lib.load().gsf_clock_offset_search(ctx.handle, hptr(ts), hptr(pos), hptr(so), hptr(gt), hptr(gp), None, hptr(go), 1, hptr(tau0), dtau, K,
+                                              float(g["time_alignment"]["max_gps_gap_threshold"]), 0, 0.0, hptr(J), hptr(nr), hptr(bk), hptr(tb), hptr(tr), None, None, None,
+                                              hptr(st)))
+    curve = {"tau": tau0[0] + np.arange(K) * dtau, "rmse": J[0], "n_rows": nr[0], "best_k": int(bk[0]), "tau_best": float(tb[0]), "status": int(st[0])}
+    return (None if bk[0] < 0 else float(tr[0])), curve
+
+
 def dynamic_time_alignment(slam_data, gps_data_source, time_align_config):
     """GPS positions interpolated onto the SLAM stamps, per gap-free segment (ref :325-387): returns
     (aligned (N,3) with NaN where unavailable, valid_mask (N,) bool).  One launch of the alignment kernel

@@ -612,6 +612,44 @@ GSF_API int gsf_time_align_loaded_rows_batch_dev(gsf_ctx *ctx, const double *sla
                                                  int32_t max_gps_per_trajectory, double max_gps_gap_threshold, double *aligned,
                                                  uint8_t *valid, int32_t *status);
 
+/* ---- clock-offset search: the offset between the SLAM clock and the GNSS clock ----------------------------------------------------------
+   The reference's estimate_time_offset (EKFGPSSLAM.py:301-323) correlates two linspace ramps and always returns 0; its workflow takes the
+   offset from the keyboard (GPSmerge.py:73-80) and dynamic_time_alignment adds it to the GNSS stamps (:337-338).  This entry sweeps that
+   number: for track b (rows slam_offsets[b]..slam_offsets[b+1] of ts[P], pos[P][3]) and candidate k < K,
+     tau[b][k] = tau0[b] + (double)k * dtau  (a product and a sum, each rounded once: numpy's tau0 + k * dtau bit for bit; tau0 == NULL: 0);
+     fixes used: fix i of log b (gps_offsets, gps_t[G], gps_utm[G][3] = (E, N, alt)) with gps_keep == NULL || gps_keep[i], and not the
+       loader's drop mark (easting AND northing NaN, as in gsf_time_align_loaded_rows_batch_dev);
+     alignment: dynamic_time_alignment (:325-387) with adjusted_gps_times = gps_t + tau[b][k] (:338), otherwise as gsf_time_align_batch_dev
+       (sort, first of equal stamps, gap split at max_gps_gap_threshold, cubic >= 4 fixes, linear 2-3, NaN outside); the splines are
+       rebuilt per candidate from the shifted stamps;
+     fit rows: the context's row rule (gsf_set_sim3_rows; :973-998 in mode 1), as gsf_fuse_pipeline_ragged_dev applies it;
+     fit: compute_sim3_transform (:428-459), src = SLAM positions, dst = aligned fixes;
+     J[b][k] = sqrt(mean ||dst_i - (s R src_i + t)||^2) over the fit rows, in metres; n_rows[b][k] (may be NULL) = their number (where the
+       row rule raises, :975 / :997: the number of valid rows it found too few).  J = NaN where the reference would raise or return None
+       (GSF_SIM3_NONE, GSF_SIM3_FLAG_FEW_ROWS), and where n_rows < min_rows (min_rows <= 0: the row rule's min_samples).
+   Per track: best_k[b] = the first k with the smallest non-NaN J (-1: none); tau_best[b] = tau[b][best_k]; tau_refined[b] = the vertex of the
+   parabola through (tau, J^2) at best_k - 1, best_k, best_k + 1, tau_best + 0.5 dtau (a - c) / (a - 2m + c), when best_k is interior, both
+   neighbours are finite and a - 2m + c > 0, else tau_best (both NaN without a best_k); R[B][9], t[B][3], s[B] (all three may be NULL) = the
+   fit of best_k (NaN without one); clk_status[b] = GSF_CLK_* bits.  An empty track gets a NaN row and GSF_CLK_NONE.
+   1 <= K <= 4096, any track length; max_fixes >= the longest log sizes the staging (LDS up to 2 560 fixes, beyond that a scratch slab with
+   one row per resident workgroup); a longer log is left unaligned (NaN row).  One 64-lane workgroup per (b, k) and one per track for the
+   pick; nothing per candidate is written but J and n_rows.  Device pointers, asynchronous. */
+#define GSF_CLK_NONE 1     /* no candidate has a fit */
+#define GSF_CLK_AT_EDGE 2  /* best_k is 0 or K - 1 with K > 1: the minimum may lie outside the grid, widen it */
+#define GSF_CLK_FLAT 4     /* max finite J - min J < flat_threshold: the offset is not observable on this track (a straight constant-velocity
+                              run); flat_threshold <= 0 never sets it */
+GSF_API int gsf_clock_offset_search_dev(gsf_ctx *ctx, const double *ts, const double *pos, const int64_t *slam_offsets, const double *gps_t,
+                                        const double *gps_utm, const uint8_t *gps_keep, const int64_t *gps_offsets, int64_t B, int32_t max_fixes,
+                                        const double *tau0, double dtau, int32_t K, double max_gps_gap_threshold, int32_t min_rows,
+                                        double flat_threshold, double *J, int32_t *n_rows, int32_t *best_k, double *tau_best, double *tau_refined,
+                                        double *R, double *t, double *s, int32_t *clk_status);
+/* the same with host arrays (max_fixes is read from gps_offsets): staged upload, the two launches, download */
+GSF_API int gsf_clock_offset_search(gsf_ctx *ctx, const double *ts, const double *pos, const int64_t *slam_offsets, const double *gps_t,
+                                    const double *gps_utm, const uint8_t *gps_keep, const int64_t *gps_offsets, int64_t B, const double *tau0,
+                                    double dtau, int32_t K, double max_gps_gap_threshold, int32_t min_rows, double flat_threshold, double *J,
+                                    int32_t *n_rows, int32_t *best_k, double *tau_best, double *tau_refined, double *R, double *t, double *s,
+                                    int32_t *clk_status);
+
 /* ---- error evaluation (main_process_gui step 6, EKFGPSSLAM.py:1013-1033) -------------------- */
 /* B trajectories x N poses, trajectory-major.  For every index with valid finite aligned GNSS and ts > ts[0] + skip_seconds:
    error = min over all such candidate fixes of |traj_pos[i] - gps[j]| (cdist + min, :1030-1031).
