@@ -208,7 +208,7 @@ const char* gsf_version(void)
 {
     // a function-local static is initialised once, also under concurrent first calls (C++11)
     static const std::string v = std::string("gsf 0.5.0 (gfx950, fp64) | ") + gsf::wave_small_build_info() + " | " + gsf::wave_big_build_info() + " | " +
-                                 gsf::wave_block_build_info();
+                                 gsf::wave_block_build_info() + " | " + gsf::wave_early_build_info();
     return v.c_str();
 }
 int gsf_abi_version(void) { return GSF_ABI_VERSION; }
@@ -241,7 +241,7 @@ static int create_common(int device_id, hipStream_t stream, bool owns, gsf_ctx**
     gsf_ctx* c = new gsf_ctx();
     c->device = device_id; c->stream = stream; c->owns_stream = owns; c->scratch = nullptr; c->scratch_bytes = 0; c->stage = nullptr; c->stage_bytes = 0; c->pinned = nullptr; c->pinned_bytes = 0;
     c->rng_scratch = nullptr; c->rng_scratch_bytes = 0; c->rows_scratch = nullptr; c->rows_scratch_bytes = 0; c->run_scratch = nullptr; c->run_scratch_bytes = 0; c->tape_draws = -1; c->small_scratch = nullptr; c->k2b_screen = 1; c->k2b_scratch = nullptr; c->k2b_scratch_bytes = 0;
-    c->ekf_variant = 0; c->synth_variant = 0; c->block_kernel = -1; c->duo_kernel = -1; c->lane_min_traj = 32768; c->poison = -1; c->tail_scan_stages = 1;
+    c->ekf_variant = 0; c->synth_variant = 0; c->block_kernel = -1; c->duo_kernel = -1; c->lane_min_traj = 32768; c->poison = -1; c->tail_scan_stages = 1; c->early_variances = -1;
     c->ransac_early_exit = 0; c->ransac_probe_trials = 64; c->prefilter_first_batch = 1; c->prefilter_speculate = 1; c->prefilter_miss_batch = 4;
     // the fused chains fit the rows main_process_gui hands to its fit (ref :973-998) under the reference's CONFIG defaults (:34, :53, :37)
     // unless the caller says otherwise (gsf_set_sim3_rows): a raw C caller of gsf_fuse_pipeline_* gets steps 3-5 as the reference runs them
@@ -354,6 +354,10 @@ int gsf_set_option(gsf_ctx* ctx, const char* key, int64_t value)
     if (strcmp(key, "duo_kernel") == 0) {
         if (value < -1 || value > 1) { set_error("gsf_set_option: duo_kernel must be -1 (automatic), 0 (one wave) or 1 (two-wave blocks)"); return GSF_ERR_INVALID_ARG; }
         ctx->duo_kernel = (int)value; return GSF_OK;
+    }
+    if (strcmp(key, "early_variances") == 0) {
+        if (value < -1 || value > 1) { set_error("gsf_set_option: early_variances must be -1 (automatic), 0 (never) or 1 (always where the build applies); the results are the same bits"); return GSF_ERR_INVALID_ARG; }
+        ctx->early_variances = (int)value; return GSF_OK;
     }
     if (strcmp(key, "tail_scan_stages") == 0) {
         if (value != 0 && value != 1) { set_error("gsf_set_option: tail_scan_stages must be 1 (the scans of a short last chunk run only the stages that reach its lanes, default) or 0 (always six stages); the results are the same bits"); return GSF_ERR_INVALID_ARG; }

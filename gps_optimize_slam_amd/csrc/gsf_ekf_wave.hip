@@ -57,6 +57,14 @@ GSF_WAVE_TAIL_KERNEL(WAVE_TAIL_FULL)
 // mostly idle -- wave 1 computes the variances of EVERY chunk (they depend on stamps and availability only, not on the fit) into
 // LDS; after one block barrier wave 0 runs the chunk loop without its two Moebius scans (-28 % instructions per chunk).
 // Same functions, same operands, same order as the one-wave kernel: bit-identical results.
+// Where the early-variance build is taken without being asked for: 1 000..1 024 tracks of 256..384 poses.  The bounds come from a sweep
+// of plain bench runs with the option at 0 and at 1 (HISTORY.md, "Early variances", holds every figure): below 1 000 tracks nothing was
+// gained (the launch does not fill the chip and does not end with a wave that gained); at 1 000 tracks lengths below 256 poses gained
+// 0.05-0.13 us, at or inside the run-to-run spread; 1 000 and 1 024 tracks gained 0.17-0.55 us over 256..384 poses; 1 536 tracks gained at
+// 271 poses but were measured at that length only.  Everything outside the measured wins stays on the one-wave kernel.
+#ifndef GSF_EARLY_AUTO_RULE
+#define GSF_EARLY_AUTO_RULE(B_, N_) ((B_) >= 1000 && (B_) <= 1024 && (N_) >= 256 && (N_) <= 384)
+#endif
 #ifndef GSF_DUO_ROLE_SHIFT
 #define GSF_DUO_ROLE_SHIFT 2        // measured best of 0..3 at 1 000 tracks (22.6 vs 23.1-23.2 us; 23.6 us without the helper)
 #endif
@@ -119,7 +127,15 @@ int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double*
     // 19.4 vs 18.9 us at 512, 20.9 vs 19.5 us at 1 000 (every SIMD then holds a main wave and the helper only competes with it)
     // -- automatic = up to 256 tracks.  The four-trajectory-per-block form of round 2 (main and helper of a trajectory forced onto
     // one SIMD) lost its edge with the shorter fit (20.2 vs 19.5 us at 1 000) and lives in tools/experiments/ now.
-    if (pipeline && !offsets && ctx->duo_kernel != 0 && N > 64 && N <= 640 && (ctx->duo_kernel == 1 || (ctx->duo_kernel == -1 && B <= 256))) {
+    // Short tracks of the fused pipeline under the default noise layout: the one-wave build that forms the FIRST chunk's variances while
+    // the track's rows are still in flight, so that this chunk runs without its Moebius scans (gsf_ekf_wave_early.hip).  Bit-identical to
+    // the kernel below, so the choice may depend on B.  gsf_set_option "early_variances": -1 automatic, 0 never, 1 always where the build
+    // applies (a forced two-wave build goes first; the automatic two-wave range, B <= 256, is kept by the automatic rule).
+    const bool ev_applies = pipeline && xy && !offsets && N > 64 && N <= 384 && B <= 2048;
+    const bool ev_forced = ev_applies && ctx->early_variances == 1 && ctx->duo_kernel != 1;
+    const bool ev_auto = ev_applies && ctx->early_variances == -1 && ctx->duo_kernel != 1 && !(ctx->duo_kernel == -1 && B <= 256) &&
+                         GSF_EARLY_AUTO_RULE(B, N);
+    if (!ev_forced && pipeline && !offsets && ctx->duo_kernel != 0 && N > 64 && N <= 640 && (ctx->duo_kernel == 1 || (ctx->duo_kernel == -1 && B <= 256))) {
         const int stride = (int)((N + 1) & ~(int64_t)1);
 #define GSF_LAUNCH_DUO_A(X_, A_) hipLaunchKernelGGL((ekf_wave_duo_kernel<true, X_>), dim3((unsigned)B), dim3(128), (size_t)stride * 9 * sizeof(double), ctx->stream, A_, k, stride)
 #define GSF_LAUNCH_DUO(X_) do { if (tail == 4) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<4>{ a }); else if (tail == 5) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<5>{ a }); else if (tail == WAVE_TAIL_FULL) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<WAVE_TAIL_FULL>{ a }); else GSF_LAUNCH_DUO_A(X_, a); } while (0)
@@ -129,6 +145,8 @@ int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double*
         GSF_HIP(hipGetLastError());
         return GSF_OK;
     }
+    if (ev_forced || ev_auto)
+        return launch_ekf_wave_early(ctx, tail, ts, pos, quat, gps, valid, cfg, B, N, R, t, s, pos_out, quat_out, status);
     {
         // up to 2 048 waves (two per SIMD) the build with inlined cold blocks costs no occupancy; same arithmetic, same bits
         const bool small = B <= 2048;

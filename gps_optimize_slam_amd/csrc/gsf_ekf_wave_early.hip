@@ -1,0 +1,211 @@
+// gsf_ekf_wave_early.hip -- the fused pipeline's one-wave kernel for SHORT tracks (64 < N <= 384, equal lengths, the default noise layout)
+// with the variances of its first chunk(s) computed EARLY: while the input burst of the fit is in flight.
+//
+// The one-wave kernel (gsf_ekf_wave.hip) asks for the track's rows and then issues nothing until they are back; its chunk loop then runs
+// the two Moebius scans of the variance recursion in every chunk.  That recursion depends on the stamps and on which fixes are used --
+// nine of the ~70 bytes per pose the burst moves.  This build
+//   1. requests the stamps and mask bytes of EVERY chunk first, then the fix columns, the SLAM positions and chunk 0's quaternions
+//      (vmcnt retires loads in issue order: the first columns asked for are the first ones back -- measured ~3 000 cycles ahead of the last);
+//   2. waits for stamps and mask bytes ALONE and takes a set mask byte to mean a usable fix (true of every row the generator, the loaders
+//      and time_align_kernel produce; a NaN fix under a set mask byte is the reference's demotion quirk, see 4);
+//   3. runs the local scans of the first GSF_EARLY_CHUNKS chunks side by side in one basic block, applies the carried variance chunk after
+//      chunk and writes P_f, P_p and the gain of their poses into LDS, in the layout of the two-wave kernel's helper.  Only what fits the
+//      shadow of the burst is done here: a chunk's scans are ~1 400-1 700 cycles of issue, and every cycle past the arrival of the rows
+//      delays the fit by as much as the chunk loop gains (all chunks early: +1.3 us; HISTORY.md, "Early variances");
+//   4. runs the fit on the rows it requested in 1 (the fit passes take them as RoundRows, nothing is loaded twice, pose 0 comes from lane 0)
+//      and learns from the fit pass's exact validity masks whether a row of those chunks has its mask byte set and a NaN in its fix.  If
+//      so those chunks' part of the table is formed again from memory, with the NaN test, wave-uniformly;
+//   5. runs wave_serial_chunks<PIPELINE, PREVAR = true, ..., PVCHUNKS>: the first chunks read the table as the two-wave kernel's main wave
+//      does, the chunks behind them run their scans as the one-wave kernel does.  There is one chunk loop per build, chosen by nothing.
+// One wave per block: no barrier, no wait on another wave; a wave's LDS operations complete in order.
+// Same functions on the same operands in the same order as the one-wave kernel -- the guarantee the two-wave build gives -- so every
+// output byte is the same.  The builds are OVERLOADS of ekf_wave_kernel<PIPELINE, SMALLBATCH, AXMODE> (the build travels in the
+// argument's type, as WaveArgsTail does), keyed by the number of chunks and by the sizing of the last chunk's scans.
+// The table holds the early chunks only: 9 x 64 x GSF_EARLY_CHUNKS x 8 bytes of dynamic LDS, 4.5 KB for one chunk.
+#include "gsf_wave_common.hpp"
+
+using namespace gsf;
+
+namespace {
+
+static_assert(GSF_ROWS_ROUND == 6, "the early-variance build hands the fit passes ONE round of six chunks");
+
+// How many chunks' variances are formed early (never the last chunk's).  Measured at 1 000 x 271, plain bench, us per step: parent 17.38,
+// one chunk 16.94, two 17.65, three 18.86, all five 18.8 (HISTORY.md, "Early variances").
+#ifndef GSF_EARLY_CHUNKS
+#define GSF_EARLY_CHUNKS 1
+#endif
+template <int NCH, int TAILNS> struct WaveArgsEarly { WaveArgs a; int pv_stride; };
+
+template <bool PIPELINE, int AXMODE, int NCH, int TAILNS>
+__device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConfig& cfg, const int pv_stride, const int64_t b, const int lane)
+{
+    static_assert(PIPELINE && AXMODE == 1 && NCH >= 2 && NCH <= 6, "fused pipeline, x and y share their noise, two to six chunks");
+    constexpr int NE = GSF_EARLY_CHUNKS < NCH - 1 ? GSF_EARLY_CHUNKS : NCH - 1;   // chunks whose variances are formed early: full ones, never the last
+    extern __shared__ double gsf_pv[];
+    GSF_STAMP(0);
+    const int64_t N = a.N, base = b * N;                                  // equal lengths: 64 (NCH - 1) < N <= 64 NCH (the launcher's choice of build)
+    int Ni = (int)N;
+    asm volatile("" : "+s"(Ni));
+    const double* __restrict__ tsb = a.ts + base;
+    const double* __restrict__ posb = a.pos + base * 3;
+    const double* __restrict__ quatb = a.quat + base * 4;
+    const double* __restrict__ gpsb = a.gps + base * 3;
+    const uint8_t* __restrict__ valb = a.valid + base;
+
+    // ---- 1. the whole track is ONE round of the fit's row pass: requested here, in the order in which it is needed
+    int stride = pv_stride; double cPx = cfg.P0[0], cPz = cfg.P0[2];      // (fetched here, with the other kernel arguments: see 3)
+    asm volatile("" : "+s"(stride), "+s"(cPx), "+s"(cPz));
+    RoundRows<6> rr;
+    int il[NCH];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) { const int i = 64 * k + lane; il[k] = (k < NCH - 1 || i < Ni) ? i : Ni - 1; }
+    uint8_t vb[NCH];                                                      // (widened below the last request: the conversion is a use, and a use waits)
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) { rr.pt[k] = tsb[il[k]]; vb[k] = valb[il[k]]; }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) { rr.pz[k][0] = gpsb[il[k] * 3]; rr.pz[k][1] = gpsb[il[k] * 3 + 1]; rr.pz[k][2] = gpsb[il[k] * 3 + 2]; }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) { rr.pa[k][0] = posb[il[k] * 3]; rr.pa[k][1] = posb[il[k] * 3 + 1]; rr.pa[k][2] = posb[il[k] * 3 + 2]; }
+    // chunk 0 of the chunk loop: its stamp, position, fix and mask byte ARE the round's first chunk; only the quaternion is its own
+    ChunkIn nxt;
+    nxt.q = Quat{ __builtin_nontemporal_load(&quatb[il[0] * 4]), __builtin_nontemporal_load(&quatb[il[0] * 4 + 1]),
+                  __builtin_nontemporal_load(&quatb[il[0] * 4 + 2]), __builtin_nontemporal_load(&quatb[il[0] * 4 + 3]) };
+#pragma unroll
+    for (int k = NCH; k < 6; ++k) {                                       // (chunks past the end of the track, as the passes' own loads leave them)
+        rr.pa[k][0] = rr.pa[k][1] = rr.pa[k][2] = 0.0; rr.pz[k][0] = rr.pz[k][1] = rr.pz[k][2] = 0.0; rr.pt[k] = 0.0; rr.pv[k] = 0u;
+    }
+    __builtin_amdgcn_sched_barrier(0);                                   // ... and stay requested HERE: nothing below is scheduled above them
+
+    // ---- 2. stamps and mask bytes have arrived (the columns behind them are still in flight)
+    // (each byte has ONE use, its widening, which then folds into the load; and the widened value is opaque from here on.  Left transparent, the
+    // compiler compared the raw byte in one place and widened it in another, the widening became an instruction right behind the byte's load,
+    // and the wave waited for that load before it had requested the other columns.)
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) { uint32_t w = vb[k]; asm volatile("" : "+v"(w) :: "memory"); rr.pv[k] = w; }
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) asm volatile("" :: "v"(rr.pt[k]) : "memory");
+    GSF_STAMP(14);                                                       // stamps and mask bytes have arrived
+    double dt[NE]; bool stepping[NE], spec[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {                                        // (full chunks, all of them: NE < NCH)
+        stepping[k] = (64 * k + lane) != 0;
+        const double c_t = (k == 0) ? lane_bcast(rr.pt[0], 0) : lane_bcast(rr.pt[k - 1], 63);
+        dt[k] = fmax(1e-6, rr.pt[k] - prev_lane(c_t, rr.pt[k]));         // ref :865
+        spec[k] = stepping[k] && rr.pv[k] != 0u;                          // the fix is taken to be usable (ref :867-869 without the NaN test)
+    }
+
+    // ---- 3. the local scans of the first NE chunks, side by side (2 NE independent chains; a lone wave issues a DPP-move + FMA chain every
+    // 7.4 cycles alone and every 4.5 with four chains beside it, tools/ubench/ilp.hip); then the carry, chunk after chunk; the table goes to LDS.
+    // (The constants of the block are fetched in front of it and pinned: left alone, the register allocator re-fetched them from the kernel
+    // arguments in front of every scan, a dozen scalar-cache round trips with nothing to cover them.)
+    double qx = cfg.Qps[0], rx = cfg.Rm[0], qz = cfg.Qps[2], rz = cfg.Rm[2];
+    asm volatile("" : "+s"(qx), "+s"(rx), "+s"(qz), "+s"(rz));
+    Moebius mx[NE], mz[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        mx[k] = variance_scan<6>(qx, rx, dt[k], stepping[k], spec[k]);
+        mz[k] = variance_scan<6>(qz, rz, dt[k], stepping[k], spec[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+        const int i = 64 * k + lane;
+        const AxisVar vx = variance_finish(mx[k], qx, rx, dt[k], cPx);
+        const AxisVar vz = variance_finish(mz[k], qz, rz, dt[k], cPz);
+        gsf_pv[0 * stride + i] = vx.Pf; gsf_pv[1 * stride + i] = vx.Pm; gsf_pv[2 * stride + i] = vx.kg;
+        gsf_pv[3 * stride + i] = vx.Pf; gsf_pv[4 * stride + i] = vx.Pm; gsf_pv[5 * stride + i] = vx.kg;   // y repeats x
+        gsf_pv[6 * stride + i] = vz.Pf; gsf_pv[7 * stride + i] = vz.Pm; gsf_pv[8 * stride + i] = vz.kg;
+        cPx = lane_bcast(vx.Pf, 63); cPz = lane_bcast(vz.Pf, 63);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    GSF_STAMP(13);                                                       // variance table written (the timing tools run five-chunk tracks: 13 is free there)
+
+    // ---- 4. the fit, on the rows requested above
+    nxt.t = rr.pt[0]; nxt.v = rr.pv[0];
+    nxt.p = Vec3{ rr.pa[0][0], rr.pa[0][1], rr.pa[0][2] };
+    nxt.z = Vec3{ rr.pz[0][0], rr.pz[0][1], rr.pz[0][2] };
+    Vec3 p0; Quat q0; int32_t fit = 0;
+    rr.nearly = NE;
+    { const Quat q0l = lane_bcast(nxt.q, 0); rr.q0[0] = q0l.x; rr.q0[1] = q0l.y; rr.q0[2] = q0l.z; rr.q0[3] = q0l.w; }
+    u64 miss = 0ull;                                                     // rows on which the assumption of 2 does not hold, from the fit pass's own masks
+    if (!wave_prelude<PIPELINE, true>(a, b, base, N, lane, p0, q0, fit, &rr, &miss)) return;   // (fit None, bad pose-0 quaternion: the table is never read)
+    if (miss != 0ull) {
+        // a NaN fix under a set mask byte in the first NE chunks (wave-uniform, rare): their part of the table again, from memory, with the
+        // NaN test -- the flags, the dt and the variance_chunk() of the chunk loop, as the two-wave kernel's helper forms them
+        asm volatile("" ::: "memory");                                   // (a real branch, not if-conversion)
+        double cP0 = cfg.P0[0], cP1 = cfg.P0[1], cP2 = cfg.P0[2], c_t = tsb[0];
+#pragma nounroll
+        for (int k = 0; k < NE; ++k) {
+            const int i = 64 * k + lane;                                  // (full chunks: every lane holds a pose of the track)
+            const double t = tsb[i], z0 = gpsb[i * 3], z1 = gpsb[i * 3 + 1], z2 = gpsb[i * 3 + 2];
+            const bool step = i != 0, avail = step && valb[i] != 0 && !(isnan(z0) || isnan(z1) || isnan(z2));   // ref :867-869
+            const double dtk = fmax(1e-6, t - prev_lane(c_t, t));       // ref :865
+            AxisVar v0, v1, v2;
+            variance_chunk<6>(cfg, 0, -1, dtk, step, avail, cP0, cP1, cP2, v0, v1, v2);   // (AXMODE 1: y repeats x, z has its own scan)
+            gsf_pv[0 * stride + i] = v0.Pf; gsf_pv[1 * stride + i] = v0.Pm; gsf_pv[2 * stride + i] = v0.kg;
+            gsf_pv[3 * stride + i] = v1.Pf; gsf_pv[4 * stride + i] = v1.Pm; gsf_pv[5 * stride + i] = v1.kg;
+            gsf_pv[6 * stride + i] = v2.Pf; gsf_pv[7 * stride + i] = v2.Pm; gsf_pv[8 * stride + i] = v2.kg;
+            cP0 = lane_bcast(v0.Pf, 63); cP1 = lane_bcast(v1.Pf, 63); cP2 = lane_bcast(v2.Pf, 63); c_t = lane_bcast(t, 63);
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    // one wave per block: its LDS operations complete in order, no barrier
+    GSF_STAMP(6);
+
+    // ---- 5. the chunk loop: its first NE chunks as the two-wave kernel's main wave runs them, the rest as the one-wave kernel does
+    wave_serial_chunks<PIPELINE, true, true, 1, AXMODE, TAILNS, NE>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, gsf_pv, stride);
+}
+
+#define GSF_WAVE_EARLY_KERNEL(C_, T_)                                                                                                 \
+    template <bool PIPELINE, bool SMALLBATCH, int AXMODE>                                                                             \
+    __global__ __launch_bounds__(64, 1) void ekf_wave_kernel(WaveArgsEarly<C_, T_> w, EkfConfig cfg)                                  \
+    {                                                                                                                                 \
+        static_assert(SMALLBATCH, "a small-batch build");                                                                             \
+        wave_early_body<PIPELINE, AXMODE, C_, T_>(w.a, cfg, w.pv_stride, (int64_t)blockIdx.x, (int)threadIdx.x);                      \
+    }
+#define GSF_WAVE_EARLY_KERNELS(C_) GSF_WAVE_EARLY_KERNEL(C_, 4) GSF_WAVE_EARLY_KERNEL(C_, 5) GSF_WAVE_EARLY_KERNEL(C_, 6) GSF_WAVE_EARLY_KERNEL(C_, WAVE_TAIL_FULL)
+GSF_WAVE_EARLY_KERNELS(2)
+GSF_WAVE_EARLY_KERNELS(3)
+GSF_WAVE_EARLY_KERNELS(4)
+GSF_WAVE_EARLY_KERNELS(5)
+GSF_WAVE_EARLY_KERNELS(6)
+#undef GSF_WAVE_EARLY_KERNELS
+#undef GSF_WAVE_EARLY_KERNEL
+
+}  // namespace
+
+namespace gsf {
+
+
+// fused pipeline, x and y sharing their noise and z not, equal lengths, 64 < N <= 384 (launch_ekf_wave has checked all of it);
+// tail = wave_tail_stages(N), or 6 for the build without sized scans
+int launch_ekf_wave_early(gsf_ctx* ctx, int tail, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                          const gsf_ekf_config* cfg, int64_t B, int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out,
+                          int32_t* status)
+{
+    GSF_REQUIRE(N > 64 && N <= 384 && B > 0 && B <= 0x7fffffff, "the early-variance build takes equal-length tracks of 65..384 poses");
+    const WaveArgs a{ ts, pos, quat, gps, valid, nullptr, nullptr, R, t, s, pos_out, quat_out, status, B, N, nullptr, ctx->fit_rows };
+    const EkfConfig k = to_core(cfg);
+    const int nch = (int)((N + 63) / 64);
+    GSF_REQUIRE(tail == 6 || tail == wave_tail_stages(N), "scan sizing does not belong to the track length");
+    const int stride = 64 * (GSF_EARLY_CHUNKS < nch - 1 ? GSF_EARLY_CHUNKS : nch - 1);   // poses the table holds (the kernel's NE chunks)
+    const size_t lds = (size_t)stride * 9 * sizeof(double);
+#define GSF_LAUNCH_EARLY_A(C_, T_) hipLaunchKernelGGL((ekf_wave_kernel<true, true, 1>), dim3((unsigned)B), dim3(64), lds, ctx->stream, WaveArgsEarly<C_, T_>{ a, stride }, k)
+#define GSF_LAUNCH_EARLY(C_) do { if (tail == 4) GSF_LAUNCH_EARLY_A(C_, 4); else if (tail == 5) GSF_LAUNCH_EARLY_A(C_, 5); else if (tail == WAVE_TAIL_FULL) GSF_LAUNCH_EARLY_A(C_, WAVE_TAIL_FULL); else GSF_LAUNCH_EARLY_A(C_, 6); } while (0)
+    switch (nch) {
+    case 2: GSF_LAUNCH_EARLY(2); break;
+    case 3: GSF_LAUNCH_EARLY(3); break;
+    case 4: GSF_LAUNCH_EARLY(4); break;
+    case 5: GSF_LAUNCH_EARLY(5); break;
+    default: GSF_LAUNCH_EARLY(6); break;
+    }
+#undef GSF_LAUNCH_EARLY
+#undef GSF_LAUNCH_EARLY_A
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
+}
+
+const char* wave_early_build_info() { return GSF_TU_BUILD_INFO("gsf_ekf_wave_early.hip"); }
+
+}  // namespace gsf

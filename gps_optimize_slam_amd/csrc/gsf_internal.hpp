@@ -42,6 +42,7 @@ struct gsf_ctx {
     int prefilter_first_batch; // trials the pre-filter chain draws and scores before its first look at scikit-learn's stopping rule (gsf_set_option "prefilter_first_batch")
     int ransac_probe_trials; // ... trials the early-exit probe draws and scores itself before the wide kernels take the rest (gsf_set_option "ransac_probe_trials")
     int duo_kernel;        // two-wave pipeline kernel for small batches (gsf_set_option "duo_kernel"): -1 automatic, 0 never, 1 always
+    int early_variances;   // one-wave pipeline build for short tracks with the first chunk's variances computed under the input burst (gsf_set_option "early_variances"): -1 automatic, 0 never, 1 always where it applies (same bits)
     int tail_scan_stages;  // wave kernels: scans of a short last chunk sized by its last active lane (gsf_set_option "tail_scan_stages"): 1 default, 0 always six stages (same bits)
     gsf::FitRows fit_rows; // rows of the fused chains' Sim3 fit (gsf_set_sim3_rows); mode 0 = all valid rows
     int64_t poison;        // tests: every workspace is filled with this 64-bit word when the option is set and after it grows (gsf_set_option "poison_workspaces"); -1 = off
@@ -86,6 +87,7 @@ struct Idx {
 const char* wave_small_build_info();
 const char* wave_big_build_info();
 const char* wave_block_build_info();
+const char* wave_early_build_info();
 
 int ensure_scratch(gsf_ctx* ctx, size_t bytes);
 int ensure_rng_scratch(gsf_ctx* ctx, size_t bytes);
@@ -105,6 +107,11 @@ int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double*
 int launch_ekf_wave_big(gsf_ctx* ctx, bool pipeline, bool xy, const double* ts, const double* pos, const double* quat, const double* gps,
                         const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B, int64_t N,
                         double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status, const int64_t* offsets);
+
+// the early-variance builds of the fused pipeline's one-wave kernel (gsf_ekf_wave_early.hip): equal lengths, 64 < N <= 384, default noise layout
+int launch_ekf_wave_early(gsf_ctx* ctx, int tail, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                          const gsf_ekf_config* cfg, int64_t B, int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out,
+                          int32_t* status);
 
 // workgroup-per-trajectory K4 / fused pipeline (gsf_ekf_block.hip): one wave per 64-pose chunk, every input byte read once
 bool ekf_block_applies(int64_t N, const int64_t* offsets);

@@ -458,10 +458,18 @@ __device__ __forceinline__ bool rows_gap_in_chunk(RowScan& rs, const u64 m, cons
 #ifndef GSF_ROWS_ROUND
 #define GSF_ROWS_ROUND 6                                                  // chunks per round of this pass (the big-batch build takes fewer: registers)
 #endif
-template <int MOM_ROUND>
+// The rows of a track's ONE round as the caller requested them itself, ahead of the pass (gsf_ekf_wave_early.hip: a track of at most
+// R chunks, its stamps and mask bytes asked for first); chunks past the end of the track hold zeros, as the passes' own loads leave them.
+// PRE: the pass takes its first round from there instead of loading it (a repeated attempt of the reference's rule loads as before) and
+// reports the rows after pose 0 whose mask byte is set but whose fix holds a NaN -- the rows on which "mask byte set" and "fix used"
+// differ (*miss_out, one lane mask OR-ed over the chunks).  Same values in the same places: the sums are the same bits.
+// q0: pose 0's quaternion as stored (wave-uniform), which the prelude otherwise fetches itself.
+// nearly: the chunks whose variances were formed under that assumption (the report covers those).
+template <int R> struct RoundRows { double pa[R][3], pz[R][3], pt[R]; uint32_t pv[R]; double q0[4]; int nearly; };
+template <int MOM_ROUND, bool PRE = false>
 __device__ __forceinline__ void fit_moments_reference_rows(const WaveArgs& a, const int64_t b, const int64_t base, const int64_t N, const int lane,
                                                            const double as0, const double as1, const double as2, double* sums, double* bs_,
-                                                           int32_t& rows_flag)
+                                                           int32_t& rows_flag, const RoundRows<MOM_ROUND>* pre = nullptr, u64* miss_out = nullptr)
 {
     const double* __restrict__ tsb = a.ts + base;
     const double* __restrict__ posb = a.pos + base * 3;
@@ -483,6 +491,14 @@ __device__ __forceinline__ void fit_moments_reference_rows(const WaveArgs& a, co
         double Sab[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
         for (int c0 = 0; c0 < Ni && c0 < row_end; c0 += 64 * MOM_ROUND) {
             double pa[MOM_ROUND][3], pz[MOM_ROUND][3], pt[MOM_ROUND]; uint32_t pv[MOM_ROUND];
+            if (PRE && attempt == 0) {                                    // (PRE: the track is one round long, and the caller holds it)
+#pragma unroll
+                for (int k = 0; k < MOM_ROUND; ++k) {
+                    pa[k][0] = pre->pa[k][0]; pa[k][1] = pre->pa[k][1]; pa[k][2] = pre->pa[k][2];
+                    pz[k][0] = pre->pz[k][0]; pz[k][1] = pre->pz[k][1]; pz[k][2] = pre->pz[k][2];
+                    pt[k] = pre->pt[k]; pv[k] = pre->pv[k];
+                }
+            } else {
 #pragma unroll
             for (int k = 0; k < MOM_ROUND; ++k) {
                 if (c0 + 64 * k < Ni) {                                   // wave-uniform
@@ -494,6 +510,7 @@ __device__ __forceinline__ void fit_moments_reference_rows(const WaveArgs& a, co
                     pa[k][0] = pa[k][1] = pa[k][2] = 0.0; pz[k][0] = pz[k][1] = pz[k][2] = 0.0; pt[k] = 0.0; pv[k] = 0u;
                 }
             }
+            }
 #pragma unroll
             for (int k = 0; k < MOM_ROUND; ++k) asm volatile("" : "+v"(pv[k]));   // (see wave_prelude: one memory round trip per round)
             // validity of the round's rows as lane masks (rows of the track, mask byte set, fix free of NaN)
@@ -501,6 +518,12 @@ __device__ __forceinline__ void fit_moments_reference_rows(const WaveArgs& a, co
 #pragma unroll
             for (int k = 0; k < MOM_ROUND; ++k)
                 mok[k] = mask_first(Ni - (c0 + 64 * k)) & mask_nonzero(pv[k]) & mask_not_nan(pz[k][0]) & mask_not_nan(pz[k][1]) & mask_not_nan(pz[k][2]);
+            if (PRE && attempt == 0) {
+                u64 ms = 0ull;
+#pragma unroll
+                for (int k = 0; k < MOM_ROUND; ++k) if (k < pre->nearly) ms |= mask_first(Ni - 64 * k) & mask_nonzero(pv[k]) & ~mok[k] & ~(k == 0 ? 1ull : 0ull);
+                *miss_out = ms;
+            }
             GSF_STAMP(1);                                                 // the round's rows have arrived
             if (!have_shift && (mok[0] & 1ull) != 0ull) {                 // the usual track: its very first row of the round is valid
                 bs0 = lane_bcast(pz[0][0], 0); bs1 = lane_bcast(pz[0][1], 0); bs2 = lane_bcast(pz[0][2], 0);
@@ -629,9 +652,9 @@ __device__ __forceinline__ void fit_moments_reference_rows(const WaveArgs& a, co
 // Initial pose of trajectory b: either the caller's Sim3-aligned pose 0, or (PIPELINE) the Umeyama fit on the rows with valid
 // finite GNSS + Sim3 of pose 0.  Returns false (after writing NaN outputs / status) when the fit is None or pose 0's quaternion
 // is invalid -- wave-uniformly.
-template <bool PIPELINE>
+template <bool PIPELINE, bool PRE = false>
 __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b, const int64_t base, const int64_t N, const int lane,
-                                             Vec3& p0_out, Quat& q0_out, int32_t& fit_out)
+                                             Vec3& p0_out, Quat& q0_out, int32_t& fit_out, const RoundRows<6>* pre = nullptr, u64* miss_out = nullptr)
 {
     const double* __restrict__ posb = a.pos + base * 3;
     const double* __restrict__ quatb = a.quat + base * 4;
@@ -647,8 +670,11 @@ __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b,
         // The rows are read in rounds of MOM_ROUND chunks with every load of a round issued before the first use, so a 271-pose
         // track (the small-batch, latency-bound case) pays ONE memory round trip for the whole pass instead of one per chunk.
         // The GNSS-side shift (first valid finite fix, wave-uniform) is found in the same pass: nothing is accumulated before it.
-        const double as0 = posb[0], as1 = posb[1], as2 = posb[2];
-        const Quat qraw0{ quatb[0], quatb[1], quatb[2], quatb[3] };      // pose 0's quaternion: requested here, used after the fit
+        // (PRE: pose 0 sits in lane 0 of the rows the caller holds -- no request of its own, whose round trip nothing would cover by now)
+        const double as0 = PRE ? lane_bcast(pre->pa[0][0], 0) : posb[0], as1 = PRE ? lane_bcast(pre->pa[0][1], 0) : posb[1],
+                     as2 = PRE ? lane_bcast(pre->pa[0][2], 0) : posb[2];
+        const Quat qraw0 = PRE ? Quat{ pre->q0[0], pre->q0[1], pre->q0[2], pre->q0[3] }
+                               : Quat{ quatb[0], quatb[1], quatb[2], quatb[3] };   // pose 0's quaternion: requested here, used after the fit
         constexpr int MOM_ROUND = 6;
         // ONE closed form behind either moments pass (the two row rules differ in which rows they sum, not in what happens to the sums)
         double sums[17], bs_[3]; int32_t rows_flag = 0;
@@ -657,7 +683,8 @@ __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b,
 #else
         if (a.rows.mode != 0) {                                           // wave-uniform: the reference's row choice (ref :973-998)
 #endif
-            fit_moments_reference_rows<GSF_ROWS_ROUND>(a, b, base, N, lane, as0, as1, as2, sums, bs_, rows_flag);
+            fit_moments_reference_rows<GSF_ROWS_ROUND, PRE>(a, b, base, N, lane, as0, as1, as2, sums, bs_, rows_flag,
+                                                            (const RoundRows<GSF_ROWS_ROUND>*)pre, miss_out);   // (PRE: GSF_ROWS_ROUND is 6, checked by the caller)
         } else {
             double bs0 = 0.0, bs1 = 0.0, bs2 = 0.0;
             bool have_shift = false;
@@ -666,6 +693,14 @@ __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b,
             double Sab[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
             for (int64_t c0 = 0; c0 < N; c0 += 64 * MOM_ROUND) {
                 double pa[MOM_ROUND][3], pz[MOM_ROUND][3]; uint32_t pv[MOM_ROUND];
+                if constexpr (PRE) {                                          // (the track is one round long, and the caller holds it)
+#pragma unroll
+                    for (int k = 0; k < MOM_ROUND; ++k) {
+                        pa[k][0] = pre->pa[k][0]; pa[k][1] = pre->pa[k][1]; pa[k][2] = pre->pa[k][2];
+                        pz[k][0] = pre->pz[k][0]; pz[k][1] = pre->pz[k][1]; pz[k][2] = pre->pz[k][2];
+                        pv[k] = pre->pv[k];
+                    }
+                } else {
 #pragma unroll
                 for (int k = 0; k < MOM_ROUND; ++k) {
                     if (c0 + 64 * k < N) {                                    // wave-uniform
@@ -677,6 +712,7 @@ __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b,
                         pa[k][0] = pa[k][1] = pa[k][2] = 0.0; pz[k][0] = pz[k][1] = pz[k][2] = 0.0; pv[k] = 0u;
                     }
                 }
+                }
                 // the mask bytes stay opaque until every load of the round is issued: left alone, the compiler turns each byte into a lane
                 // mask right behind its load (one VGPR less) and thereby waits for memory once per 64 rows instead of once per round
 #pragma unroll
@@ -686,6 +722,12 @@ __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b,
                 for (int k = 0; k < MOM_ROUND; ++k)
                     mok[k] = mask_first((int)(N - (c0 + 64 * k) > 64 ? 64 : N - (c0 + 64 * k))) & mask_nonzero(pv[k]) & mask_not_nan(pz[k][0]) & mask_not_nan(pz[k][1]) &
                              mask_not_nan(pz[k][2]);
+                if constexpr (PRE) {
+                    u64 ms = 0ull;
+#pragma unroll
+                    for (int k = 0; k < MOM_ROUND; ++k) if (k < pre->nearly) ms |= mask_first((int)N - 64 * k) & mask_nonzero(pv[k]) & ~mok[k] & ~(k == 0 ? 1ull : 0ull);
+                    *miss_out = ms;
+                }
                 GSF_STAMP(1);                                             // the round's rows have arrived
                 if (!have_shift && (mok[0] & 1ull) != 0ull) {             // the usual track: its very first row is valid
                     bs0 = lane_bcast(pz[0][0], 0); bs1 = lane_bcast(pz[0][1], 0); bs2 = lane_bcast(pz[0][2], 0);
@@ -857,7 +899,10 @@ template <> struct RingStore<0> {
 // TAILNS (4 | 5): the caller guarantees that the track's last chunk ends below lane 16 | 32 (wave_tail_stages); that chunk then runs
 // its scans with 4 | 5 stages (GSF_SCAN_STAGES_N: same bits).  TAILNS = 6: every chunk runs the six-stage body.  WAVE_TAIL_FULL: the caller
 // guarantees that N is a multiple of 64.
-template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6>
+// PVCHUNKS (early-variance build, gsf_ekf_wave_early.hip): only the first PVCHUNKS chunks -- full ones -- take their variances from the
+// table, the chunks behind them run their scans; 0: PREVAR holds for every chunk.
+template <bool V> struct FromTable { static constexpr bool value = V; };
+template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6, int PVCHUNKS = 0>
 __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfConfig& cfg, const int64_t b, const int lane, const int64_t base,
                                                    const int64_t N, const Vec3& p0, const Quat& q0, const int32_t fit,
                                                    typename NextChunk<GSF_WIDE(SMALLBATCH)>::type nxt,
@@ -913,8 +958,9 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
     bool cq_fresh = true;
     // One chunk: 64 poses starting at c0, L = last active lane.  NS (ScanStages<4 | 5 | 6>) = scan stages compiled into this instance of the
     // body: 6 is the full chunk; 4 and 5 serve a short last chunk (GSF_SCAN_STAGES_N).
-    auto chunk_body = [&](auto ns_tag, const int64_t c0, const int L) __attribute__((always_inline)) {
+    auto chunk_body = [&](auto ns_tag, auto pv_tag, const int64_t c0, const int L) __attribute__((always_inline)) {
         constexpr int NS = decltype(ns_tag)::value;
+        constexpr bool FROM_TABLE = PREVAR && decltype(pv_tag)::value;
         const int64_t i = c0 + lane;
         // Lane predicates that depend on the lane index alone are formed as 64-bit masks on the SCALAR unit and handed to the lanes with
         // inverse_ballot (a register copy): no compare / select / shift of the vector unit is spent on the outage structure.
@@ -1012,9 +1058,9 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         // ---- variances (ref :712-713, :723-731): scanned here, or -- PREVAR -- already computed by the helper wave (LDS)
         double Pf[3], Pm[3], kg[3];
 #ifdef GSF_EXP_HYBRID
-        if (PREVAR && (a).use_pv != 0) {
+        if (FROM_TABLE && (a).use_pv != 0) {
 #else
-        if (PREVAR) {
+        if (FROM_TABLE) {
 #endif
             const int64_t il = active ? i : N - 1;
 #pragma unroll
@@ -1206,14 +1252,27 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
     // In a sized kernel the loop's chunks are FULL ones by construction, so L = 63 is a constant there and the lane masks built from it
     // fold away -- measured, that is worth as much as the stages the last chunk skips (HISTORY.md, "Sized scans for a short last chunk").
     // (Three instances side by side in ONE loop, chosen per iteration, were measured first: the full chunk lost 130 cycles to them.)
-    if constexpr (TAILNS == 6) {
-        for (int64_t c0 = 0; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, c0, (int)((N - c0 < 64) ? (N - c0 - 1) : 63));
+    if constexpr (PVCHUNKS > 0) {
+        // (the caller guarantees more than PVCHUNKS chunks: the chunks that read the table are full ones, the rest is the loop of the kernel without a table)
+        int64_t c0 = 0;
+#pragma nounroll
+        for (; c0 < 64 * PVCHUNKS; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<true>{}, c0, 63);
+        if constexpr (TAILNS == 6) {
+            for (; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<false>{}, c0, (int)((N - c0 < 64) ? (N - c0 - 1) : 63));
+        } else if constexpr (TAILNS == WAVE_TAIL_FULL) {
+            for (; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<false>{}, c0, 63);
+        } else {
+            for (; c0 + 64 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<false>{}, c0, 63);
+            chunk_body(ScanStages<TAILNS>{}, FromTable<false>{}, c0, (int)(N - c0 - 1));
+        }
+    } else if constexpr (TAILNS == 6) {
+        for (int64_t c0 = 0; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<true>{}, c0, (int)((N - c0 < 64) ? (N - c0 - 1) : 63));
     } else if constexpr (TAILNS == WAVE_TAIL_FULL) {
-        for (int64_t c0 = 0; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, c0, 63);
+        for (int64_t c0 = 0; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<true>{}, c0, 63);
     } else {
         int64_t c0 = 0;
-        for (; c0 + 64 < N; c0 += 64) chunk_body(ScanStages<6>{}, c0, 63);
-        chunk_body(ScanStages<TAILNS>{}, c0, (int)(N - c0 - 1));
+        for (; c0 + 64 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<true>{}, c0, 63);
+        chunk_body(ScanStages<TAILNS>{}, FromTable<true>{}, c0, (int)(N - c0 - 1));
     }
     GSF_STAMP_FLUSH();
     if (lane == 0 && GSF_STATUS_PTR(a)) a.status[b] = (status | (c_prev_avail ? 0 : ST_ENDED_IN_OUTAGE)) | (PIPELINE ? (fit << 8) : 0);
