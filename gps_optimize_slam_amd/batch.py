@@ -971,3 +971,119 @@ def ekf_covariance_batch(batch, config=None, want_filtered=True):
     offsets = torch.arange(batch.B + 1, dtype=torch.int64, device=batch.ts.device) * batch.N
     return ekf_covariance_ragged(batch.ts.view(P), batch.quat.view(P, 4), batch.gps.view(P, 3), batch.valid.view(P), offsets, config=config,
                                  want_filtered=want_filtered)
+
+
+class PoseQuery:
+    """The fused track at query stamps (query_poses_ragged), flat over the M queries: pos (M,3), quat (M,4), flags (M,) uint8 of _lib.Q_* bits,
+    index (M,) int32 = the bracket's first pose relative to its track (-1: none), pose_flags (M,) uint8 or None = the _lib.POSE_* bits of
+    the bracket's poses or'ed, track_state (B,) int32 of _lib.QT_* bits (None for a call without queries), q_offsets (B+1,)."""
+
+    def __init__(self, pos, quat, flags, index, pose_flags, track_state, q_offsets):
+        self.pos, self.quat, self.flags, self.index, self.pose_flags = pos, quat, flags, index, pose_flags
+        self.track_state, self.q_offsets = track_state, q_offsets
+
+
+class GeorefPoints:
+    """Sensor points in the fused track's frame (georef_points_ragged): xyz (M,3), lonlatalt (M,3) rows [lon, lat, alt] or None, flags / index
+    / pose_flags / track_state / q_offsets as in PoseQuery."""
+
+    def __init__(self, xyz, lonlatalt, flags, index, pose_flags, track_state, q_offsets):
+        self.xyz, self.lonlatalt, self.flags, self.index, self.pose_flags = xyz, lonlatalt, flags, index, pose_flags
+        self.track_state, self.q_offsets = track_state, q_offsets
+
+
+def _query_args(name, ts, pos, quat, offsets, q_t, q_offsets, pose_flags, run_status):
+    B = _offsets_chk(offsets)
+    if _offsets_chk(q_offsets) != B:
+        raise ValueError(f"{name}: offsets and the query offsets must describe the same number of tracks")
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    M = int(q_t.shape[0]) if q_t.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(q_t, torch.float64, (M,), "query stamps")
+    if pose_flags is not None:
+        _chk(pose_flags, torch.uint8, (P,), "pose_flags")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    return B, P, M
+
+
+def _query_outputs(B, M, dev, want_pose_flags):
+    flags = torch.empty((M,), dtype=torch.uint8, device=dev)
+    index = torch.empty((M,), dtype=torch.int32, device=dev)
+    pf = torch.empty((M,), dtype=torch.uint8, device=dev) if want_pose_flags else None
+    state = torch.empty((B,), dtype=torch.int32, device=dev)
+    return flags, index, pf, state
+
+
+def _unread_rows(ts, pos, quat):
+    """a batch without a single pose: the entries want non-NULL arrays, which they then never read"""
+    z = torch.zeros((8,), dtype=torch.float64, device=ts.device)
+    return (z[:1], z[:3].view(1, 3), z[:4].view(1, 4)) if ts.numel() == 0 else (ts, pos, quat)
+
+
+def query_poses_ragged(ts, pos, quat, offsets, q_t, q_offsets, pose_flags=None, run_status=None, max_gap=0.0):
+    """The fused tracks at any stamps (gsf_pose_query_dev): ts (P,), pos (P,3), quat (P,4), offsets (B+1,) int64 as the ragged entries give
+    them; q_t (M,) query stamps in any order, q_offsets (B+1,) int64.  Between two poses the position is interpolated linearly and the
+    orientation by quaternion_nlerp (EKFGPSSLAM.py:94-105); a query on a pose's stamp returns that pose bit for bit; before the first /
+    after the last stamp, across a bracket wider than max_gap (> 0) and on an unusable track the rows are NaN and flags says why.
+    pose_flags (P,) uint8 = FusedCovariance.flags; run_status (B,) int32: tracks with run_status != 0 are not read.  Returns a PoseQuery."""
+    B, P, M = _query_args("query_poses_ragged", ts, pos, quat, offsets, q_t, q_offsets, pose_flags, run_status)
+    f = dict(dtype=torch.float64, device=ts.device)
+    out_pos, out_quat = torch.empty((M, 3), **f), torch.empty((M, 4), **f)
+    flags, index, pf, state = _query_outputs(B, M, ts.device, pose_flags is not None)
+    if M == 0:                                                           # the entry does nothing without queries: no track_state either
+        return PoseQuery(out_pos, out_quat, flags, index, pf, None, q_offsets)
+    ts_, pos_, quat_ = _unread_rows(ts, pos, quat)
+    check(_lib.load().gsf_pose_query_dev(context().handle, _p(ts_), _p(pos_), _p(quat_), _p(offsets), _p(run_status), _p(pose_flags), B, _p(q_t),
+                                         _p(q_offsets), M, float(max_gap), _p(out_pos), _p(out_quat), _p(flags), _p(index), _p(pf), _p(state)))
+    return PoseQuery(out_pos, out_quat, flags, index, pf, state, q_offsets)
+
+
+def georef_points_ragged(ts, pos, quat, offsets, pt_t, pt_xyz, pt_offsets, ext_q=None, ext_t=None, scale=None, pose_flags=None, run_status=None,
+                         max_gap=0.0, zone=None, south=None):
+    """Sensor points into the fused tracks' frame (gsf_georef_points_dev): pt_xyz (M,3) in the sensor frame stamped by pt_t (M,), pt_offsets
+    (B+1,) int64; ext_q (B,4) / ext_t (B,3) = sensor -> body per track (None: identity / zero), scale (B,) (None: 1; map points in SLAM units
+    pass the run's s).  xyz = p(t) + R(q(t)) (scale (R(ext_q) x + ext_t)) with the pose of query_poses_ragged.  zone / south (B,) int32
+    given: lonlatalt = utm_to_wgs84_ragged(xyz, pt_offsets, zone, south, run_status).  Returns a GeorefPoints."""
+    B, P, M = _query_args("georef_points_ragged", ts, pos, quat, offsets, pt_t, pt_offsets, pose_flags, run_status)
+    _chk(pt_xyz, torch.float64, (M, 3), "pt_xyz")
+    if ext_q is not None:
+        _chk(ext_q, torch.float64, (B, 4), "ext_q")
+    if ext_t is not None:
+        _chk(ext_t, torch.float64, (B, 3), "ext_t")
+    if scale is not None:
+        _chk(scale, torch.float64, (B,), "scale")
+    if (zone is None) != (south is None):
+        raise ValueError("georef_points_ragged: zone and south go together")
+    xyz = torch.empty((M, 3), dtype=torch.float64, device=ts.device)
+    flags, index, pf, state = _query_outputs(B, M, ts.device, pose_flags is not None)
+    if M == 0:                                                           # the entry does nothing without points: no track_state either
+        return GeorefPoints(xyz, xyz.clone() if zone is not None else None, flags, index, pf, None, pt_offsets)
+    ts_, pos_, quat_ = _unread_rows(ts, pos, quat)
+    check(_lib.load().gsf_georef_points_dev(context().handle, _p(ts_), _p(pos_), _p(quat_), _p(offsets), _p(run_status), _p(pose_flags), B, _p(pt_t),
+                                            _p(pt_offsets), M, float(max_gap), _p(pt_xyz), _p(ext_q), _p(ext_t), _p(scale), _p(xyz), _p(flags),
+                                            _p(index), _p(pf), _p(state)))
+    lla = utm_to_wgs84_ragged(xyz, pt_offsets, zone, south, run_status) if zone is not None else None
+    return GeorefPoints(xyz, lla, flags, index, pf, state, pt_offsets)
+
+
+def _fused_pose_flags(r):
+    cov = getattr(r, "cov", None)
+    return cov.flags if cov is not None else None
+
+
+def query_fused(rb, r, q_t, q_offsets, max_gap=0.0):
+    """query_poses_ragged on a run_fusion_ragged result: rb.ts, r.fused.pos / .quat, rb.slam_offsets, r.run_status, and r.cov.flags when the
+    run carries them (want_cov=True)."""
+    return query_poses_ragged(rb.ts, r.fused.pos, r.fused.quat, rb.slam_offsets, q_t, q_offsets, pose_flags=_fused_pose_flags(r),
+                              run_status=r.run_status, max_gap=max_gap)
+
+
+def georef_fused(rb, r, pt_t, pt_xyz, pt_offsets, ext_q=None, ext_t=None, scale=None, max_gap=0.0, wgs84=False):
+    """georef_points_ragged on a run_fusion_ragged result (see query_fused).  wgs84=True: lonlatalt through the run's projector (r.zone /
+    r.south); a projected=True run has none and raises ValueError."""
+    if wgs84 and (getattr(r, "zone", None) is None or getattr(r, "south", None) is None):
+        raise ValueError("georef_fused: wgs84=True needs the run's projector, and a projected=True run has none (ref :1096)")
+    return georef_points_ragged(rb.ts, r.fused.pos, r.fused.quat, rb.slam_offsets, pt_t, pt_xyz, pt_offsets, ext_q=ext_q, ext_t=ext_t, scale=scale,
+                                pose_flags=_fused_pose_flags(r), run_status=r.run_status, max_gap=max_gap,
+                                zone=r.zone if wgs84 else None, south=r.south if wgs84 else None)

@@ -725,4 +725,55 @@ int gsf_ransac_poly_batch(gsf_ctx* ctx, const double* t, const double* y, const 
     ST_RUN(gsf_ransac_poly_batch_dev(ctx, dt, dy, doff, P, didx, max_trials, min_samples, degree, residual_threshold, stop_probability, dmask, dnt, dni, dst_));
 }
 
+// the fused track at M query stamps, host arrays (the outputs that are NULL are neither staged nor computed)
+int gsf_pose_query(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const int64_t* offsets, const int32_t* run_status,
+                   const uint8_t* pose_flags, int64_t B, const double* q_t, const int64_t* q_offsets, int64_t M, double max_gap, double* out_pos,
+                   double* out_quat, uint8_t* q_flags, int32_t* q_index, uint8_t* q_pose_flags, int32_t* track_state)
+{
+    GSF_REQUIRE(ctx && B >= 0 && M >= 0, "bad arguments");
+    if (B == 0 || M == 0) return GSF_OK;
+    GSF_REQUIRE(offsets && q_t && q_offsets && out_pos && out_quat && q_flags && track_state, "NULL array");
+    const int64_t total = offsets[B];
+    GSF_REQUIRE(total >= 0 && (total == 0 || (ts && pos && quat)), "bad offsets / NULL arrays");
+    const size_t P = total > 0 ? (size_t)total : 1, Mq = (size_t)M;      // (no poses at all: one unread row stands in for the arrays)
+    const double zero_row[8] = { 0.0 };
+    ST_BEGIN(P * 65 + Mq * 78 + (size_t)(B + 1) * 16 + (size_t)B * 8 + 64, 14);
+    const double* dts = st.in(total > 0 ? ts : zero_row, P); const double* dpos = st.in(total > 0 ? pos : zero_row, P * 3);
+    const double* dquat = st.in(total > 0 ? quat : zero_row, P * 4); const int64_t* doff = st.in(offsets, (size_t)B + 1);
+    const int32_t* drs = run_status ? st.in(run_status, (size_t)B) : nullptr;
+    const uint8_t* dpf = (pose_flags && total > 0) ? st.in(pose_flags, P) : nullptr;
+    const double* dqt = st.in(q_t, Mq); const int64_t* dqo = st.in(q_offsets, (size_t)B + 1);
+    double* dop = st.out(out_pos, Mq * 3); double* doq = st.out(out_quat, Mq * 4); uint8_t* dfl = st.out(q_flags, Mq);
+    int32_t* dqi = q_index ? st.out(q_index, Mq) : nullptr; uint8_t* dqp = q_pose_flags ? st.out(q_pose_flags, Mq) : nullptr;
+    int32_t* dst_ = st.out(track_state, (size_t)B);
+    ST_RUN(gsf_pose_query_dev(ctx, dts, dpos, dquat, doff, drs, dpf, B, dqt, dqo, M, max_gap, dop, doq, dfl, dqi, dqp, dst_));
+}
+
+// sensor points carried into the fused track's frame, host arrays
+int gsf_georef_points(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const int64_t* offsets, const int32_t* run_status,
+                      const uint8_t* pose_flags, int64_t B, const double* q_t, const int64_t* q_offsets, int64_t M, double max_gap, const double* x,
+                      const double* ext_q, const double* ext_t, const double* scale, double* out_xyz, uint8_t* q_flags, int32_t* q_index,
+                      uint8_t* q_pose_flags, int32_t* track_state)
+{
+    GSF_REQUIRE(ctx && B >= 0 && M >= 0, "bad arguments");
+    if (B == 0 || M == 0) return GSF_OK;
+    GSF_REQUIRE(offsets && q_t && q_offsets && x && out_xyz && q_flags && track_state, "NULL array");
+    const int64_t total = offsets[B];
+    GSF_REQUIRE(total >= 0 && (total == 0 || (ts && pos && quat)), "bad offsets / NULL arrays");
+    const size_t P = total > 0 ? (size_t)total : 1, Mq = (size_t)M;
+    const double zero_row[8] = { 0.0 };
+    ST_BEGIN(P * 65 + Mq * 70 + (size_t)(B + 1) * 16 + (size_t)B * 72 + 64, 17);
+    const double* dts = st.in(total > 0 ? ts : zero_row, P); const double* dpos = st.in(total > 0 ? pos : zero_row, P * 3);
+    const double* dquat = st.in(total > 0 ? quat : zero_row, P * 4); const int64_t* doff = st.in(offsets, (size_t)B + 1);
+    const int32_t* drs = run_status ? st.in(run_status, (size_t)B) : nullptr;
+    const uint8_t* dpf = (pose_flags && total > 0) ? st.in(pose_flags, P) : nullptr;
+    const double* dqt = st.in(q_t, Mq); const int64_t* dqo = st.in(q_offsets, (size_t)B + 1); const double* dx = st.in(x, Mq * 3);
+    const double* deq = ext_q ? st.in(ext_q, (size_t)B * 4) : nullptr; const double* det = ext_t ? st.in(ext_t, (size_t)B * 3) : nullptr;
+    const double* dsc = scale ? st.in(scale, (size_t)B) : nullptr;
+    double* dxyz = st.out(out_xyz, Mq * 3); uint8_t* dfl = st.out(q_flags, Mq);
+    int32_t* dqi = q_index ? st.out(q_index, Mq) : nullptr; uint8_t* dqp = q_pose_flags ? st.out(q_pose_flags, Mq) : nullptr;
+    int32_t* dst_ = st.out(track_state, (size_t)B);
+    ST_RUN(gsf_georef_points_dev(ctx, dts, dpos, dquat, doff, drs, dpf, B, dqt, dqo, M, max_gap, dx, deq, det, dsc, dxyz, dfl, dqi, dqp, dst_));
+}
+
 }  // extern "C"

@@ -524,6 +524,45 @@ def ekf_cov_aligned(timestamps, quaternions, aligned_gps, valid_mask, global_con
     return filt, cov, flags, int(st[0])
 
 
+def _track_and_queries(timestamps, positions, quaternions, query_times):
+    ts, qt = f64(timestamps).ravel(), f64(query_times).ravel()
+    n, m = ts.size, qt.size
+    return ts, f64(positions, (n, 3)), f64(quaternions, (n, 4)), qt, np.array([0, n], dtype=np.int64), np.array([0, m], dtype=np.int64), n, m
+
+
+def interpolate_trajectory(timestamps, positions, quaternions, query_times, max_gap=None):
+    """One track at any stamps (gsf_pose_query, host arrays): -> (positions (m,3), quaternions (m,4), flags (m,) uint8 of GSF_Q_* bits).  The
+    position is interpolated linearly, the orientation by quaternion_nlerp (ref :94-105); a query on a pose's stamp returns that pose bit for
+    bit (GSF_Q_EXACT); outside the track, across a bracket wider than max_gap and on a track whose stamps are not ascending the rows are NaN
+    and flags says why.  query_times need not be sorted."""
+    ts, pos, quat, qt, off, qoff, n, m = _track_and_queries(timestamps, positions, quaternions, query_times)
+    po, qo, fl, st = np.empty((m, 3)), np.empty((m, 4)), np.empty((m,), dtype=np.uint8), np.zeros(1, dtype=np.int32)
+    if m == 0:
+        return po, qo, fl
+    check(_lib.load().gsf_pose_query(_ctx().handle, hptr(ts), hptr(pos), hptr(quat), hptr(off), None, None, 1, hptr(qt), hptr(qoff), m,
+                                     float(max_gap or 0.0), hptr(po), hptr(qo), hptr(fl), None, None, hptr(st)))
+    return po, qo, fl
+
+
+def georeference_points(timestamps, positions, quaternions, point_times, points, ext_quat=None, ext_trans=None, scale=1.0, max_gap=None):
+    """Sensor-frame points stamped by point_times into the track's frame (gsf_georef_points, host arrays): -> (xyz (m,3), flags (m,) uint8).
+    xyz = p(t) + R(q(t)) (scale (R(ext_quat) x + ext_trans)) with the pose of interpolate_trajectory; ext_quat / ext_trans = sensor -> body
+    (None: identity / zero).  An ext_quat that cannot be normalised raises ValueError, as Rotation.from_quat does."""
+    ts, pos, quat, qt, off, qoff, n, m = _track_and_queries(timestamps, positions, quaternions, point_times)
+    x = f64(points, (m, 3))
+    eq = None if ext_quat is None else f64(ext_quat, (1, 4))
+    et = None if ext_trans is None else f64(ext_trans, (1, 3))
+    sc = np.array([float(scale)])
+    xyz, fl, st = np.empty((m, 3)), np.empty((m,), dtype=np.uint8), np.zeros(1, dtype=np.int32)
+    if m == 0:
+        return xyz, fl
+    check(_lib.load().gsf_georef_points(_ctx().handle, hptr(ts), hptr(pos), hptr(quat), hptr(off), None, None, 1, hptr(qt), hptr(qoff), m,
+                                        float(max_gap or 0.0), hptr(x), hptr(eq), hptr(et), hptr(sc), hptr(xyz), hptr(fl), None, None, hptr(st)))
+    if int(st[0]) & _lib.QT_BAD_EXTRINSIC:
+        raise ValueError("georeference_points: ext_quat has zero, NaN or infinite norm")
+    return xyz, fl
+
+
 # ---------------------------------------------------------------------------- helpers of the EKF surface (EKFGPSSLAM.py:77-105, :679-826)
 def calculate_relative_pose(pose1_pos, pose1_quat, pose2_pos, pose2_quat):
     """Relative motion pose1 -> pose2 in pose1's frame: (delta_pos_local (3,), delta_quat (4,)); an invalid (zero-norm)

@@ -567,6 +567,67 @@ GSF_API int gsf_ekf_cov_ragged(gsf_ctx *ctx, const double *ts, const double *qua
                                const int64_t *offsets, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
                                double *cov_filt, double *cov_out, uint8_t *pose_flags, int32_t *status);
 
+/* ---- pose queries: the fused track at any stamp, sensor points into the track's frame ----------------------------------------------------
+   The fused track exists at the SLAM stamps; LiDAR returns, other exposures, map points and a second receiver have stamps of their own.
+   These entries evaluate the track between its poses with the rule the filter itself uses for orientations (quaternion_nlerp,
+   EKFGPSSLAM.py:94-105) and, for points, carry a sensor-frame point through its extrinsics and the interpolated pose.
+   Tracks are given as the ragged entries give them: ts[P], pos[P][3], quat[P][4], offsets int64[B+1].  Queries are ragged per track:
+   q_t[M], q_offsets int64[B+1] (query m belongs to track b with q_offsets[b] <= m < q_offsets[b+1]); they need not be sorted.  M is
+   passed by the host.  All indexing is int64.
+   Per track, track_state[B] (required output) holds GSF_QT_* bits; 0 = usable:
+   - GSF_QT_SKIPPED: run_status != NULL && run_status[b] != 0.  The track's rows are not read and no other bit is set.
+   - GSF_QT_EMPTY: the track has 0 poses.
+   - GSF_QT_UNSORTED: ts[0] is NaN, or !(ts[i] >= ts[i-1]) for some i inside the track (a NaN stamp counts).
+   - GSF_QT_BAD_EXTRINSIC (points entry only): ext_q[b] has a norm that is 0, NaN or infinite (Rotation.from_quat raises).
+   Per query tau of track b (n poses, stamps t[0..n-1]), q_flags[M] holds GSF_Q_* bits and the outputs are:
+   - track_state[b] != 0: NaN, GSF_Q_TRACK (also a query that q_offsets assigns to no track).
+   - tau is NaN: NaN, GSF_Q_NAN.   tau < t[0]: NaN, GSF_Q_BEFORE.   tau > t[n-1]: NaN, GSF_Q_AFTER.  There is no extrapolation.
+   - otherwise i = #{k : t[k] <= tau} - 1 = np.searchsorted(t, tau, side='right') - 1 (among equal stamps: the last one), and
+     - t[i] == tau: pose i copied bit for bit, GSF_Q_EXACT; pose i + 1 is not read, so a NaN neighbour cannot leak in;
+     - else j = i + 1 (it exists and t[j] > t[i]), gap = t[j] - t[i]:
+       - max_gap > 0 && gap > max_gap: NaN, GSF_Q_GAP (nobody interpolates across a tracking loss);
+       - else w = (tau - t[i]) / gap (two subtractions and one IEEE division), pos_c = fma(w, p_j,c - p_i,c, p_i,c),
+         quat = quaternion_nlerp(q_i, q_j, w) (:94-105: sign flip on a negative dot product, clip of w, and q_i / q_j by w < 0.5 where the
+         blend's norm is below 1e-9); flags 0.
+   Optional outputs (may be NULL): q_index[M] = i relative to the track's first pose, -1 where the query has no bracket (GSF_Q_GAP keeps
+   its i); q_pose_flags[M] = pose_flags[i] | pose_flags[j] (exact hit: pose_flags[i]; no bracket: 0) when the GSF_POSE_* flags of
+   gsf_ekf_cov_ragged_dev are passed as pose_flags[P] (may be NULL): "was this point georeferenced through a dead-reckoned stretch".
+   A query's result does not depend on the other queries of the call, nor on their order.  B == 0 or M == 0: nothing is done, GSF_OK.
+   Two launches on the context's stream (track_state, then the queries); no workspace. */
+#define GSF_QT_EMPTY 1
+#define GSF_QT_UNSORTED 2
+#define GSF_QT_SKIPPED 4
+#define GSF_QT_BAD_EXTRINSIC 8
+#define GSF_Q_EXACT 1      /* the query hit a pose's stamp: that pose, bit for bit */
+#define GSF_Q_BEFORE 2
+#define GSF_Q_AFTER 4
+#define GSF_Q_GAP 8
+#define GSF_Q_NAN 16
+#define GSF_Q_TRACK 32
+#define GSF_Q_BAD_QUAT 64  /* points entry only: the pose's quaternion at tau cannot be normalised (norm 0, NaN or infinite): NaN row */
+/* Out: out_pos[M][3], out_quat[M][4] (the blend is normalised by quaternion_nlerp; an exact hit returns the stored quaternion as it is). */
+GSF_API int gsf_pose_query_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *offsets,
+                               const int32_t *run_status, const uint8_t *pose_flags, int64_t B, const double *q_t, const int64_t *q_offsets,
+                               int64_t M, double max_gap, double *out_pos, double *out_quat, uint8_t *q_flags, int32_t *q_index,
+                               uint8_t *q_pose_flags, int32_t *track_state);
+/* Points: x[M][3] in the sensor frame, stamped by q_t.  ext_q[B][4] / ext_t[B][3] = sensor -> body per track (NULL: identity / zero);
+   scale[B] (NULL: 1): map points in SLAM units pass the run's s, a metric sensor passes nothing.  With p(tau), q(tau) as above:
+     y = scale * (R(ext_q / |ext_q|) x + ext_t);   qh = q(tau) / |q(tau)| (fails: NaN row, GSF_Q_BAD_QUAT or'ed in);   out_xyz = p(tau) + R(qh) y.
+   R(.) x is Rotation.apply of the unit quaternion.  Rows without a pose (the NaN cases above) are NaN with the same flags. */
+GSF_API int gsf_georef_points_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *offsets,
+                                  const int32_t *run_status, const uint8_t *pose_flags, int64_t B, const double *q_t, const int64_t *q_offsets,
+                                  int64_t M, double max_gap, const double *x, const double *ext_q, const double *ext_t, const double *scale,
+                                  double *out_xyz, uint8_t *q_flags, int32_t *q_index, uint8_t *q_pose_flags, int32_t *track_state);
+/* the same with host arrays: staged upload, the two launches, download */
+GSF_API int gsf_pose_query(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *offsets,
+                           const int32_t *run_status, const uint8_t *pose_flags, int64_t B, const double *q_t, const int64_t *q_offsets,
+                           int64_t M, double max_gap, double *out_pos, double *out_quat, uint8_t *q_flags, int32_t *q_index,
+                           uint8_t *q_pose_flags, int32_t *track_state);
+GSF_API int gsf_georef_points(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *offsets,
+                              const int32_t *run_status, const uint8_t *pose_flags, int64_t B, const double *q_t, const int64_t *q_offsets,
+                              int64_t M, double max_gap, const double *x, const double *ext_q, const double *ext_t, const double *scale,
+                              double *out_xyz, uint8_t *q_flags, int32_t *q_index, uint8_t *q_pose_flags, int32_t *track_state);
+
 /* ---- step 7 of main_process_gui (EKFGPSSLAM.py:1085-1104): the corrected track as WGS84 rows and as the bytes of its TUM files ------------
    Rows are flat over P poses with offsets int64[B+1], as in gsf_run_fusion_ragged_dev; any offsets work (a dense batch: b * N). */
 /* Rows [E, N, alt] (pos[P][3]) -> rows [lon deg, lat deg, alt] (lonlatalt[P][3]): utm_to_wgs84(corrected_pos, projector) (:1097, :291-296),
