@@ -551,9 +551,9 @@ static int time_align_launch(gsf_ctx* ctx, const double* slam_t, const int64_t* 
     size_t lds = (size_t)max_gps_per_trajectory * 8 * sizeof(double);                // T + Y(3) + M(3) + W
     double* gscratch = nullptr;
     if (max_gps_per_trajectory > 2560) {                                             // does not fit 160 KB of LDS: stage in HBM scratch
-        int rc = ensure_scratch(ctx, lds * (size_t)B);
+        int rc = ensure_workspace(ctx, GSF_WS_KERNEL, lds * (size_t)B);
         if (rc) return rc;
-        gscratch = (double*)ctx->scratch; lds = 0;
+        gscratch = workspace<double>(ctx, GSF_WS_KERNEL); lds = 0;
     } else if (lds > 64 * 1024) {
         GSF_HIP(hipFuncSetAttribute((const void*)time_align_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
@@ -620,9 +620,9 @@ int gsf_clock_offset_search_dev(gsf_ctx* ctx, const double* ts, const double* po
         GSF_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
         slab_rows = (int64_t)(cus > 0 ? cus : 1) * 8;
         if (slab_rows > B * K) slab_rows = B * K;
-        int rc = ensure_scratch(ctx, lds * (size_t)slab_rows);
+        int rc = ensure_workspace(ctx, GSF_WS_KERNEL, lds * (size_t)slab_rows);
         if (rc) return rc;
-        gscratch = (double*)ctx->scratch; lds = 0;
+        gscratch = workspace<double>(ctx, GSF_WS_KERNEL); lds = 0;
     } else if (lds > 64 * 1024) {
         GSF_HIP(hipFuncSetAttribute((const void*)clock_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }

@@ -27,73 +27,23 @@ int fail_hip(hipError_t e, const char* what)
     return GSF_ERR_HIP;
 }
 
-int ensure_scratch(gsf_ctx* ctx, size_t bytes)
-{
-    if (ctx->scratch_bytes >= bytes) return GSF_OK;
-    if (ctx->scratch) {
-        GSF_HIP(hipStreamSynchronize(ctx->stream));
-        GSF_HIP(hipFree(ctx->scratch));
-        ctx->scratch = nullptr; ctx->scratch_bytes = 0;
-    }
-    GSF_HIP(hipMalloc(&ctx->scratch, bytes));
-    ctx->scratch_bytes = bytes;
-    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->scratch, ctx->scratch_bytes, (uint64_t)ctx->poison);
-    return GSF_OK;
-}
+// growth per slot: the kernel workspace is allocated at exactly the bytes asked for (hundreds of MB at the largest batches: headroom there
+// would be footprint), the others with a quarter on top so that slowly growing calls stop allocating
+static const bool WS_HEADROOM[GSF_WS_COUNT] = { /* KERNEL */ false, /* RNG */ true, /* K2B */ true, /* ROWS */ true, /* RUN */ true };
 
-int ensure_rng_scratch(gsf_ctx* ctx, size_t bytes)
+int ensure_workspace(gsf_ctx* ctx, int slot, size_t bytes)
 {
-    if (ctx->rng_scratch_bytes >= bytes) return GSF_OK;
-    if (ctx->rng_scratch) {
+    auto& w = ctx->ws[slot];
+    if (w.bytes >= bytes) return GSF_OK;
+    if (w.p) {
         GSF_HIP(hipStreamSynchronize(ctx->stream));
-        GSF_HIP(hipFree(ctx->rng_scratch));
-        ctx->rng_scratch = nullptr; ctx->rng_scratch_bytes = 0;
+        GSF_HIP(hipFree(w.p));
+        w.p = nullptr; w.bytes = 0;
     }
-    GSF_HIP(hipMalloc(&ctx->rng_scratch, bytes + bytes / 4));
-    ctx->rng_scratch_bytes = bytes + bytes / 4;
-    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->rng_scratch, ctx->rng_scratch_bytes, (uint64_t)ctx->poison);
-    return GSF_OK;
-}
-
-int ensure_k2b_scratch(gsf_ctx* ctx, size_t bytes)
-{
-    if (ctx->k2b_scratch_bytes >= bytes) return GSF_OK;
-    if (ctx->k2b_scratch) {
-        GSF_HIP(hipStreamSynchronize(ctx->stream));
-        GSF_HIP(hipFree(ctx->k2b_scratch));
-        ctx->k2b_scratch = nullptr; ctx->k2b_scratch_bytes = 0;
-    }
-    GSF_HIP(hipMalloc(&ctx->k2b_scratch, bytes + bytes / 4));
-    ctx->k2b_scratch_bytes = bytes + bytes / 4;
-    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->k2b_scratch, ctx->k2b_scratch_bytes, (uint64_t)ctx->poison);
-    return GSF_OK;
-}
-
-int ensure_run_scratch(gsf_ctx* ctx, size_t bytes)
-{
-    if (ctx->run_scratch_bytes >= bytes) return GSF_OK;
-    if (ctx->run_scratch) {
-        GSF_HIP(hipStreamSynchronize(ctx->stream));
-        GSF_HIP(hipFree(ctx->run_scratch));
-        ctx->run_scratch = nullptr; ctx->run_scratch_bytes = 0;
-    }
-    GSF_HIP(hipMalloc(&ctx->run_scratch, bytes + bytes / 4));
-    ctx->run_scratch_bytes = bytes + bytes / 4;
-    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->run_scratch, ctx->run_scratch_bytes, (uint64_t)ctx->poison);
-    return GSF_OK;
-}
-
-int ensure_rows_scratch(gsf_ctx* ctx, size_t bytes)
-{
-    if (ctx->rows_scratch_bytes >= bytes) return GSF_OK;
-    if (ctx->rows_scratch) {
-        GSF_HIP(hipStreamSynchronize(ctx->stream));
-        GSF_HIP(hipFree(ctx->rows_scratch));
-        ctx->rows_scratch = nullptr; ctx->rows_scratch_bytes = 0;
-    }
-    GSF_HIP(hipMalloc(&ctx->rows_scratch, bytes + bytes / 4));
-    ctx->rows_scratch_bytes = bytes + bytes / 4;
-    if (ctx->poison >= 0) return launch_fill_words(ctx, ctx->rows_scratch, ctx->rows_scratch_bytes, (uint64_t)ctx->poison);
+    const size_t want = WS_HEADROOM[slot] ? bytes + bytes / 4 : bytes;
+    GSF_HIP(hipMalloc(&w.p, want));
+    w.bytes = want;
+    if (ctx->poison >= 0) return launch_fill_words(ctx, w.p, w.bytes, (uint64_t)ctx->poison);
     return GSF_OK;
 }
 
@@ -239,13 +189,7 @@ static int create_common(int device_id, hipStream_t stream, bool owns, gsf_ctx**
     if (device_id < 0 || device_id >= n) { set_error("gsf_create: device %d out of range [0,%d)", device_id, n); return GSF_ERR_INVALID_ARG; }
     GSF_HIP(hipSetDevice(device_id));
     gsf_ctx* c = new gsf_ctx();
-    c->device = device_id; c->stream = stream; c->owns_stream = owns; c->scratch = nullptr; c->scratch_bytes = 0; c->stage = nullptr; c->stage_bytes = 0; c->pinned = nullptr; c->pinned_bytes = 0;
-    c->rng_scratch = nullptr; c->rng_scratch_bytes = 0; c->rows_scratch = nullptr; c->rows_scratch_bytes = 0; c->run_scratch = nullptr; c->run_scratch_bytes = 0; c->tape_draws = -1; c->small_scratch = nullptr; c->k2b_screen = 1; c->k2b_scratch = nullptr; c->k2b_scratch_bytes = 0;
-    c->ekf_variant = 0; c->synth_variant = 0; c->block_kernel = -1; c->duo_kernel = -1; c->lane_min_traj = 32768; c->poison = -1; c->tail_scan_stages = 1; c->early_variances = -1;
-    c->ransac_early_exit = 0; c->ransac_probe_trials = 64; c->prefilter_first_batch = 1; c->prefilter_speculate = 1; c->prefilter_miss_batch = 4;
-    // the fused chains fit the rows main_process_gui hands to its fit (ref :973-998) under the reference's CONFIG defaults (:34, :53, :37)
-    // unless the caller says otherwise (gsf_set_sim3_rows): a raw C caller of gsf_fuse_pipeline_* gets steps 3-5 as the reference runs them
-    c->fit_rows = gsf::FitRows{ 1, 4, 5.0, 180.0 };
+    c->device = device_id; c->stream = stream; c->owns_stream = owns;     // (everything else: the defaults of gsf_ctx)
     if (owns) {
         hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
         if (e != hipSuccess) { delete c; return fail_hip(e, "hipStreamCreateWithFlags"); }
@@ -275,12 +219,9 @@ void gsf_destroy(gsf_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->rng_scratch) (void)hipFree(ctx->rng_scratch);
-    if (ctx->rows_scratch) (void)hipFree(ctx->rows_scratch);
-    if (ctx->run_scratch) (void)hipFree(ctx->run_scratch);
+    for (auto& w : ctx->ws)
+        if (w.p) (void)hipFree(w.p);
     if (ctx->small_scratch) (void)hipFree(ctx->small_scratch);
-    if (ctx->k2b_scratch) (void)hipFree(ctx->k2b_scratch);
     if (ctx->stage) (void)hipFree(ctx->stage);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     (void)hipEventDestroy(ctx->ev0);
@@ -294,11 +235,8 @@ int gsf_trim(gsf_ctx* ctx)
     GSF_REQUIRE(ctx, "ctx is NULL");
     GSF_HIP(hipSetDevice(ctx->device));
     GSF_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->scratch) { GSF_HIP(hipFree(ctx->scratch)); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
-    if (ctx->rng_scratch) { GSF_HIP(hipFree(ctx->rng_scratch)); ctx->rng_scratch = nullptr; ctx->rng_scratch_bytes = 0; }
-    if (ctx->k2b_scratch) { GSF_HIP(hipFree(ctx->k2b_scratch)); ctx->k2b_scratch = nullptr; ctx->k2b_scratch_bytes = 0; }
-    if (ctx->rows_scratch) { GSF_HIP(hipFree(ctx->rows_scratch)); ctx->rows_scratch = nullptr; ctx->rows_scratch_bytes = 0; }
-    if (ctx->run_scratch) { GSF_HIP(hipFree(ctx->run_scratch)); ctx->run_scratch = nullptr; ctx->run_scratch_bytes = 0; }
+    for (auto& w : ctx->ws)                                              // (the 512-byte small_scratch stays)
+        if (w.p) { GSF_HIP(hipFree(w.p)); w.p = nullptr; w.bytes = 0; }
     if (ctx->stage) { GSF_HIP(hipFree(ctx->stage)); ctx->stage = nullptr; ctx->stage_bytes = 0; }
     if (ctx->pinned) { GSF_HIP(hipHostFree(ctx->pinned)); ctx->pinned = nullptr; ctx->pinned_bytes = 0; }
     return GSF_OK;
@@ -311,59 +249,41 @@ int gsf_synchronize(gsf_ctx* ctx)
     return GSF_OK;
 }
 
+// the integer options that are a field and an inclusive range (what each one does: at the field, gsf_internal.hpp)
+static const struct { const char* key; int gsf_ctx::*field; int64_t lo, hi; const char* message; } INT_OPTIONS[] = {
+    { "ekf_variant", &gsf_ctx::ekf_variant, INT64_MIN, INT64_MAX, "" },
+    { "synth_variant", &gsf_ctx::synth_variant, 0, 1, "synth_variant must be 0 (white SLAM noise) or 1 (random-walk drift, SURVEY 8d)" },
+    { "block_kernel", &gsf_ctx::block_kernel, -1, 1, "block_kernel must be -1 (automatic), 0 (never) or 1 (whenever it applies)" },
+    { "k2b_screen", &gsf_ctx::k2b_screen, 0, 1, "k2b_screen must be 1 (single-precision screen + exact re-check, default) or 0 (double throughout)" },
+    { "ransac_early_exit", &gsf_ctx::ransac_early_exit, 0, 1,
+      "ransac_early_exit must be 0 (every trajectory draws all max_trials: the generator ends where the reference leaves it) or 1 (a trajectory stops at the first "
+      "trial that counts every row: same R, t, s, mask and poses)" },
+    { "prefilter_speculate", &gsf_ctx::prefilter_speculate, 0, 1, "prefilter_speculate must be 0 or 1" },
+    { "prefilter_miss_batch", &gsf_ctx::prefilter_miss_batch, 1, 64, "prefilter_miss_batch must be in [1, 64]" },
+    { "prefilter_first_batch", &gsf_ctx::prefilter_first_batch, 1, 64, "prefilter_first_batch must be in [1, 64]" },
+    { "ransac_probe_trials", &gsf_ctx::ransac_probe_trials, 1, 1 << 20, "ransac_probe_trials must be in [1, 2^20]" },
+    { "duo_kernel", &gsf_ctx::duo_kernel, -1, 1, "duo_kernel must be -1 (automatic), 0 (one wave) or 1 (two-wave blocks)" },
+    { "early_variances", &gsf_ctx::early_variances, -1, 1,
+      "early_variances must be -1 (automatic), 0 (never) or 1 (always where the build applies); the results are the same bits" },
+    { "tail_scan_stages", &gsf_ctx::tail_scan_stages, 0, 1,
+      "tail_scan_stages must be 1 (the scans of a short last chunk run only the stages that reach its lanes, default) or 0 (always six stages); the results are the "
+      "same bits" },
+};
+
 int gsf_set_option(gsf_ctx* ctx, const char* key, int64_t value)
 {
     GSF_REQUIRE(ctx && key, "NULL argument");
-    if (strcmp(key, "ekf_variant") == 0) { ctx->ekf_variant = (int)value; return GSF_OK; }
-    if (strcmp(key, "synth_variant") == 0) {
-        if (value < 0 || value > 1) { set_error("gsf_set_option: synth_variant must be 0 (white SLAM noise) or 1 (random-walk drift, SURVEY 8d)"); return GSF_ERR_INVALID_ARG; }
-        ctx->synth_variant = (int)value; return GSF_OK;
+    for (const auto& o : INT_OPTIONS) {
+        if (strcmp(key, o.key) != 0) continue;
+        if (value < o.lo || value > o.hi) { set_error("gsf_set_option: %s", o.message); return GSF_ERR_INVALID_ARG; }
+        ctx->*o.field = (int)value;
+        return GSF_OK;
     }
-    if (strcmp(key, "block_kernel") == 0) {
-        if (value < -1 || value > 1) { set_error("gsf_set_option: block_kernel must be -1 (automatic), 0 (never) or 1 (whenever it applies)"); return GSF_ERR_INVALID_ARG; }
-        ctx->block_kernel = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "k2b_screen") == 0) {
-        if (value < 0 || value > 1) { set_error("gsf_set_option: k2b_screen must be 1 (single-precision screen + exact re-check, default) or 0 (double throughout)"); return GSF_ERR_INVALID_ARG; }
-        ctx->k2b_screen = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "tape_draws") == 0) {
+    if (strcmp(key, "tape_draws") == 0) {                                     // (not in the table: 1 is not a value)
         if (value < -1 || value > 2 || value == 1) { set_error("gsf_set_option: tape_draws must be -1 (automatic: a few streams are drawn chip-wide), 0 (always one wave per stream) or 2 (tests: a tape cut short, so that the one-wave kernel takes over)"); return GSF_ERR_INVALID_ARG; }
         ctx->tape_draws = (int)value; return GSF_OK;
     }
-    if (strcmp(key, "ransac_early_exit") == 0) {
-        if (value < 0 || value > 1) { set_error("gsf_set_option: ransac_early_exit must be 0 (every trajectory draws all max_trials: the generator ends where the reference leaves it) or 1 (a trajectory stops at the first trial that counts every row: same R, t, s, mask and poses)"); return GSF_ERR_INVALID_ARG; }
-        ctx->ransac_early_exit = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "prefilter_speculate") == 0) {
-        if (value != 0 && value != 1) { set_error("gsf_set_option: prefilter_speculate must be 0 or 1"); return GSF_ERR_INVALID_ARG; }
-        ctx->prefilter_speculate = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "prefilter_miss_batch") == 0) {
-        if (value < 1 || value > 64) { set_error("gsf_set_option: prefilter_miss_batch must be in [1, 64]"); return GSF_ERR_INVALID_ARG; }
-        ctx->prefilter_miss_batch = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "prefilter_first_batch") == 0) {
-        if (value < 1 || value > 64) { set_error("gsf_set_option: prefilter_first_batch must be in [1, 64]"); return GSF_ERR_INVALID_ARG; }
-        ctx->prefilter_first_batch = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "ransac_probe_trials") == 0) {
-        if (value < 1 || value > (1 << 20)) { set_error("gsf_set_option: ransac_probe_trials must be in [1, 2^20]"); return GSF_ERR_INVALID_ARG; }
-        ctx->ransac_probe_trials = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "duo_kernel") == 0) {
-        if (value < -1 || value > 1) { set_error("gsf_set_option: duo_kernel must be -1 (automatic), 0 (one wave) or 1 (two-wave blocks)"); return GSF_ERR_INVALID_ARG; }
-        ctx->duo_kernel = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "early_variances") == 0) {
-        if (value < -1 || value > 1) { set_error("gsf_set_option: early_variances must be -1 (automatic), 0 (never) or 1 (always where the build applies); the results are the same bits"); return GSF_ERR_INVALID_ARG; }
-        ctx->early_variances = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "tail_scan_stages") == 0) {
-        if (value != 0 && value != 1) { set_error("gsf_set_option: tail_scan_stages must be 1 (the scans of a short last chunk run only the stages that reach its lanes, default) or 0 (always six stages); the results are the same bits"); return GSF_ERR_INVALID_ARG; }
-        ctx->tail_scan_stages = (int)value; return GSF_OK;
-    }
-    if (strcmp(key, "lane_min_traj") == 0) {
+    if (strcmp(key, "lane_min_traj") == 0) {                                  // (64-bit, no upper bound)
         if (value < 0) { set_error("gsf_set_option: lane_min_traj must be >= 0"); return GSF_ERR_INVALID_ARG; }
         ctx->lane_min_traj = value; return GSF_OK;
     }
@@ -375,10 +295,12 @@ int gsf_set_option(gsf_ctx* ctx, const char* key, int64_t value)
         GSF_HIP(hipSetDevice(ctx->device));
         GSF_HIP(hipStreamSynchronize(ctx->stream));
         if (ctx->pinned) fill_words_host(ctx->pinned, ctx->pinned_bytes, (uint64_t)value);
-        void* const ws[7] = { ctx->scratch, ctx->rng_scratch, ctx->k2b_scratch, ctx->rows_scratch, ctx->run_scratch, ctx->stage, ctx->small_scratch };
-        const size_t nb[7] = { ctx->scratch_bytes, ctx->rng_scratch_bytes, ctx->k2b_scratch_bytes, ctx->rows_scratch_bytes, ctx->run_scratch_bytes, ctx->stage_bytes, 512 };
-        for (int k = 0; k < 7; ++k)
-            if (ws[k]) { const int rc = launch_fill_words(ctx, ws[k], nb[k], (uint64_t)value); if (rc != GSF_OK) return rc; }
+        for (auto& w : ctx->ws)
+            if (w.p) { const int rc = launch_fill_words(ctx, w.p, w.bytes, (uint64_t)value); if (rc != GSF_OK) return rc; }
+        void* const more[2] = { ctx->stage, ctx->small_scratch };
+        const size_t nb[2] = { ctx->stage_bytes, 512 };
+        for (int k = 0; k < 2; ++k)
+            if (more[k]) { const int rc = launch_fill_words(ctx, more[k], nb[k], (uint64_t)value); if (rc != GSF_OK) return rc; }
         return GSF_OK;
     }
     set_error("gsf_set_option: unknown key '%s'", key);

@@ -254,9 +254,9 @@ static int fuse_time_major_via_wave(gsf_ctx* ctx, bool pipeline, const double* t
                                     int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status)
 {
     const size_t P = (size_t)B * (size_t)N;
-    int rc = ensure_scratch(ctx, P * (18 * 8) + ((P + 7) & ~(size_t)7) + 64);
+    int rc = ensure_workspace(ctx, GSF_WS_KERNEL, P * (18 * 8) + ((P + 7) & ~(size_t)7) + 64);
     if (rc) return rc;
-    double* wts = (double*)ctx->scratch; double* wpos = wts + P; double* wquat = wpos + 3 * P; double* wgps = wquat + 4 * P;
+    double* wts = workspace<double>(ctx, GSF_WS_KERNEL); double* wpos = wts + P; double* wquat = wpos + 3 * P; double* wgps = wquat + 4 * P;
     double* wpo = wgps + 3 * P; double* wqo = wpo + 3 * P; uint8_t* wval = (uint8_t*)(wqo + 4 * P);
     // three launches: the five inputs in one transpose, the wave kernel, the two outputs in one transpose
     const void* isrc[5] = { ts, pos, quat, gps, valid }; void* idst[5] = { wts, wpos, wquat, wgps, wval };

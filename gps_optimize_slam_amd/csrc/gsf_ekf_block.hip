@@ -611,9 +611,9 @@ int launch_ekf_block(gsf_ctx* ctx, bool pipeline, const double* ts, const double
     const uint8_t* rowsel = nullptr; const int32_t* rows_status = nullptr;
     if (pipeline && ctx->fit_rows.mode != 0) {
         const size_t P = (size_t)B * (size_t)N, o_st = (P + 255) & ~(size_t)255, o_n = o_st + (((size_t)B * 4 + 255) & ~(size_t)255);
-        int rc = ensure_rows_scratch(ctx, o_n + (size_t)B * 4);
+        int rc = ensure_workspace(ctx, GSF_WS_ROWS, o_n + (size_t)B * 4);
         if (rc) return rc;
-        char* w = (char*)ctx->rows_scratch;
+        char* w = workspace(ctx, GSF_WS_ROWS);
         if ((rc = launch_sim3_rows(ctx, ts, gps, valid, nullptr, B, N, ctx->fit_rows, (uint8_t*)w, (int32_t*)(w + o_n), (int32_t*)(w + o_st)))) return rc;
         rowsel = (const uint8_t*)w; rows_status = (const int32_t*)(w + o_st);
     }

@@ -815,9 +815,9 @@ int gsf_ransac_poly_batch_dev(gsf_ctx* ctx, const double* t, const double* y, co
     if (max_trials > RP_MAX_TRIALS || min_samples > RP_MAX_SAMPLES || degree > RP_MAX_DEGREE) {
         // beyond the one-pass kernel: the wide kernel with its per-trial slab in the context's workspace
         const size_t slots = (size_t)P * (size_t)max_trials;
-        int rc = ensure_scratch(ctx, slots * 12 + 64);
+        int rc = ensure_workspace(ctx, GSF_WS_KERNEL, slots * 12 + 64);
         if (rc) return rc;
-        double* sc = (double*)ctx->scratch; int32_t* cn = (int32_t*)(sc + slots);
+        double* sc = workspace<double>(ctx, GSF_WS_KERNEL); int32_t* cn = (int32_t*)(sc + slots);
         hipLaunchKernelGGL(ransac_poly_wide_kernel, dim3((unsigned)P), dim3(RPW_THREADS), 0, ctx->stream, t, y, offsets, sample_idx, (int)max_trials,
                            (int)min_samples, (int)degree, residual_threshold, stop_probability, cn, sc, inlier_mask, n_trials, n_inliers, status);
         GSF_HIP(hipGetLastError());

@@ -7,46 +7,48 @@
 #include "../../include/gsf.h"
 #include "gsf_ekf_core.hpp"
 
+// The grow-only device workspaces of a context, one slot each.  They are separate allocations because a slot may grow (free + malloc) while a
+// caller further up the chain still holds pointers into another one; no two of them may be merged.
+enum gsf_ws_slot {
+    GSF_WS_KERNEL,   // kernel workspace (time-alignment slabs, the transposed copy of a small time-major batch, robust_chain's layout), sized exactly
+    GSF_WS_RNG,      // tape, transition tables and swap partners of the chip-wide draws (gsf_rng_tape.hip); separate from the kernel slot, whose
+                     // layout the caller of launch_mt_choice (robust_chain) may hold pointers into
+    GSF_WS_K2B,      // K2b's rows as floats (screened residual counts, gsf_sim3.hip); grows below robust_chain as well
+    GSF_WS_ROWS,     // row mask + flags of the Sim3 row choice for the kernels that take it as a pre-pass (gsf_ekf_block.hip); below robust_chain too
+    GSF_WS_RUN,      // temporaries of the whole-run chain (gsf_run.hip), which holds pointers into it while its stages grow the kernel slot
+    GSF_WS_COUNT
+};
+
 struct gsf_ctx {
-    int device;
-    hipStream_t stream;
-    bool owns_stream;
-    hipEvent_t ev0, ev1;
-    // kernel workspace (time-alignment slabs, the transposed copy of a small time-major batch), grown on demand
-    void* scratch;
-    size_t scratch_bytes;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool owns_stream = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct { void* p = nullptr; size_t bytes = 0; } ws[GSF_WS_COUNT];   // gsf::ensure_workspace / gsf::workspace
     // staging of the host-pointer entry points: one grow-only device arena + a pinned host mirror (see gsf::Staging)
-    void* stage;
-    size_t stage_bytes;
-    void* pinned;
-    size_t pinned_bytes;
-    // tape, transition tables and swap partners of the chip-wide draws (gsf_rng_tape.hip); separate from `scratch`, whose layout the caller of
-    // launch_mt_choice may hold pointers into
-    void* small_scratch;   // 512 B: arg-max keys of the split K2b launch (gsf_sim3.hip: up to 32 sets x 16 B)
-    void* k2b_scratch;     // K2b's rows as floats (screened residual counts, gsf_sim3.hip), grow-only
-    size_t k2b_scratch_bytes;
-    void* rng_scratch;
-    size_t rng_scratch_bytes;
-    void* run_scratch;     // temporaries of gsf_run_fusion_batch_dev (its stages use `scratch` themselves), grow-only
-    size_t run_scratch_bytes;
-    void* rows_scratch;    // row mask + flags of the Sim3 row choice for the kernels that take it as a pre-pass (gsf_ekf_block.hip), grow-only
-    size_t rows_scratch_bytes;
-    int k2b_screen;        // K2b residual counts screened in packed single precision, exact re-check in the band (gsf_set_option "k2b_screen"): 1 default, 0 all double
-    int tape_draws;        // chip-wide draws for a few streams (gsf_set_option "tape_draws"): -1 automatic, 0 never, 2 tests (tape cut short)
-    int ekf_variant;       // reserved tuning knob (gsf_set_option "ekf_variant"); 0 = default
-    int synth_variant;     // synthetic workload (gsf_set_option "synth_variant"): 0 = white SLAM noise (default), 1 = SURVEY 8d's random-walk drift
-    int block_kernel;      // workgroup-per-trajectory kernel for 64 < N <= 1024 (gsf_set_option "block_kernel"): -1 automatic, 0 never, 1 always
-    int ransac_early_exit; // robust chain: stop a trajectory's trials at the first one that counts every row (gsf_set_option "ransac_early_exit"): 0 default, 1 on
-    int prefilter_miss_batch; // ... and the largest batch the sequential walk opens with after the speculative pass has missed (gsf_set_option "prefilter_miss_batch")
-    int prefilter_speculate;  // the pre-filter chain tries "every axis of the window stops after its first trial" first (gsf_set_option "prefilter_speculate")
-    int prefilter_first_batch; // trials the pre-filter chain draws and scores before its first look at scikit-learn's stopping rule (gsf_set_option "prefilter_first_batch")
-    int ransac_probe_trials; // ... trials the early-exit probe draws and scores itself before the wide kernels take the rest (gsf_set_option "ransac_probe_trials")
-    int duo_kernel;        // two-wave pipeline kernel for small batches (gsf_set_option "duo_kernel"): -1 automatic, 0 never, 1 always
-    int early_variances;   // one-wave pipeline build for short tracks with the first chunk's variances computed under the input burst (gsf_set_option "early_variances"): -1 automatic, 0 never, 1 always where it applies (same bits)
-    int tail_scan_stages;  // wave kernels: scans of a short last chunk sized by its last active lane (gsf_set_option "tail_scan_stages"): 1 default, 0 always six stages (same bits)
-    gsf::FitRows fit_rows; // rows of the fused chains' Sim3 fit (gsf_set_sim3_rows); mode 0 = all valid rows
-    int64_t poison;        // tests: every workspace is filled with this 64-bit word when the option is set and after it grows (gsf_set_option "poison_workspaces"); -1 = off
-    int64_t lane_min_traj; // time-major batches with fewer trajectories are transposed and run by the wave kernel (gsf_set_option "lane_min_traj")
+    void* stage = nullptr;
+    size_t stage_bytes = 0;
+    void* pinned = nullptr;
+    size_t pinned_bytes = 0;
+    void* small_scratch = nullptr;   // 512 B: arg-max keys of the split K2b launch (gsf_sim3.hip: up to 32 sets x 16 B)
+    int k2b_screen = 1;        // K2b residual counts screened in packed single precision, exact re-check in the band (gsf_set_option "k2b_screen"): 1 default, 0 all double
+    int tape_draws = -1;       // chip-wide draws for a few streams (gsf_set_option "tape_draws"): -1 automatic, 0 never, 2 tests (tape cut short)
+    int ekf_variant = 0;       // reserved tuning knob (gsf_set_option "ekf_variant"); 0 = default
+    int synth_variant = 0;     // synthetic workload (gsf_set_option "synth_variant"): 0 = white SLAM noise (default), 1 = SURVEY 8d's random-walk drift
+    int block_kernel = -1;     // workgroup-per-trajectory kernel for 64 < N <= 1024 (gsf_set_option "block_kernel"): -1 automatic, 0 never, 1 always
+    int ransac_early_exit = 0; // robust chain: stop a trajectory's trials at the first one that counts every row (gsf_set_option "ransac_early_exit"): 0 default, 1 on
+    int prefilter_miss_batch = 4; // ... and the largest batch the sequential walk opens with after the speculative pass has missed (gsf_set_option "prefilter_miss_batch")
+    int prefilter_speculate = 1;  // the pre-filter chain tries "every axis of the window stops after its first trial" first (gsf_set_option "prefilter_speculate")
+    int prefilter_first_batch = 1; // trials the pre-filter chain draws and scores before its first look at scikit-learn's stopping rule (gsf_set_option "prefilter_first_batch")
+    int ransac_probe_trials = 64; // ... trials the early-exit probe draws and scores itself before the wide kernels take the rest (gsf_set_option "ransac_probe_trials")
+    int duo_kernel = -1;       // two-wave pipeline kernel for small batches (gsf_set_option "duo_kernel"): -1 automatic, 0 never, 1 always
+    int early_variances = -1;  // one-wave pipeline build for short tracks with the first chunk's variances computed under the input burst (gsf_set_option "early_variances"): -1 automatic, 0 never, 1 always where it applies (same bits)
+    int tail_scan_stages = 1;  // wave kernels: scans of a short last chunk sized by its last active lane (gsf_set_option "tail_scan_stages"): 1 default, 0 always six stages (same bits)
+    // rows of the fused chains' Sim3 fit (gsf_set_sim3_rows); mode 0 = all valid rows.  Default: the rows main_process_gui hands to its fit
+    // (ref :973-998) under the reference's CONFIG defaults (:34, :53, :37), so a raw C caller of gsf_fuse_pipeline_* gets steps 3-5 as the reference runs them
+    gsf::FitRows fit_rows{ 1, 4, 5.0, 180.0 };
+    int64_t poison = -1;       // tests: every workspace is filled with this 64-bit word when the option is set and after it grows (gsf_set_option "poison_workspaces"); -1 = off
+    int64_t lane_min_traj = 32768; // time-major batches with fewer trajectories are transposed and run by the wave kernel (gsf_set_option "lane_min_traj")
 };
 
 namespace gsf {
@@ -89,11 +91,9 @@ const char* wave_big_build_info();
 const char* wave_block_build_info();
 const char* wave_early_build_info();
 
-int ensure_scratch(gsf_ctx* ctx, size_t bytes);
-int ensure_rng_scratch(gsf_ctx* ctx, size_t bytes);
-int ensure_k2b_scratch(gsf_ctx* ctx, size_t bytes);
-int ensure_rows_scratch(gsf_ctx* ctx, size_t bytes);
-int ensure_run_scratch(gsf_ctx* ctx, size_t bytes);
+// slot `slot` (gsf_ws_slot) holds at least `bytes` afterwards; a regrowth synchronises the stream, frees the old block and invalidates pointers into it
+int ensure_workspace(gsf_ctx* ctx, int slot, size_t bytes);
+template <class T = char> inline T* workspace(const gsf_ctx* ctx, int slot) { return (T*)ctx->ws[slot].p; }
 // `bytes` at p (device memory, 8-byte aligned) <- the 64-bit word repeated, on the context's stream (gsf_util.hip)
 int launch_fill_words(gsf_ctx* ctx, void* p, size_t bytes, uint64_t word);
 

@@ -427,9 +427,9 @@ int launch_mt_tape(gsf_ctx* ctx, uint32_t* state, const int32_t* counts, int64_t
 {
     TapePlan pl;
     if (!tape_plan(B, trials, k, n_max, ctx->tape_draws == 2, pl)) { set_error("launch_mt_tape: out of range"); return GSF_ERR_INVALID_ARG; }
-    int rc = ensure_rng_scratch(ctx, pl.bytes);
+    int rc = ensure_workspace(ctx, GSF_WS_RNG, pl.bytes);
     if (rc) return rc;
-    char* w = (char*)ctx->rng_scratch;
+    char* w = workspace(ctx, GSF_WS_RNG);
     TapeHdr* hdr = (TapeHdr*)(w + pl.o_hdr);
     uint32_t* tape = (uint32_t*)(w + pl.o_tape);
     uint16_t* jseq = (uint16_t*)(w + pl.o_jseq);

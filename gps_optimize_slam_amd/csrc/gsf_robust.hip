@@ -428,9 +428,9 @@ int robust_chain(gsf_ctx* ctx, const double* ts, const double* pos, const double
                  o_idx = take(nb * (size_t)max_trials * (size_t)min_samples * 4 + 4), o_fit = take(nb * 4), o_fail = take(nb * 4), o_ip = take(nb * 24),
                  o_iq = take(nb * 32), o_sel = take(P), o_rst = take(nb * 4), o_rn = take(nb * 4), o_key = take(nb * 16), o_dec = take(nb * 4),
                  o_pinfo = take(nb * 8);
-    int rc = ensure_scratch(ctx, off);
+    int rc = ensure_workspace(ctx, GSF_WS_KERNEL, off);
     if (rc) return rc;
-    char* w = (char*)ctx->scratch;
+    char* w = workspace(ctx, GSF_WS_KERNEL);
     double* src = (double*)(w + o_src); double* dst = (double*)(w + o_dst); int32_t* rowmap = (int32_t*)(w + o_map); uint8_t* mask_c = (uint8_t*)(w + o_mask);
     int32_t* counts = (int32_t*)(w + o_cnt); int64_t* cofs = (int64_t*)(w + o_off); int32_t* idx = (int32_t*)(w + o_idx);
     int32_t* fit = (int32_t*)(w + o_fit); int32_t* fail = (int32_t*)(w + o_fail); double* ip = (double*)(w + o_ip); double* iq = (double*)(w + o_iq);

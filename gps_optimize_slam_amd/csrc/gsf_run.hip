@@ -143,7 +143,217 @@ __global__ __launch_bounds__(64) void run_outcome_kernel(int64_t B, int64_t N, c
     }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+// ---------------------------------------------------------------------------------------------------------------- the chain, host side
+// one GNSS log per track (the primary logs, or the ground truth): inputs, then what step 1 leaves behind.  NULL means what it means in include/gsf.h
+struct RunLog {
+    const double* t; const double* llh /* NULL: utm holds the projected rows already */; const int64_t* offsets; int64_t total; int32_t max_fixes;
+    const gsf_prefilter_config* filter; int32_t* zone; int32_t* south; double* utm; uint8_t* keep;
+};
+
+// every pointer and size of a run: what the two device entries fill in from their arguments (device pointers) and the two host entries from
+// theirs (host pointers, staged by run_staged).  NULL means what it means in include/gsf.h
+struct RunIO {
+    const double* ts; const double* pos; const double* quat;
+    const int64_t* slam_offsets;     // NULL: the dense entry, B tracks of N poses each
+    int64_t B, N, total_poses;       // N: poses per track (dense) / the longest track (ragged); total_poses: rows of ts, pos, quat
+    RunLog gps, gt;                  // gt.offsets == NULL: no ground-truth leg (the dense entry has none)
+    const gsf_run_config* cfg; uint32_t* mt_state;
+    double* R; double* t; double* s; double* pos_out; double* quat_out; int32_t* status; int32_t* n_inliers; double* aligned; uint8_t* valid;
+    double* sim3_pos; double* gt_aligned; uint8_t* gt_valid;
+    double* err_stats;               // dense: [3][B][4]; ragged: [2][3][B][4], the second block against the ground truth
+    int32_t* plot_ref; int32_t* run_status; uint8_t* inlier_mask; int32_t* trial_info;
+};
+
+// temporaries of the chain in the run workspace (byte offsets, 256-byte aligned); used by run_chain and by nothing else
+struct RunLayout {
+    struct Log { size_t ct, cp, map, ck, cnt, ls, fut; } gps, gt;             // per log: compacted stamps / rows, row map, keep marks, counts, status, filtered rows
+    size_t li, so, as, sp, sq, bq, err, grs, bytes;
+};
+
+RunLayout run_layout(const RunIO& io)
+{
+    const bool ragged = io.slam_offsets != nullptr;
+    const size_t nb = (size_t)io.B, P = (size_t)io.total_poses;
+    RunLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
+    auto log = [&](RunLayout::Log& l, size_t T, size_t per_track) {
+        l.ct = take(T * 8); l.cp = take(T * 24); l.map = take(T * 4); l.ck = take(T); l.cnt = take(per_track); l.ls = take(per_track); l.fut = take(T * 24);
+    };
+    log(L.gps, (size_t)(io.gps.total > 0 ? io.gps.total : 1), nb * 4);
+    L.li = take(nb * 8);
+    L.so = take(ragged ? 0 : (nb + 1) * 8);                                      // the dense entry's fixed-stride offsets
+    L.as = take(nb * 4);
+    L.sp = take(io.sim3_pos ? 0 : P * 24); L.sq = take(P * 32); L.bq = take(nb * 4); L.err = take(P * 24);
+    log(L.gt, io.gt.offsets ? (size_t)(io.gt.total > 0 ? io.gt.total : 1) : 0, ragged ? nb * 4 : 0);
+    L.grs = take(ragged ? nb * 4 : 0);
+    L.bytes = off;
+    return L;
+}
+
+// step 1 of one log (load_gps_data, ref :258-287): mask, zone, UTM; the loaded rows compacted; the pre-filter -- the next draws of each track's
+// generator --; the filtered log w.fut and its flags rs.  gate (may be NULL): tracks with gate[b] != 0 count no fix and draw nothing.
+// slam_off / badq (may be NULL) and N: the two chores run_filtered_rows_kernel carries for the later steps
+int load_log(gsf_ctx* ctx, const RunLog& g, char* ws, const RunLayout::Log& w, int32_t* log_info, int64_t B, uint32_t* mt_state, const int32_t* gate, int32_t* rs,
+             int64_t* slam_off, int32_t* badq, int64_t N)
+{
+    double* ct = (double*)(ws + w.ct); double* cp = (double*)(ws + w.cp); int32_t* rowmap = (int32_t*)(ws + w.map); uint8_t* ckeep = (uint8_t*)(ws + w.ck);
+    int32_t* counts = (int32_t*)(ws + w.cnt); int32_t* log_status = (int32_t*)(ws + w.ls); double* fut = (double*)(ws + w.fut);
+    int rc;
+    // (llh == NULL: the caller's utm rows are the projected log already)
+    if (g.llh && (rc = gsf_gps_rows_to_utm_batch_dev(ctx, g.llh, g.offsets, B, g.utm, g.zone, g.south))) return rc;
+    hipLaunchKernelGGL(run_compact_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, g.t, (const double*)g.utm, g.offsets, ct, cp, rowmap, counts, gate);
+    GSF_HIP(hipGetLastError());
+    if ((rc = launch_gps_prefilter_auto(ctx, ct, cp, g.offsets, counts, B, g.max_fixes > 0 ? g.max_fixes : 1, g.filter, mt_state, ckeep, log_status, log_info))) return rc;
+    hipLaunchKernelGGL(run_filtered_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const double*)g.utm, g.offsets, (const int32_t*)counts,
+                       (const int32_t*)rowmap, (const uint8_t*)ckeep, (const int32_t*)log_status, fut, g.keep, rs, slam_off, badq, B, N);
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
+}
+
+// the chain of both device entries; the arguments were checked by the entry.  What differs between the two is said where it differs.
+int run_chain(gsf_ctx* ctx, const RunIO& io)
+{
+    const bool ragged = io.slam_offsets != nullptr, gt = io.gt.offsets != nullptr;
+    const gsf_run_config* cfg = io.cfg;
+    const int64_t B = io.B, nmax = io.N > 0 ? io.N : 1;                          // (only a ragged batch can have N == 0: every track empty)
+    int rc;
+    // both pre-filters' configurations and log lengths before the first one draws: a failing call leaves every generator where it was
+    // (the dense entry used to meet this check inside launch_gps_prefilter_auto: the same code and message, now earlier)
+    if ((rc = check_gps_prefilter(io.gps.filter, io.gps.max_fixes > 0 ? io.gps.max_fixes : 1, B))) return rc;
+    if (gt && (rc = check_gps_prefilter(io.gt.filter, io.gt.max_fixes > 0 ? io.gt.max_fixes : 1, B))) return rc;
+    GSF_HIP(hipSetDevice(ctx->device));
+    const RunLayout L = run_layout(io);
+    if ((rc = ensure_workspace(ctx, GSF_WS_RUN, L.bytes))) return rc;
+    char* w = workspace(ctx, GSF_WS_RUN);
+    int32_t* log_info = (int32_t*)(w + L.li); int32_t* align_status = (int32_t*)(w + L.as);     // (both logs' launches reuse these two)
+    double* fut = (double*)(w + L.gps.fut); double* gfut = (double*)(w + L.gt.fut); int32_t* grs = (int32_t*)(w + L.grs);
+    double* sp = io.sim3_pos ? io.sim3_pos : (double*)(w + L.sp); double* sq = (double*)(w + L.sq); int32_t* badq = (int32_t*)(w + L.bq);
+    double* errs = (double*)(w + L.err);
+    // the tracks' row offsets for the alignment and step 4.  Dense: fixed-stride offsets written on the device by run_filtered_rows_kernel (which
+    // gets N for that); ragged: the caller's, and the kernel gets no array and N = 0
+    const int64_t* track_off = ragged ? io.slam_offsets : (const int64_t*)(w + L.so);
+    // ---- step 1, primary log (ref :961) -- the first draws of each track's generator
+    if ((rc = load_log(ctx, io.gps, w, L.gps, log_info, B, io.mt_state, nullptr, io.run_status, ragged ? nullptr : (int64_t*)(w + L.so), badq, ragged ? 0 : io.N))) return rc;
+    // ---- step 1, ground-truth log (ref :962-966): its own zone, its own pre-filter (CONFIG['ground_truth_gps_filtering']) -- the next draws, and
+    // none for a track whose primary log already stopped the run (gated to 0 fixes) or that has no ground truth (an empty range)
+    if (gt && (rc = load_log(ctx, io.gt, w, L.gt, log_info, B, io.mt_state, io.run_status, grs, nullptr, nullptr, 0))) return rc;
+    // ---- ragged only: the ground truth's outcome and the empty SLAM track (ref :964, :967); a dense batch has neither
+    if (ragged) {
+        hipLaunchKernelGGL(run_gt_status_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, io.slam_offsets, io.gps.offsets, io.gt.offsets, (const int32_t*)grs,
+                           io.run_status, fut);
+        GSF_HIP(hipGetLastError());
+    }
+    // ---- step 2
+    if ((rc = gsf_time_align_loaded_rows_batch_dev(ctx, io.ts, track_off, io.gps.t, fut, io.gps.offsets, B, io.gps.max_fixes > 2 ? io.gps.max_fixes : 2,
+                                                   cfg->max_gps_gap_threshold, io.aligned, io.valid, align_status))) return rc;
+    // ---- steps 3-5 on the rows main_process_gui picks (ref :973-998), whatever the context's own row rule is: restored on every path below.
+    // Dense passes offsets = NULL here and to step 6: that selects the equal-length kernel builds (sized tail scans, the workgroup kernel, early
+    // variances, the LDS metric kernel); the offsets in the workspace would give the same results, slower
+    const FitRows saved = ctx->fit_rows;
+    ctx->fit_rows = FitRows{ 1, cfg->sim3_min_samples, cfg->max_gps_gap_threshold, cfg->sim3_max_initial_duration };
+    rc = robust_chain(ctx, io.ts, io.pos, io.quat, io.aligned, io.valid, &cfg->ekf, B, nmax, io.slam_offsets, ragged ? io.total_poses : 0, cfg->sim3_min_samples,
+                      cfg->sim3_residual_threshold, cfg->sim3_max_trials, cfg->sim3_min_inliers_needed, io.mt_state, io.R, io.t, io.s, io.pos_out, io.quat_out,
+                      io.status, io.n_inliers, io.inlier_mask, io.trial_info);
+    ctx->fit_rows = saved;
+    if (rc) return rc;
+    // ---- step 4 for every pose, step 6 against the primary fixes and (ref :1035-1062) against the ground truth, aligned with the same values
+    if ((rc = launch_apply_sim3(ctx, io.pos, io.quat, track_off, B, io.R, io.t, io.s, sp, sq, badq, true))) return rc;
+    if ((rc = launch_eval_errors3(ctx, io.ts, io.pos, sp, io.pos_out, io.aligned, io.valid, B, nmax, cfg->eval_skip_seconds, io.err_stats, errs, io.slam_offsets,
+                                  ragged ? io.total_poses : 0))) return rc;
+    // err_stats: 12 doubles per track in the dense entry; 24 in the ragged one, whose second block the outcome kernel fills itself (count 0, NaN)
+    // when no ground-truth leg ran (gt_none)
+    double* err_gt = ragged ? io.err_stats + (size_t)B * 12 : nullptr;
+    if (gt) {
+        if ((rc = gsf_time_align_loaded_rows_batch_dev(ctx, io.ts, track_off, io.gt.t, gfut, io.gt.offsets, B, io.gt.max_fixes > 2 ? io.gt.max_fixes : 2,
+                                                       cfg->max_gps_gap_threshold, io.gt_aligned, io.gt_valid, align_status))) return rc;
+        if ((rc = launch_eval_errors3(ctx, io.ts, io.pos, sp, io.pos_out, io.gt_aligned, io.gt_valid, B, nmax, cfg->eval_skip_seconds, err_gt, errs, io.slam_offsets,
+                                      io.total_poses))) return rc;
+    }
+    hipLaunchKernelGGL(run_outcome_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, B, ragged ? (int64_t)0 : io.N, (const int32_t*)io.status, io.run_status, io.R,
+                       io.t, io.s, io.pos_out, io.quat_out, io.sim3_pos, io.err_stats, io.n_inliers, (const int32_t*)badq, io.slam_offsets, err_gt,
+                       (ragged && !gt) ? 1 : 0, io.plot_ref);
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
+}
+
+// the dense device entry on a RunIO: its argument checks (before the context is touched), then the chain
+int run_fusion_batch_dev(gsf_ctx* ctx, const RunIO& io)
+{
+    GSF_REQUIRE(ctx && io.cfg, "ctx/cfg is NULL");
+    GSF_REQUIRE(io.B >= 0 && io.N >= 0 && io.B <= 0x7fffffff && io.gps.total >= 0 && io.gps.max_fixes >= 0, "bad B, N, total_fixes or max_fixes");
+    if (io.B == 0 || io.N == 0) return GSF_OK;                                   // nothing written
+    GSF_REQUIRE(io.ts && io.pos && io.quat && io.gps.offsets && io.mt_state && io.R && io.t && io.s && io.pos_out && io.quat_out && io.status && io.n_inliers &&
+                io.aligned && io.valid && io.err_stats && io.run_status && (!io.gps.llh || (io.gps.zone && io.gps.south)), "NULL array");
+    GSF_REQUIRE(io.gps.total == 0 || (io.gps.t && io.gps.utm && io.gps.keep), "NULL GNSS array");
+    GSF_REQUIRE(io.N <= 28000, "N too large for the device-side draws (<= 28000 poses per trajectory)");
+    return run_chain(ctx, io);
+}
+
+// the ragged device entry on a RunIO.  Unlike the dense one it returns early only for B == 0: a batch whose tracks are all empty runs (SLAM_EMPTY)
+int run_fusion_ragged_dev(gsf_ctx* ctx, const RunIO& io)
+{
+    const RunLog& g = io.gt;
+    GSF_REQUIRE(ctx && io.cfg, "ctx/cfg is NULL");
+    GSF_REQUIRE(io.B >= 0 && io.B <= 0x7fffffff && io.total_poses >= 0 && io.N >= 0 && io.gps.total >= 0 && io.gps.max_fixes >= 0 && g.total >= 0 && g.max_fixes >= 0,
+                "bad B, total_poses, max_poses, total_fixes, max_fixes, gt_total or gt_max_fixes");
+    if (io.B == 0) return GSF_OK;                                                // nothing written
+    GSF_REQUIRE(io.N <= 28000, "a track is too long for the device-side draws (<= 28000 poses per trajectory)");
+    GSF_REQUIRE(io.slam_offsets && io.gps.offsets && io.mt_state && io.R && io.t && io.s && io.status && io.n_inliers && io.err_stats && io.run_status &&
+                (!io.gps.llh || (io.gps.zone && io.gps.south)), "NULL array");
+    GSF_REQUIRE(io.total_poses == 0 || (io.ts && io.pos && io.quat && io.pos_out && io.quat_out && io.aligned && io.valid), "NULL SLAM array");
+    GSF_REQUIRE(io.gps.total == 0 || (io.gps.t && io.gps.utm && io.gps.keep), "NULL GNSS array");
+    GSF_REQUIRE(!g.offsets || (g.filter && (!g.llh || (g.zone && g.south)) && (io.total_poses == 0 || (io.gt_aligned && io.gt_valid)) &&
+                               (g.total == 0 || (g.t && g.utm && g.keep))), "NULL ground-truth array");
+    return run_chain(ctx, io);
+}
+
+// the host-pointer entries: h holds host pointers (checked by the entry); one staged upload, `dev` on the device copies, one download.
+// The arena is sized from the list of arrays below, walked twice: once to add up the bytes, once to stage them
+int run_staged(gsf_ctx* ctx, const RunIO& h, int (*dev)(gsf_ctx*, const RunIO&))
+{
+    const bool ragged = h.slam_offsets != nullptr, gt = h.gt.offsets != nullptr;
+    const size_t nb = (size_t)h.B, P = (size_t)h.total_poses, T = (size_t)h.gps.total, Tg = (size_t)h.gt.total;
+    Staging* st = nullptr;
+    size_t bytes = 0; int n = 0;
+    auto in = [&](auto* host, size_t count, bool want = true) -> decltype(host) {
+        if (!want) return nullptr;
+        if (!st) { bytes += count * sizeof(*host); ++n; return nullptr; }
+        return st->in(host, count);
+    };
+    auto out = [&](auto* host, size_t count, bool want = true) -> decltype(host) {
+        if (!want) return nullptr;
+        if (!st) { bytes += count * sizeof(*host); ++n; return nullptr; }
+        return st->out(host, count);
+    };
+    RunIO d = h;
+    const uint32_t* state_in = nullptr;
+    auto arrays = [&]() {
+        d.ts = in(h.ts, P); d.pos = in(h.pos, P * 3); d.quat = in(h.quat, P * 4); d.slam_offsets = in(h.slam_offsets, nb + 1, ragged);
+        d.gps.t = in(h.gps.t, T); d.gps.llh = in(h.gps.llh, T * 3); d.gps.offsets = in(h.gps.offsets, nb + 1);
+        d.gt.t = in(h.gt.t, Tg, gt); d.gt.llh = in(h.gt.llh, Tg * 3, gt); d.gt.offsets = in(h.gt.offsets, nb + 1, gt);
+        state_in = in((const uint32_t*)h.mt_state, nb * 625);
+        d.mt_state = out(h.mt_state, nb * 625);
+        d.R = out(h.R, nb * 9); d.t = out(h.t, nb * 3); d.s = out(h.s, nb); d.pos_out = out(h.pos_out, P * 3); d.quat_out = out(h.quat_out, P * 4);
+        d.status = out(h.status, nb); d.n_inliers = out(h.n_inliers, nb); d.gps.zone = out(h.gps.zone, nb); d.gps.south = out(h.gps.south, nb);
+        d.gps.utm = out(h.gps.utm, T * 3); d.gps.keep = out(h.gps.keep, T); d.aligned = out(h.aligned, P * 3); d.valid = out(h.valid, P);
+        d.sim3_pos = out(h.sim3_pos, P * 3, h.sim3_pos != nullptr);
+        d.gt.zone = out(h.gt.zone, nb, gt); d.gt.south = out(h.gt.south, nb, gt); d.gt.utm = out(h.gt.utm, Tg * 3, gt); d.gt.keep = out(h.gt.keep, Tg, gt);
+        d.gt_aligned = out(h.gt_aligned, P * 3, gt); d.gt_valid = out(h.gt_valid, P, gt);
+        d.err_stats = out(h.err_stats, nb * (ragged ? 24 : 12)); d.plot_ref = out(h.plot_ref, nb, h.plot_ref != nullptr); d.run_status = out(h.run_status, nb);
+        d.inlier_mask = out(h.inlier_mask, P, h.inlier_mask != nullptr); d.trial_info = out(h.trial_info, nb * 2, h.trial_info != nullptr);
+    };
+    arrays();
+    Staging staging(ctx, bytes, n);
+    if (staging.rc()) return staging.rc();
+    st = &staging;
+    arrays();
+    int rc = staging.upload();
+    if (rc) return rc;
+    GSF_HIP(hipMemcpyAsync(d.mt_state, state_in, nb * 625 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = dev(ctx, d))) return rc;
+    return staging.finish();
+}
 
 }  // namespace
 
@@ -154,55 +364,11 @@ extern "C" int gsf_run_fusion_batch_dev(gsf_ctx* ctx, const double* ts, const do
                                         double* gps_utm, uint8_t* gps_keep, double* aligned, uint8_t* valid, double* sim3_pos,
                                         double* err_stats, int32_t* run_status, uint8_t* inlier_mask, int32_t* trial_info)
 {
-    GSF_REQUIRE(ctx && cfg, "ctx/cfg is NULL");
-    GSF_REQUIRE(B >= 0 && N >= 0 && B <= 0x7fffffff && total_fixes >= 0 && max_fixes >= 0, "bad B, N, total_fixes or max_fixes");
-    if (B == 0 || N == 0) return GSF_OK;
-    GSF_REQUIRE(ts && pos && quat && gps_offsets && mt_state && R && t && s && pos_out && quat_out && status && n_inliers && aligned && valid && err_stats &&
-                run_status && (!gps_llh || (zone && south)), "NULL array");
-    GSF_REQUIRE(total_fixes == 0 || (gps_t && gps_utm && gps_keep), "NULL GNSS array");
-    GSF_REQUIRE(N <= 28000, "N too large for the device-side draws (<= 28000 poses per trajectory)");
-    GSF_HIP(hipSetDevice(ctx->device));
-    const size_t P = (size_t)B * (size_t)N, nb = (size_t)B, T = (size_t)(total_fixes > 0 ? total_fixes : 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off = up256(off + bytes); return at; };
-    const size_t o_ct = take(T * 8), o_cp = take(T * 24), o_map = take(T * 4), o_ck = take(T), o_cnt = take(nb * 4), o_ls = take(nb * 4), o_li = take(nb * 8),
-                 o_fut = take(T * 24), o_so = take((nb + 1) * 8), o_as = take(nb * 4), o_sp = take(sim3_pos ? 0 : P * 24), o_sq = take(P * 32),
-                 o_bq = take(nb * 4), o_err = take(P * 24);
-    int rc = ensure_run_scratch(ctx, off);
-    if (rc) return rc;
-    char* w = (char*)ctx->run_scratch;
-    double* ct = (double*)(w + o_ct); double* cp = (double*)(w + o_cp); int32_t* rowmap = (int32_t*)(w + o_map); uint8_t* ckeep = (uint8_t*)(w + o_ck);
-    int32_t* counts = (int32_t*)(w + o_cnt); int32_t* log_status = (int32_t*)(w + o_ls); int32_t* log_info = (int32_t*)(w + o_li);
-    double* fut = (double*)(w + o_fut); int64_t* slam_off = (int64_t*)(w + o_so); int32_t* align_status = (int32_t*)(w + o_as);
-    double* sp = sim3_pos ? sim3_pos : (double*)(w + o_sp); double* sq = (double*)(w + o_sq); int32_t* badq = (int32_t*)(w + o_bq);
-    double* errs = (double*)(w + o_err);
-    // ---- step 1 (GPS side of load_gps_data)
-    // (gps_llh == NULL: the caller's gps_utm rows are the projected log already)
-    if (gps_llh && (rc = gsf_gps_rows_to_utm_batch_dev(ctx, gps_llh, gps_offsets, B, gps_utm, zone, south))) return rc;
-    hipLaunchKernelGGL(run_compact_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, gps_t, (const double*)gps_utm, gps_offsets, ct, cp, rowmap, counts,
-                       (const int32_t*)nullptr);
-    GSF_HIP(hipGetLastError());
-    if ((rc = launch_gps_prefilter_auto(ctx, ct, cp, gps_offsets, counts, B, max_fixes > 0 ? max_fixes : 1, &cfg->gps_filter, mt_state, ckeep, log_status, log_info))) return rc;
-    hipLaunchKernelGGL(run_filtered_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const double*)gps_utm, gps_offsets, (const int32_t*)counts,
-                       (const int32_t*)rowmap, (const uint8_t*)ckeep, (const int32_t*)log_status, fut, gps_keep, run_status, slam_off, badq, B, N);
-    GSF_HIP(hipGetLastError());
-    // ---- step 2
-    if ((rc = gsf_time_align_loaded_rows_batch_dev(ctx, ts, slam_off, gps_t, fut, gps_offsets, B, max_fixes > 2 ? max_fixes : 2, cfg->max_gps_gap_threshold,
-                                                   aligned, valid, align_status))) return rc;
-    // ---- steps 3-5 on the rows main_process_gui picks (ref :973-998), whatever the context's own row rule is
-    const FitRows saved = ctx->fit_rows;
-    ctx->fit_rows = FitRows{ 1, cfg->sim3_min_samples, cfg->max_gps_gap_threshold, cfg->sim3_max_initial_duration };
-    rc = robust_chain(ctx, ts, pos, quat, aligned, valid, &cfg->ekf, B, N, nullptr, 0, cfg->sim3_min_samples, cfg->sim3_residual_threshold,
-                      cfg->sim3_max_trials, cfg->sim3_min_inliers_needed, mt_state, R, t, s, pos_out, quat_out, status, n_inliers, inlier_mask, trial_info);
-    ctx->fit_rows = saved;
-    if (rc) return rc;
-    // ---- step 4 for every pose, step 6
-    if ((rc = launch_apply_sim3(ctx, pos, quat, slam_off, B, R, t, s, sp, sq, badq, true))) return rc;
-    if ((rc = launch_eval_errors3(ctx, ts, pos, sp, pos_out, aligned, valid, B, N, cfg->eval_skip_seconds, err_stats, errs))) return rc;
-    hipLaunchKernelGGL(run_outcome_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, B, N, (const int32_t*)status, run_status, R, t, s, pos_out, quat_out,
-                       sim3_pos, err_stats, n_inliers, (const int32_t*)badq, (const int64_t*)nullptr, (double*)nullptr, 0, (int32_t*)nullptr);
-    GSF_HIP(hipGetLastError());
-    return GSF_OK;
+    const RunIO io = { ts, pos, quat, nullptr, B, N, B * N,
+                       { gps_t, gps_llh, gps_offsets, total_fixes, max_fixes, cfg ? &cfg->gps_filter : nullptr, zone, south, gps_utm, gps_keep }, {},
+                       cfg, mt_state, R, t, s, pos_out, quat_out, status, n_inliers, aligned, valid, sim3_pos, nullptr, nullptr,
+                       err_stats, nullptr, run_status, inlier_mask, trial_info };
+    return run_fusion_batch_dev(ctx, io);
 }
 
 // the same with host arrays (what a cgo / JNI / ctypes caller with its data in host memory calls): one staged upload, the chain, one download
@@ -221,29 +387,11 @@ extern "C" int gsf_run_fusion_batch(gsf_ctx* ctx, const double* ts, const double
     int64_t max_fixes = 0;
     for (int64_t b = 0; b < B; ++b) { const int64_t g = gps_offsets[b + 1] - gps_offsets[b]; GSF_REQUIRE(g >= 0, "gps_offsets must not decrease"); if (g > max_fixes) max_fixes = g; }
     GSF_REQUIRE(max_fixes <= 0x7fffffff, "a log is too long");
-    const size_t P = (size_t)B * (size_t)N, nb = (size_t)B, T = (size_t)total;
-    Staging st(ctx, P * (64 + 56 + 24 + 1 + 24 + 1) + T * (8 + 24 + 24 + 1) + nb * (8 + 625 * 8 + 13 * 8 + 5 * 4 + 96 + 8) + 4096, 24);
-    if (st.rc()) return st.rc();
-    const double* dts = st.in(ts, P); const double* dpos = st.in(pos, P * 3); const double* dquat = st.in(quat, P * 4);
-    const double* dgt = st.in(gps_t, T); const double* dllh = st.in(gps_llh, T * 3); const int64_t* doff = st.in(gps_offsets, nb + 1);
-    const uint32_t* dst_in = st.in(mt_state, nb * 625);
-    uint32_t* dstate = st.out(mt_state, nb * 625);
-    double* dR = st.out(R, nb * 9); double* dt = st.out(t, nb * 3); double* ds = st.out(s, nb);
-    double* dpo = st.out(pos_out, P * 3); double* dqo = st.out(quat_out, P * 4); int32_t* dstat = st.out(status, nb); int32_t* dni = st.out(n_inliers, nb);
-    int32_t* dzone = st.out(zone, nb); int32_t* dsouth = st.out(south, nb);
-    double* dutm = st.out(gps_utm, T * 3); uint8_t* dkeep = st.out(gps_keep, T);
-    double* dal = st.out(aligned, P * 3); uint8_t* dva = st.out(valid, P);
-    double* dsp = sim3_pos ? st.out(sim3_pos, P * 3) : nullptr;
-    double* derr = st.out(err_stats, nb * 12); int32_t* drs = st.out(run_status, nb);
-    uint8_t* dmask = inlier_mask ? st.out(inlier_mask, P) : nullptr;
-    int32_t* dinfo = trial_info ? st.out(trial_info, nb * 2) : nullptr;
-    int rc = st.upload();
-    if (rc) return rc;
-    GSF_HIP(hipMemcpyAsync(dstate, dst_in, nb * 625 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = gsf_run_fusion_batch_dev(ctx, dts, dpos, dquat, B, N, dgt, dllh, doff, total, (int32_t)max_fixes, cfg, dstate, dR, dt, ds, dpo, dqo, dstat, dni, dzone, dsouth,
-                                  dutm, dkeep, dal, dva, dsp, derr, drs, dmask, dinfo);
-    if (rc) return rc;
-    return st.finish();
+    const RunIO io = { ts, pos, quat, nullptr, B, N, B * N,
+                       { gps_t, gps_llh, gps_offsets, total, (int32_t)max_fixes, &cfg->gps_filter, zone, south, gps_utm, gps_keep }, {},
+                       cfg, mt_state, R, t, s, pos_out, quat_out, status, n_inliers, aligned, valid, sim3_pos, nullptr, nullptr,
+                       err_stats, nullptr, run_status, inlier_mask, trial_info };
+    return run_staged(ctx, io, run_fusion_batch_dev);
 }
 
 // ---- the ragged entry: tracks of different lengths, optional ground-truth log (include/gsf.h)
@@ -257,90 +405,12 @@ extern "C" int gsf_run_fusion_ragged_dev(gsf_ctx* ctx, const double* ts, const d
                                          double* gt_aligned, uint8_t* gt_valid, double* err_stats, int32_t* plot_ref, int32_t* run_status,
                                          uint8_t* inlier_mask, int32_t* trial_info)
 {
-    GSF_REQUIRE(ctx && cfg, "ctx/cfg is NULL");
-    GSF_REQUIRE(B >= 0 && B <= 0x7fffffff && total_poses >= 0 && max_poses >= 0 && total_fixes >= 0 && max_fixes >= 0 && gt_total >= 0 && gt_max_fixes >= 0,
-                "bad B, total_poses, max_poses, total_fixes, max_fixes, gt_total or gt_max_fixes");
-    if (B == 0) return GSF_OK;
-    GSF_REQUIRE(max_poses <= 28000, "a track is too long for the device-side draws (<= 28000 poses per trajectory)");
-    GSF_REQUIRE(slam_offsets && gps_offsets && mt_state && R && t && s && status && n_inliers && err_stats && run_status && (!gps_llh || (zone && south)),
-                "NULL array");
-    GSF_REQUIRE(total_poses == 0 || (ts && pos && quat && pos_out && quat_out && aligned && valid), "NULL SLAM array");
-    GSF_REQUIRE(total_fixes == 0 || (gps_t && gps_utm && gps_keep), "NULL GNSS array");
-    const bool gt = gt_offsets != nullptr;
-    int rc0 = GSF_OK;
-    GSF_REQUIRE(!gt || (gt_filter && (!gt_llh || (gt_zone && gt_south)) && (total_poses == 0 || (gt_aligned && gt_valid)) &&
-                        (gt_total == 0 || (gt_t && gt_utm && gt_keep))), "NULL ground-truth array");
-    // both pre-filters' configurations and log lengths before the first one draws: a failing call leaves every generator where it was
-    if ((rc0 = check_gps_prefilter(&cfg->gps_filter, max_fixes > 0 ? max_fixes : 1, B))) return rc0;
-    if (gt && (rc0 = check_gps_prefilter(gt_filter, gt_max_fixes > 0 ? gt_max_fixes : 1, B))) return rc0;
-    GSF_HIP(hipSetDevice(ctx->device));
-    const int32_t nmax = max_poses > 0 ? max_poses : 1;
-    const size_t P = (size_t)total_poses, nb = (size_t)B, T = (size_t)(total_fixes > 0 ? total_fixes : 1), Tg = gt ? (size_t)(gt_total > 0 ? gt_total : 1) : 0;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off = up256(off + bytes); return at; };
-    const size_t o_ct = take(T * 8), o_cp = take(T * 24), o_map = take(T * 4), o_ck = take(T), o_cnt = take(nb * 4), o_ls = take(nb * 4), o_li = take(nb * 8),
-                 o_fut = take(T * 24), o_as = take(nb * 4), o_sp = take(sim3_pos ? 0 : P * 24), o_sq = take(P * 32), o_bq = take(nb * 4), o_err = take(P * 24),
-                 o_gct = take(Tg * 8), o_gcp = take(Tg * 24), o_gmap = take(Tg * 4), o_gck = take(Tg), o_gcnt = take(nb * 4), o_gls = take(nb * 4),
-                 o_gfut = take(Tg * 24), o_grs = take(nb * 4);
-    int rc = ensure_run_scratch(ctx, off);
-    if (rc) return rc;
-    char* w = (char*)ctx->run_scratch;
-    double* ct = (double*)(w + o_ct); double* cp = (double*)(w + o_cp); int32_t* rowmap = (int32_t*)(w + o_map); uint8_t* ckeep = (uint8_t*)(w + o_ck);
-    int32_t* counts = (int32_t*)(w + o_cnt); int32_t* log_status = (int32_t*)(w + o_ls); int32_t* log_info = (int32_t*)(w + o_li);
-    double* fut = (double*)(w + o_fut); int32_t* align_status = (int32_t*)(w + o_as);
-    double* sp = sim3_pos ? sim3_pos : (double*)(w + o_sp); double* sq = (double*)(w + o_sq); int32_t* badq = (int32_t*)(w + o_bq);
-    double* errs = (double*)(w + o_err);
-    // ---- step 1, primary log (load_gps_data, ref :961): mask, zone, UTM, pre-filter -- the first draws of each track's generator
-    if (gps_llh && (rc = gsf_gps_rows_to_utm_batch_dev(ctx, gps_llh, gps_offsets, B, gps_utm, zone, south))) return rc;
-    hipLaunchKernelGGL(run_compact_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, gps_t, (const double*)gps_utm, gps_offsets, ct, cp, rowmap, counts,
-                       (const int32_t*)nullptr);
-    GSF_HIP(hipGetLastError());
-    if ((rc = launch_gps_prefilter_auto(ctx, ct, cp, gps_offsets, counts, B, max_fixes > 0 ? max_fixes : 1, &cfg->gps_filter, mt_state, ckeep, log_status, log_info))) return rc;
-    hipLaunchKernelGGL(run_filtered_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const double*)gps_utm, gps_offsets, (const int32_t*)counts,
-                       (const int32_t*)rowmap, (const uint8_t*)ckeep, (const int32_t*)log_status, fut, gps_keep, run_status, (int64_t*)nullptr, badq, B, (int64_t)0);
-    GSF_HIP(hipGetLastError());
-    // ---- step 1, ground-truth log (ref :962-966): its own zone, its own pre-filter (CONFIG['ground_truth_gps_filtering']) -- the next draws, and
-    // none for a track whose primary log already stopped the run (gated to 0 fixes) or that has no ground truth (an empty range)
-    int32_t* grs = (int32_t*)(w + o_grs);
-    double* gfut = (double*)(w + o_gfut);
-    if (gt) {
-        double* gct = (double*)(w + o_gct); double* gcp = (double*)(w + o_gcp); int32_t* gmap = (int32_t*)(w + o_gmap); uint8_t* gck = (uint8_t*)(w + o_gck);
-        int32_t* gcnt = (int32_t*)(w + o_gcnt); int32_t* gls = (int32_t*)(w + o_gls);
-        if (gt_llh && (rc = gsf_gps_rows_to_utm_batch_dev(ctx, gt_llh, gt_offsets, B, gt_utm, gt_zone, gt_south))) return rc;
-        hipLaunchKernelGGL(run_compact_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, gt_t, (const double*)gt_utm, gt_offsets, gct, gcp, gmap, gcnt,
-                           (const int32_t*)run_status);
-        GSF_HIP(hipGetLastError());
-        if ((rc = launch_gps_prefilter_auto(ctx, gct, gcp, gt_offsets, gcnt, B, gt_max_fixes > 0 ? gt_max_fixes : 1, gt_filter, mt_state, gck, gls, log_info))) return rc;
-        hipLaunchKernelGGL(run_filtered_rows_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const double*)gt_utm, gt_offsets, (const int32_t*)gcnt,
-                           (const int32_t*)gmap, (const uint8_t*)gck, (const int32_t*)gls, gfut, gt_keep, grs, (int64_t*)nullptr, (int32_t*)nullptr, B, (int64_t)0);
-        GSF_HIP(hipGetLastError());
-    }
-    // ---- the ground truth's outcome and the empty SLAM track (ref :964, :967)
-    hipLaunchKernelGGL(run_gt_status_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, slam_offsets, gps_offsets, gt_offsets, (const int32_t*)grs, run_status, fut);
-    GSF_HIP(hipGetLastError());
-    // ---- step 2
-    if ((rc = gsf_time_align_loaded_rows_batch_dev(ctx, ts, slam_offsets, gps_t, fut, gps_offsets, B, max_fixes > 2 ? max_fixes : 2, cfg->max_gps_gap_threshold,
-                                                   aligned, valid, align_status))) return rc;
-    // ---- steps 3-5 (the reference's row choice, as in the dense entry)
-    const FitRows saved = ctx->fit_rows;
-    ctx->fit_rows = FitRows{ 1, cfg->sim3_min_samples, cfg->max_gps_gap_threshold, cfg->sim3_max_initial_duration };
-    rc = robust_chain(ctx, ts, pos, quat, aligned, valid, &cfg->ekf, B, nmax, slam_offsets, total_poses, cfg->sim3_min_samples, cfg->sim3_residual_threshold,
-                      cfg->sim3_max_trials, cfg->sim3_min_inliers_needed, mt_state, R, t, s, pos_out, quat_out, status, n_inliers, inlier_mask, trial_info);
-    ctx->fit_rows = saved;
-    if (rc) return rc;
-    // ---- step 4 for every pose, step 6 against the primary fixes and (ref :1035-1062) against the ground truth, aligned with the same values
-    if ((rc = launch_apply_sim3(ctx, pos, quat, slam_offsets, B, R, t, s, sp, sq, badq, true))) return rc;
-    if ((rc = launch_eval_errors3(ctx, ts, pos, sp, pos_out, aligned, valid, B, nmax, cfg->eval_skip_seconds, err_stats, errs, slam_offsets, total_poses))) return rc;
-    double* err_gt = err_stats + nb * 12;
-    if (gt) {
-        if ((rc = gsf_time_align_loaded_rows_batch_dev(ctx, ts, slam_offsets, gt_t, gfut, gt_offsets, B, gt_max_fixes > 2 ? gt_max_fixes : 2,
-                                                       cfg->max_gps_gap_threshold, gt_aligned, gt_valid, align_status))) return rc;
-        if ((rc = launch_eval_errors3(ctx, ts, pos, sp, pos_out, gt_aligned, gt_valid, B, nmax, cfg->eval_skip_seconds, err_gt, errs, slam_offsets, total_poses))) return rc;
-    }
-    hipLaunchKernelGGL(run_outcome_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, B, (int64_t)0, (const int32_t*)status, run_status, R, t, s, pos_out, quat_out,
-                       sim3_pos, err_stats, n_inliers, (const int32_t*)badq, slam_offsets, err_gt, gt ? 0 : 1, plot_ref);
-    GSF_HIP(hipGetLastError());
-    return GSF_OK;
+    const RunIO io = { ts, pos, quat, slam_offsets, B, max_poses, total_poses,
+                       { gps_t, gps_llh, gps_offsets, total_fixes, max_fixes, cfg ? &cfg->gps_filter : nullptr, zone, south, gps_utm, gps_keep },
+                       { gt_t, gt_llh, gt_offsets, gt_total, gt_max_fixes, gt_filter, gt_zone, gt_south, gt_utm, gt_keep },
+                       cfg, mt_state, R, t, s, pos_out, quat_out, status, n_inliers, aligned, valid, sim3_pos, gt_aligned, gt_valid,
+                       err_stats, plot_ref, run_status, inlier_mask, trial_info };
+    return run_fusion_ragged_dev(ctx, io);
 }
 
 // host arrays: the offsets are read here (sizes, limits), then one staged upload, the chain, one download
@@ -374,36 +444,13 @@ extern "C" int gsf_run_fusion_ragged(gsf_ctx* ctx, const double* ts, const doubl
     const bool gt = gt_offsets != nullptr;
     GSF_REQUIRE(!gt || (gt_filter && gt_zone && gt_south && (P == 0 || (gt_aligned && gt_valid)) && (gtot == 0 || (gt_t && gt_llh && gt_utm && gt_keep))),
                 "NULL ground-truth array");
+    // both pre-filters' configurations before the context is touched
     int rc0 = check_gps_prefilter(&cfg->gps_filter, max_fixes > 0 ? (int32_t)max_fixes : 1, B);
     if (rc0 || (gt && (rc0 = check_gps_prefilter(gt_filter, gmax > 0 ? (int32_t)gmax : 1, B)))) return rc0;
-    const size_t nb = (size_t)B, Pz = (size_t)P, T = (size_t)total, Tg = (size_t)gtot;
-    Staging st(ctx, Pz * (64 + 56 + 24 + 1 + 24 + 1 + 24 + 1) + (T + Tg) * (8 + 24 + 24 + 1) + nb * (24 + 625 * 8 + 13 * 8 + 9 * 4 + 192 + 8) + 8192, 40);
-    if (st.rc()) return st.rc();
-    const double* dts = st.in(ts, Pz); const double* dpos = st.in(pos, Pz * 3); const double* dquat = st.in(quat, Pz * 4);
-    const int64_t* dso = st.in(slam_offsets, nb + 1);
-    const double* dgt = st.in(gps_t, T); const double* dllh = st.in(gps_llh, T * 3); const int64_t* doff = st.in(gps_offsets, nb + 1);
-    const double* dtt = gt ? st.in(gt_t, Tg) : nullptr; const double* dtllh = gt ? st.in(gt_llh, Tg * 3) : nullptr;
-    const int64_t* dtoff = gt ? st.in(gt_offsets, nb + 1) : nullptr;
-    const uint32_t* dst_in = st.in(mt_state, nb * 625);
-    uint32_t* dstate = st.out(mt_state, nb * 625);
-    double* dR = st.out(R, nb * 9); double* dt = st.out(t, nb * 3); double* ds = st.out(s, nb);
-    double* dpo = st.out(pos_out, Pz * 3); double* dqo = st.out(quat_out, Pz * 4); int32_t* dstat = st.out(status, nb); int32_t* dni = st.out(n_inliers, nb);
-    int32_t* dzone = st.out(zone, nb); int32_t* dsouth = st.out(south, nb);
-    double* dutm = st.out(gps_utm, T * 3); uint8_t* dkeep = st.out(gps_keep, T);
-    double* dal = st.out(aligned, Pz * 3); uint8_t* dva = st.out(valid, Pz);
-    double* dsp = sim3_pos ? st.out(sim3_pos, Pz * 3) : nullptr;
-    int32_t* dgz = gt ? st.out(gt_zone, nb) : nullptr; int32_t* dgs = gt ? st.out(gt_south, nb) : nullptr;
-    double* dgu = gt ? st.out(gt_utm, Tg * 3) : nullptr; uint8_t* dgk = gt ? st.out(gt_keep, Tg) : nullptr;
-    double* dga = gt ? st.out(gt_aligned, Pz * 3) : nullptr; uint8_t* dgv = gt ? st.out(gt_valid, Pz) : nullptr;
-    double* derr = st.out(err_stats, nb * 24); int32_t* dpr = plot_ref ? st.out(plot_ref, nb) : nullptr; int32_t* drs = st.out(run_status, nb);
-    uint8_t* dmask = inlier_mask ? st.out(inlier_mask, Pz) : nullptr;
-    int32_t* dinfo = trial_info ? st.out(trial_info, nb * 2) : nullptr;
-    int rc = st.upload();
-    if (rc) return rc;
-    GSF_HIP(hipMemcpyAsync(dstate, dst_in, nb * 625 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = gsf_run_fusion_ragged_dev(ctx, dts, dpos, dquat, dso, B, P, (int32_t)max_poses, dgt, dllh, doff, total, (int32_t)max_fixes, dtt, dtllh, dtoff, gtot,
-                                   (int32_t)gmax, cfg, gt_filter, dstate, dR, dt, ds, dpo, dqo, dstat, dni, dzone, dsouth, dutm, dkeep, dal, dva, dsp, dgz, dgs,
-                                   dgu, dgk, dga, dgv, derr, dpr, drs, dmask, dinfo);
-    if (rc) return rc;
-    return st.finish();
+    const RunIO io = { ts, pos, quat, slam_offsets, B, max_poses, P,
+                       { gps_t, gps_llh, gps_offsets, total, (int32_t)max_fixes, &cfg->gps_filter, zone, south, gps_utm, gps_keep },
+                       { gt_t, gt_llh, gt_offsets, gtot, (int32_t)gmax, gt_filter, gt_zone, gt_south, gt_utm, gt_keep },
+                       cfg, mt_state, R, t, s, pos_out, quat_out, status, n_inliers, aligned, valid, sim3_pos, gt_aligned, gt_valid,
+                       err_stats, plot_ref, run_status, inlier_mask, trial_info };
+    return run_staged(ctx, io, run_fusion_ragged_dev);
 }

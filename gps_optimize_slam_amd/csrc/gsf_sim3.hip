@@ -955,9 +955,9 @@ int launch_sim3_ransac(gsf_ctx* ctx, const double* src, const double* dst, const
     const float* frows = nullptr; const double* fhdr = nullptr; const int32_t* ridx = nullptr;
     if (ctx->k2b_screen != 0 && total_rows > 0 && total_rows < ((int64_t)1 << 31) && trials - trial0 >= 64) {   // (slots and row indices of the screen are int32)
         const size_t hdr_bytes = ((size_t)B * RANSAC_HDR * 8 + 255) & ~(size_t)255;
-        const int rc = ensure_k2b_scratch(ctx, hdr_bytes + (size_t)total_rows * 28);
+        const int rc = ensure_workspace(ctx, GSF_WS_K2B, hdr_bytes + (size_t)total_rows * 28);
         if (rc) return rc;
-        double* h = (double*)ctx->k2b_scratch; float* f = (float*)((char*)ctx->k2b_scratch + hdr_bytes); int32_t* ri = (int32_t*)(f + (size_t)total_rows * 6);
+        double* h = workspace<double>(ctx, GSF_WS_K2B); float* f = (float*)(workspace(ctx, GSF_WS_K2B) + hdr_bytes); int32_t* ri = (int32_t*)(f + (size_t)total_rows * 6);
         hipLaunchKernelGGL(ransac_rows_kernel, dim3((unsigned)B), dim3(256), 0, ctx->stream, src, dst, offsets, counts, total_rows, f, ri, h, decided);
         GSF_HIP(hipGetLastError());                                       // a failed staging launch must not leave the scoring kernels on unstaged rows
         frows = f; fhdr = h; ridx = ri;
@@ -1019,9 +1019,9 @@ int gsf_sim3_umeyama_windows_dev(gsf_ctx* ctx, const double* src, const double* 
     GSF_REQUIRE(W == 0 || (src && dst), "NULL points");
     GSF_HIP(hipSetDevice(ctx->device));
     if (W == 0 || W > 4096) {                                             // empty windows (all None) / long windows: the ragged kernel on generated offsets
-        int rc = ensure_scratch(ctx, (size_t)(B + 1) * 8);
+        int rc = ensure_workspace(ctx, GSF_WS_KERNEL, (size_t)(B + 1) * 8);
         if (rc) return rc;
-        int64_t* off = (int64_t*)ctx->scratch;
+        int64_t* off = workspace<int64_t>(ctx, GSF_WS_KERNEL);
         hipLaunchKernelGGL(window_offsets_kernel, dim3((unsigned)((B + 256) / 256)), dim3(256), 0, ctx->stream, off, B, (int64_t)W);
         GSF_HIP(hipGetLastError());
         return gsf_sim3_umeyama_batch_dev(ctx, src, dst, mask, off, B, R, t, s, status);
@@ -1037,9 +1037,9 @@ int gsf_sim3_umeyama_windows_dev(gsf_ctx* ctx, const double* src, const double* 
         GSF_HIP(hipGetLastError());
         return GSF_OK;
     }
-    int rc = ensure_scratch(ctx, (size_t)B * WIN_REC * 8);
+    int rc = ensure_workspace(ctx, GSF_WS_KERNEL, (size_t)B * WIN_REC * 8);
     if (rc) return rc;
-    double* rec = (double*)ctx->scratch;
+    double* rec = workspace<double>(ctx, GSF_WS_KERNEL);
     const int64_t groups = (B + 3) / 4 * 4;                               // one 16-lane row per window and trip; grid-stride beyond 64 k blocks
     int64_t blocks = (groups * 16 + 255) / 256;
     if (blocks > 65536) blocks = 65536;
