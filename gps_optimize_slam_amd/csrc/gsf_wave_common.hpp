@@ -785,12 +785,29 @@ struct AxisVar { double Pf, Pm, kg; };
 // the scan on its own (identity carry): lane i holds the composition of the maps of poses first..i of the chunk; lanes that do not
 // step hold the identity, so lane 63 always holds the chunk's total
 struct Moebius { double A, B, C, D; };
+// 2^-e for a normal positive d = m 2^e with 1 <= m < 2, so that d * pow2_rcp_below(d) lies in [1, 2): two integer operations on the
+// high word (biased exponent E -> 2046 - E)
+__device__ __forceinline__ double pow2_rcp_below(const double d)
+{
+    return __hiloint2double(0x7fe00000 - (__double2hiint(d) & 0x7ff00000), 0);
+}
+// RANGE.  The step of a used fix is the map [[r, r q dt], [1, q dt + r]].  Multiplied out as it stands, 64 of them give entries of order
+// lambda^64 (lambda + r^2 / lambda = 2 r + q dt): beyond a double for r >= 1e5 or q dt >= 1e5, zero for r, q dt <= 1e-6 -- and the quotient of
+// moebius_apply() is then inf / inf or 0 / 0.  A Moebius map is unchanged by a common factor on its four entries, so every used fix scales
+// ITS OWN step by the power of two that brings D = q dt + r into [1, 2).  D lies within a factor of two of lambda (max diagonal entry <=
+// lambda <= trace), and it is what the step multiplies the denominator of the composed map by when the variance before it is small:
+// applied to P = 0 the denominator of a run of used fixes is the product of the innovation variances S_i = P_{i-1} + q dt_i + r over the
+// scaled D_i, each factor in [1, 4) because P_{i-1} < r after an update; a fix that ends an outage of k poses adds a factor of about k.  So
+// the scaled product stays below 4^64 times a few powers of 64, its C entry never falls below the first scale, and nothing depends on how
+// q dt and r compare.  Powers of two commute with every rounding of the products below and of moebius_apply() (no entry is subnormal on either side
+// wherever the unscaled form stayed in range), so the variances are the ones of the unscaled form BIT FOR BIT there -- the default
+// CONFIG included.  Stated range (include/gsf.h): 0 <= P0 <= 1e8, 1e-8 <= R <= 1e8, 0 <= Q dt <= 1e14.
 template <int NS = 6>
 __device__ __forceinline__ Moebius variance_scan(const double q, const double rr, const double dt, const bool stepping, const bool avail)
 {
     const double b0 = q * dt;
     double A = 1.0, Bm = stepping ? b0 : 0.0, Cm = 0.0, Dm = 1.0;
-    if (avail) { A = rr; Bm = rr * b0; Cm = 1.0; Dm = b0 + rr; }
+    if (avail) { const double d = b0 + rr, sc = pow2_rcp_below(d); A = rr * sc; Bm = (rr * b0) * sc; Cm = sc; Dm = d * sc; }
     // mine (later) o other (earlier); lanes without a source see the identity map (1,0;0,1)
 #define GSF_MSTAGE(CTRL, RM) {                                                                                              \
         const double oA = dpp<CTRL, RM>(1.0, A), oB = dpp0<CTRL, RM>(Bm), oC = dpp0<CTRL, RM>(Cm), oD = dpp<CTRL, RM>(1.0, Dm); \

@@ -54,7 +54,14 @@ typedef enum {
     GSF_LAYOUT_TIME_MAJOR = 1
 } gsf_layout;
 
-/* CONFIG['ekf'] + CONFIG['rts_decision'] of the reference (EKFGPSSLAM.py:24-29, :67-70) */
+/* CONFIG['ekf'] + CONFIG['rts_decision'] of the reference (EKFGPSSLAM.py:24-29, :67-70).
+   Stated range of the noise values, per position axis (P0 = initial_cov_diag, Q = process_noise_diag, R = meas_noise_diag, dt = the step
+   between two stamps in whatever unit the stamps are in, clamped to 1e-6 from below):
+       0 <= P0 <= 1e8,   1e-8 <= R <= 1e8,   0 <= Q dt <= 1e14,   finite inputs.
+   Inside it every route -- wave, two-wave, big-batch, early-variance, block, lane kernel, the covariance entry -- agrees with the oracle to
+   the stated gates (1e-6 m, status words exact; variances 1e-10 relative): tests/test_ekf_noise_domain.py.  The scan-based routes scale
+   every step matrix of their variance scans by a power of two, so the range does not depend on how Q dt and R compare or on the time unit
+   of the stamps.  Outside the range the behaviour is undocumented. */
 typedef struct {
     double initial_cov_diag[7];        /* :25 */
     double process_noise_diag[7];      /* :26  per second, used as variances */

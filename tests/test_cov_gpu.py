@@ -4,7 +4,9 @@ the decisions of the pose kernel behind ekf_fuse_ragged, inside the whole-run en
 stream and NULL optional outputs.
 
 Tolerance of every variance comparison: 1e-10 relative.  Derived, not tuned: the rounding of a 64-stage Moebius composition plus the carries
-is about 1e-14, and the smallest real mistake -- one dt off by a pose, a missed update, a wrong carry-in, a smoothing range off by one --
+is about 1e-14 (over the stated noise range 0 <= P0 <= 1e8, 1e-8 <= R <= 1e8, 0 <= Q dt <= 1e14, which tests/test_ekf_noise_domain.py covers:
+the scan scales its step matrices by powers of two; the smoothed variances of that file's extreme cases carry the cancellation of their closed
+form on top, see there), and the smallest real mistake -- one dt off by a pose, a missed update, a wrong carry-in, a smoothing range off by one --
 moves a variance by more than 1e-3 relative.  Flags, status words and everything called "the same" are compared exactly."""
 import copy
 import ctypes as C
