@@ -586,16 +586,11 @@ int gsf_time_align_batch(gsf_ctx* ctx, const double* slam_t, const int64_t* slam
     GSF_REQUIRE(ns >= 0 && ng >= 0 && (ns == 0 || (slam_t && aligned && valid)) && (ng == 0 || (gps_t && gps_p)), "bad offsets / NULL arrays");
     int64_t maxg = 2;
     for (int64_t b = 0; b < B; ++b) { const int64_t g = gps_offsets[b + 1] - gps_offsets[b]; if (g > maxg) maxg = g; }
-    Staging st(ctx, (size_t)ns * 33 + (size_t)ng * 32 + (size_t)(B + 1) * 16 + (size_t)B * 4, 8);
-    if (st.rc()) return st.rc();
-    const double* dst = st.in(slam_t, (size_t)ns); const double* dgt = st.in(gps_t, (size_t)ng); const double* dgp = st.in(gps_p, (size_t)ng * 3);
-    const int64_t* dso = st.in(slam_offsets, (size_t)B + 1); const int64_t* dgo = st.in(gps_offsets, (size_t)B + 1);
-    double* dal = st.out(aligned, (size_t)ns * 3); uint8_t* dva = st.out(valid, (size_t)ns); int32_t* dstat = st.out(status, (size_t)B);
-    int rc = st.upload();
-    if (rc) return rc;
-    rc = gsf_time_align_batch_dev(ctx, dst, dso, dgt, dgp, dgo, B, (int32_t)maxg, max_gps_gap_threshold, dal, dva, dstat);
-    if (rc) return rc;
-    return st.finish();
+    Staging st(ctx);
+    auto dst = st.in(slam_t, (size_t)ns); auto dgt = st.in(gps_t, (size_t)ng); auto dgp = st.in(gps_p, (size_t)ng * 3);
+    auto dso = st.in(slam_offsets, (size_t)B + 1); auto dgo = st.in(gps_offsets, (size_t)B + 1);
+    auto dal = st.out(aligned, (size_t)ns * 3); auto dva = st.out(valid, (size_t)ns); auto dstat = st.out(status, (size_t)B);
+    ST_RUN(gsf_time_align_batch_dev(ctx, dst, dso, dgt, dgp, dgo, B, (int32_t)maxg, max_gps_gap_threshold, dal, dva, dstat));
 }
 
 int gsf_clock_offset_search_dev(gsf_ctx* ctx, const double* ts, const double* pos, const int64_t* slam_offsets, const double* gps_t, const double* gps_utm,
@@ -652,21 +647,16 @@ int gsf_clock_offset_search(gsf_ctx* ctx, const double* ts, const double* pos, c
     }
     const size_t P = (size_t)slam_offsets[B], G = (size_t)gps_offsets[B], BK = (size_t)B * (size_t)K;
     GSF_REQUIRE((P == 0 || (ts && pos)) && (G == 0 || (gps_t && gps_utm)), "NULL arrays");
-    Staging st(ctx, P * 32 + G * 33 + (size_t)(B + 1) * 16 + (size_t)B * 8 + BK * 12 + (size_t)B * 136, 17);
-    if (st.rc()) return st.rc();
-    const double* dts = st.in(ts, P); const double* dpos = st.in(pos, P * 3); const int64_t* dso = st.in(slam_offsets, (size_t)B + 1);
-    const double* dgt = st.in(gps_t, G); const double* dgp = st.in(gps_utm, G * 3); const uint8_t* dgk = gps_keep ? st.in(gps_keep, G) : nullptr;
-    const int64_t* dgo = st.in(gps_offsets, (size_t)B + 1); const double* dt0 = tau0 ? st.in(tau0, (size_t)B) : nullptr;
-    double* dJ = st.out(J, BK); int32_t* dnr = n_rows ? st.out(n_rows, BK) : nullptr; int32_t* dbk = st.out(best_k, (size_t)B);
-    double* dtb = st.out(tau_best, (size_t)B); double* dtr = st.out(tau_refined, (size_t)B);
-    double* dR = R ? st.out(R, (size_t)B * 9) : nullptr; double* dt = R ? st.out(t, (size_t)B * 3) : nullptr; double* ds = R ? st.out(s, (size_t)B) : nullptr;
-    int32_t* dcs = st.out(clk_status, (size_t)B);
-    int rc = st.upload();
-    if (rc) return rc;
-    rc = gsf_clock_offset_search_dev(ctx, dts, dpos, dso, dgt, dgp, dgk, dgo, B, (int32_t)maxg, dt0, dtau, K, max_gps_gap_threshold, min_rows, flat_threshold,
-                                     dJ, dnr, dbk, dtb, dtr, dR, dt, ds, dcs);
-    if (rc) return rc;
-    return st.finish();
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dpos = st.in(pos, P * 3); auto dso = st.in(slam_offsets, (size_t)B + 1);
+    auto dgt = st.in(gps_t, G); auto dgp = st.in(gps_utm, G * 3); auto dgk = st.in_opt(gps_keep, G);
+    auto dgo = st.in(gps_offsets, (size_t)B + 1); auto dt0 = st.in_opt(tau0, (size_t)B);
+    auto dJ = st.out(J, BK); auto dnr = st.out_opt(n_rows, BK); auto dbk = st.out(best_k, (size_t)B);
+    auto dtb = st.out(tau_best, (size_t)B); auto dtr = st.out(tau_refined, (size_t)B);
+    auto dR = st.out_opt(R, (size_t)B * 9); auto dt = st.out_opt(t, (size_t)B * 3); auto ds = st.out_opt(s, (size_t)B);
+    auto dcs = st.out(clk_status, (size_t)B);
+    ST_RUN(gsf_clock_offset_search_dev(ctx, dts, dpos, dso, dgt, dgp, dgk, dgo, B, (int32_t)maxg, dt0, dtau, K, max_gps_gap_threshold, min_rows, flat_threshold,
+                                       dJ, dnr, dbk, dtb, dtr, dR, dt, ds, dcs));
 }
 
 }  // extern "C"

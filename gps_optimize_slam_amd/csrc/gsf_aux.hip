@@ -255,9 +255,6 @@ __global__ void rts_segment_kernel(const double* xf, const double* Pf, const dou
 
 }  // namespace
 
-#define ST_BEGIN(bytes, n) Staging st(ctx, (bytes), (n)); if (st.rc()) return st.rc()
-#define ST_UPLOAD() do { int rc__ = st.upload(); if (rc__) return rc__; } while (0)
-
 extern "C" {
 
 int gsf_relative_pose_batch(gsf_ctx* ctx, const double* p1, const double* q1, const double* p2, const double* q2, int64_t n, double* dp,
@@ -265,10 +262,10 @@ int gsf_relative_pose_batch(gsf_ctx* ctx, const double* p1, const double* q1, co
 {
     GSF_REQUIRE(ctx && n >= 0 && (n == 0 || (p1 && q1 && p2 && q2 && dp && dq)), "bad arguments");
     if (n == 0) return GSF_OK;
-    ST_BEGIN((size_t)n * (21 * 8 + 4), 7);
-    const double* a = st.in(p1, (size_t)n * 3); const double* dq1 = st.in(q1, (size_t)n * 4);
-    const double* dp2 = st.in(p2, (size_t)n * 3); const double* dq2 = st.in(q2, (size_t)n * 4);
-    double* ddp = st.out(dp, (size_t)n * 3); double* ddq = st.out(dq, (size_t)n * 4); int32_t* dbad = st.out(bad, (size_t)n);
+    Staging st(ctx);
+    auto a = st.in(p1, (size_t)n * 3); auto dq1 = st.in(q1, (size_t)n * 4);
+    auto dp2 = st.in(p2, (size_t)n * 3); auto dq2 = st.in(q2, (size_t)n * 4);
+    auto ddp = st.out(dp, (size_t)n * 3); auto ddq = st.out(dq, (size_t)n * 4); auto dbad = st.out(bad, (size_t)n);
     ST_UPLOAD();
     hipLaunchKernelGGL(relative_pose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a, dq1, dp2, dq2, n, ddp, ddq, dbad);
     GSF_HIP(hipGetLastError());
@@ -279,9 +276,9 @@ int gsf_quaternion_nlerp_batch(gsf_ctx* ctx, const double* q1, const double* q2,
 {
     GSF_REQUIRE(ctx && n >= 0 && (n == 0 || (q1 && q2 && w && out)), "bad arguments");
     if (n == 0) return GSF_OK;
-    ST_BEGIN((size_t)n * 13 * 8, 4);
-    const double* a = st.in(q1, (size_t)n * 4); const double* b = st.in(q2, (size_t)n * 4); const double* dw = st.in(w, (size_t)n);
-    double* o = st.out(out, (size_t)n * 4);
+    Staging st(ctx);
+    auto a = st.in(q1, (size_t)n * 4); auto b = st.in(q2, (size_t)n * 4); auto dw = st.in(w, (size_t)n);
+    auto o = st.out(out, (size_t)n * 4);
     ST_UPLOAD();
     hipLaunchKernelGGL(nlerp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a, b, dw, n, o);
     GSF_HIP(hipGetLastError());
@@ -295,11 +292,11 @@ int gsf_is_sharp_turn_batch(gsf_ctx* ctx, const double* quats, const double* sta
     if (B == 0) return GSF_OK;
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (quats && stamps)), "bad offsets / NULL arrays");
-    ST_BEGIN((size_t)total * 5 * 8 + (size_t)(B + 1) * 8 + (size_t)B * 12, 5);
-    const double* dq = st.in(quats, (size_t)total * 4); const double* dt = st.in(stamps, (size_t)total);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    int32_t* dres = st.out(result, (size_t)B);
-    double* dmr = max_rate ? st.out(max_rate, (size_t)B) : st.tmp<double>((size_t)B);
+    Staging st(ctx);
+    auto dq = st.in(quats, (size_t)total * 4); auto dt = st.in(stamps, (size_t)total);
+    auto doff = st.in(offsets, (size_t)B + 1);
+    auto dres = st.out(result, (size_t)B);
+    auto dmr = st.out(max_rate, (size_t)B);                                       // (NULL: scratch, not copied back)
     ST_UPLOAD();
     hipLaunchKernelGGL(sharp_turn_kernel, dim3((unsigned)B), dim3(64), 0, ctx->stream, dq, dt, doff, yaw_rate_threshold_rad_per_sec, dres, dmr);
     GSF_HIP(hipGetLastError());
@@ -317,13 +314,11 @@ int gsf_ekf_process_step(gsf_ctx* ctx, double* state, double* cov, const double*
     memcpy(h.state, state, sizeof h.state); memcpy(h.cov, cov, sizeof h.cov);
     memcpy(h.Qps, process_noise_per_sec, sizeof h.Qps); memcpy(h.R, meas_noise, sizeof h.R);
     h.gnss_prev = *gnss_available_prev; h.weight = *gnss_update_weight; h.current_steps = current_transition_steps;
-    ST_BEGIN(2 * sizeof(StepIO) + (3 + 4 + 3 + 7 + 49) * 8, 8);
+    Staging st(ctx);
     const double znan[3] = { NAN, NAN, NAN };
-    const StepIO* din = st.in(&h, 1);
-    const double* ddp = st.in(delta_pos_local, 3); const double* ddq = st.in(delta_quat, 4); const double* dz = st.in(gps_meas ? gps_meas : znan, 3);
-    StepIO* dio = st.out(&h, 1); double* dps = st.out(pred_state, 7); double* dpc = st.out(pred_cov, 49);
+    auto ddp = st.in(delta_pos_local, 3); auto ddq = st.in(delta_quat, 4); auto dz = st.in(gps_meas ? gps_meas : znan, 3);
+    auto dio = st.inout(&h, 1); auto dps = st.out(pred_state, 7); auto dpc = st.out(pred_cov, 49);
     ST_UPLOAD();
-    GSF_HIP(hipMemcpyAsync(dio, din, sizeof(StepIO), hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(process_step_kernel, dim3(1), dim3(64), 0, ctx->stream, dio, ddp, ddq, dz, gps_meas ? 1 : 0, gnss_is_available ? 1 : 0,
                        delta_time, override_transition_steps, dps, dpc);
     GSF_HIP(hipGetLastError());
@@ -342,11 +337,11 @@ int gsf_rts_smoother_segment_batch(gsf_ctx* ctx, const double* states_filt, cons
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (states_filt && covs_filt && states_pred && covs_pred && states_smooth && covs_smooth)), "NULL arrays");
     if (total == 0) return GSF_OK;
-    ST_BEGIN((size_t)total * (3 * 7 + 3 * 49) * 8 + (size_t)(B + 1) * 8, 7);
-    const double* xf = st.in(states_filt, (size_t)total * 7); const double* xp = st.in(states_pred, (size_t)total * 7);
-    const double* Pf = st.in(covs_filt, (size_t)total * 49); const double* Pp = st.in(covs_pred, (size_t)total * 49);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    double* xs = st.out(states_smooth, (size_t)total * 7); double* Ps = st.out(covs_smooth, (size_t)total * 49);
+    Staging st(ctx);
+    auto xf = st.in(states_filt, (size_t)total * 7); auto xp = st.in(states_pred, (size_t)total * 7);
+    auto Pf = st.in(covs_filt, (size_t)total * 49); auto Pp = st.in(covs_pred, (size_t)total * 49);
+    auto doff = st.in(offsets, (size_t)B + 1);
+    auto xs = st.out(states_smooth, (size_t)total * 7); auto Ps = st.out(covs_smooth, (size_t)total * 49);
     ST_UPLOAD();
     hipLaunchKernelGGL(rts_segment_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, xf, Pf, xp, Pp, doff, B, xs, Ps);
     GSF_HIP(hipGetLastError());

@@ -69,79 +69,58 @@ static void fill_words_host(void* p, size_t bytes, uint64_t word)
     for (size_t i = 0; i < bytes; ++i) ((unsigned char*)p)[i] = (unsigned char)(word >> (8 * (i & 7)));
 }
 
-Staging::Staging(gsf_ctx* ctx, size_t payload_bytes, int n_arrays) : ctx_(ctx)
+int Staging::add(void* host, size_t bytes, int kind, int from)
 {
-    cap_ = payload_bytes + (size_t)256 * (size_t)(n_arrays + 1);
-    direct_ = cap_ > PINNED_MAX;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) { rc_ = fail_hip(e, "hipSetDevice"); return; }
-    const void* const stage0 = ctx->stage; const void* const pinned0 = ctx->pinned;
-    rc_ = ensure_arena(&ctx->stage, &ctx->stage_bytes, cap_, false, ctx->stream);
-    if (rc_ == GSF_OK && !direct_) rc_ = ensure_arena(&ctx->pinned, &ctx->pinned_bytes, cap_, true, ctx->stream);
-    d_ = (char*)ctx->stage; h_ = (char*)ctx->pinned;
-    if (ctx->poison >= 0 && rc_ == GSF_OK) {                              // an arena that has just grown is dirtied like the others
-        if (ctx->stage != stage0) rc_ = launch_fill_words(ctx, ctx->stage, ctx->stage_bytes, (uint64_t)ctx->poison);
-        if (ctx->pinned && ctx->pinned != pinned0) fill_words_host(ctx->pinned, ctx->pinned_bytes, (uint64_t)ctx->poison);
+    const int i = tab_.add(bytes, kind, host != nullptr);
+    if (i < 0) {
+        if (rc_ == GSF_OK) { set_error("staging: more than %d arrays declared", STAGE_MAX_BLOCKS); rc_ = GSF_ERR_INVALID_ARG; }
+        return -1;
     }
-}
-
-void* Staging::take(size_t bytes, size_t& at)
-{
-    at = (off_ + 255) & ~(size_t)255;
-    if (rc_ != GSF_OK || at + bytes > cap_) {
-        if (rc_ == GSF_OK) { set_error("staging arena overrun (internal sizing error)"); rc_ = GSF_ERR_INVALID_ARG; }
-        return nullptr;
-    }
-    off_ = at + bytes;
-    return d_ + at;
-}
-
-void* Staging::in_bytes(const void* host, size_t bytes)
-{
-    size_t at; void* p = take(bytes, at);
-    if (!p) return nullptr;
-    if (has_out_) { set_error("staging: in() after out()"); rc_ = GSF_ERR_INVALID_ARG; return nullptr; }
-    if (bytes && host) {
-        if (direct_) { hipError_t e = hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, ctx_->stream); if (e != hipSuccess) rc_ = fail_hip(e, "hipMemcpyAsync(H2D)"); }
-        else memcpy(h_ + at, host, bytes);
-    }
-    in_end_ = off_;
-    return p;
-}
-
-void* Staging::out_bytes(void* host, size_t bytes)
-{
-    size_t at; void* p = take(bytes, at);
-    if (!p) return nullptr;
-    if (!has_out_) { has_out_ = true; out_lo_ = at; }
-    if (host && bytes) {
-        if (n_out_ >= MAX_OUT) { set_error("staging: too many outputs"); rc_ = GSF_ERR_INVALID_ARG; return nullptr; }
-        outs_[n_out_++] = Out{ host, at, bytes };
-    }
-    return p;
+    host_[i] = host; bind_[i] = nullptr; from_[i] = from;
+    return i;
 }
 
 int Staging::upload()
 {
     if (rc_ != GSF_OK) return rc_;
-    if (!direct_ && in_end_) GSF_HIP(hipMemcpyAsync(d_, h_, in_end_, hipMemcpyHostToDevice, ctx_->stream));
+    plan_ = stage_plan(tab_.b, tab_.n);
+    direct_ = plan_.cap > PINNED_MAX;
+    GSF_HIP(hipSetDevice(ctx_->device));
+    gsf_ctx* const ctx = ctx_;
+    const void* const stage0 = ctx->stage; const void* const pinned0 = ctx->pinned;
+    if ((rc_ = ensure_arena(&ctx->stage, &ctx->stage_bytes, plan_.cap, false, ctx->stream))) return rc_;
+    if (!direct_ && (rc_ = ensure_arena(&ctx->pinned, &ctx->pinned_bytes, plan_.cap, true, ctx->stream))) return rc_;
+    d_ = (char*)ctx->stage; h_ = (char*)ctx->pinned;
+    if (ctx->poison >= 0) {                                               // an arena that has just grown is dirtied like the others
+        if (ctx->stage != stage0 && (rc_ = launch_fill_words(ctx, ctx->stage, ctx->stage_bytes, (uint64_t)ctx->poison))) return rc_;
+        if (ctx->pinned && ctx->pinned != pinned0) fill_words_host(ctx->pinned, ctx->pinned_bytes, (uint64_t)ctx->poison);
+    }
+    for (int i = 0; i < tab_.n; ++i) {
+        const StageBlock& b = tab_.b[i];
+        if (bind_[i]) *bind_[i] = d_ + b.off;
+        if (b.kind != STAGE_IN || !b.host) continue;
+        if (direct_) GSF_HIP(hipMemcpyAsync(d_ + b.off, host_[i], b.bytes, hipMemcpyHostToDevice, ctx->stream));
+        else memcpy(h_ + b.off, host_[i], b.bytes);
+    }
+    if (!direct_ && plan_.in_end) GSF_HIP(hipMemcpyAsync(d_, h_, plan_.in_end, hipMemcpyHostToDevice, ctx->stream));
+    for (int i = 0; i < tab_.n; ++i)
+        if (from_[i] >= 0) GSF_HIP(hipMemcpyAsync(d_ + tab_.b[i].off, d_ + tab_.b[from_[i]].off, tab_.b[i].bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return GSF_OK;
 }
 
 int Staging::finish()
 {
     if (rc_ != GSF_OK) return rc_;
-    if (direct_) {
-        for (int k = 0; k < n_out_; ++k) GSF_HIP(hipMemcpyAsync(outs_[k].host, d_ + outs_[k].off, outs_[k].bytes, hipMemcpyDeviceToHost, ctx_->stream));
-        GSF_HIP(hipStreamSynchronize(ctx_->stream));
-        return GSF_OK;
+    if (!direct_ && plan_.d2h_hi > plan_.d2h_lo)
+        GSF_HIP(hipMemcpyAsync(h_ + plan_.d2h_lo, d_ + plan_.d2h_lo, plan_.d2h_hi - plan_.d2h_lo, hipMemcpyDeviceToHost, ctx_->stream));
+    if (!direct_) GSF_HIP(hipStreamSynchronize(ctx_->stream));
+    for (int i = 0; i < tab_.n; ++i) {
+        const StageBlock& b = tab_.b[i];
+        if (b.kind != STAGE_OUT || !b.host) continue;
+        if (direct_) GSF_HIP(hipMemcpyAsync(host_[i], d_ + b.off, b.bytes, hipMemcpyDeviceToHost, ctx_->stream));
+        else memcpy(host_[i], h_ + b.off, b.bytes);
     }
-    if (n_out_) {
-        const size_t hi = outs_[n_out_ - 1].off + outs_[n_out_ - 1].bytes;
-        GSF_HIP(hipMemcpyAsync(h_ + out_lo_, d_ + out_lo_, hi - out_lo_, hipMemcpyDeviceToHost, ctx_->stream));
-    }
-    GSF_HIP(hipStreamSynchronize(ctx_->stream));
-    for (int k = 0; k < n_out_; ++k) memcpy(outs_[k].host, h_ + outs_[k].off, outs_[k].bytes);
+    if (direct_) GSF_HIP(hipStreamSynchronize(ctx_->stream));
     return GSF_OK;
 }
 
@@ -335,18 +314,15 @@ int gsf_timer_stop(gsf_ctx* ctx, float* elapsed_ms)
 // ------------------------------------------------------------------------------------------
 // host-pointer forms: pack -> one H2D -> *_dev launch -> one D2H -> synchronise (gsf::Staging)
 // ------------------------------------------------------------------------------------------
-#define ST_BEGIN(bytes, n) Staging st(ctx, (bytes), (n)); if (st.rc()) return st.rc()
-#define ST_RUN(call) do { int rc__ = st.upload(); if (rc__) return rc__; rc__ = (call); if (rc__) return rc__; return st.finish(); } while (0)
-
 static int utm_host(gsf_ctx* ctx, bool inverse, const double* a, const double* b, int64_t n, int32_t zone, int32_t south, double* oa, double* ob)
 {
     GSF_REQUIRE(ctx && (n == 0 || (a && b && oa && ob)) && n >= 0, "bad arguments");
     if (n == 0) return GSF_OK;
-    ST_BEGIN((size_t)n * 32 + 24, 6);
+    Staging st(ctx);
     const int64_t off[2] = { 0, n }; const int32_t zs[2] = { zone, south };
-    const double* da = st.in(a, (size_t)n); const double* db = st.in(b, (size_t)n);
-    const int64_t* doff = st.in(off, 2); const int32_t* dzs = st.in(zs, 2);
-    double* doa = st.out(oa, (size_t)n); double* dob = st.out(ob, (size_t)n);
+    auto da = st.in(a, (size_t)n); auto db = st.in(b, (size_t)n);
+    auto doff = st.in(off, 2); auto dzs = st.in(zs, 2);
+    auto doa = st.out(oa, (size_t)n); auto dob = st.out(ob, (size_t)n);
     if (inverse) ST_RUN(gsf_utm_inverse_batch_dev(ctx, da, db, doff, dzs, dzs + 1, 1, doa, dob));
     ST_RUN(gsf_utm_forward_batch_dev(ctx, da, db, doff, dzs, dzs + 1, 1, doa, dob));
 }
@@ -368,12 +344,12 @@ int gsf_sim3_umeyama_batch(gsf_ctx* ctx, const double* src, const double* dst, c
     if (B == 0) return GSF_OK;
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (src && dst)), "bad offsets / NULL points");
-    ST_BEGIN((size_t)total * 49 + (size_t)(B + 1) * 8 + (size_t)B * 108, 8);
-    const double* dsrc = st.in(src, (size_t)total * 3); const double* ddst = st.in(dst, (size_t)total * 3);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const uint8_t* dmask = mask ? st.in(mask, (size_t)total) : nullptr;
-    double* dR = st.out(R, (size_t)B * 9); double* dt = st.out(t, (size_t)B * 3); double* ds = st.out(s, (size_t)B);
-    int32_t* dst_ = st.out(status, (size_t)B);
+    Staging st(ctx);
+    auto dsrc = st.in(src, (size_t)total * 3); auto ddst = st.in(dst, (size_t)total * 3);
+    auto doff = st.in(offsets, (size_t)B + 1);
+    auto dmask = st.in_opt(mask, (size_t)total);
+    auto dR = st.out(R, (size_t)B * 9); auto dt = st.out(t, (size_t)B * 3); auto ds = st.out(s, (size_t)B);
+    auto dst_ = st.out(status, (size_t)B);
     ST_RUN(gsf_sim3_umeyama_batch_dev(ctx, dsrc, ddst, dmask, doff, B, dR, dt, ds, dst_));
 }
 
@@ -387,13 +363,13 @@ int gsf_sim3_ransac_batch(gsf_ctx* ctx, const double* src, const double* dst, co
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (src && dst)), "bad offsets / NULL points");
     const size_t nidx = (size_t)B * (size_t)trials * (size_t)min_samples;
-    ST_BEGIN((size_t)total * 49 + (size_t)(B + 1) * 8 + nidx * 4 + (size_t)B * 112, 10);
-    const double* dsrc = st.in(src, (size_t)total * 3); const double* ddst = st.in(dst, (size_t)total * 3);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const int32_t* didx = st.in(sample_idx, nidx);
-    double* dR = st.out(R, (size_t)B * 9); double* dt = st.out(t, (size_t)B * 3); double* ds = st.out(s, (size_t)B);
-    int32_t* dst_ = st.out(status, (size_t)B); int32_t* dni = st.out(n_inliers, (size_t)B);
-    uint8_t* dmask = st.out(inlier_mask, (size_t)total);
+    Staging st(ctx);
+    auto dsrc = st.in(src, (size_t)total * 3); auto ddst = st.in(dst, (size_t)total * 3);
+    auto doff = st.in(offsets, (size_t)B + 1);
+    auto didx = st.in(sample_idx, nidx);
+    auto dR = st.out(R, (size_t)B * 9); auto dt = st.out(t, (size_t)B * 3); auto ds = st.out(s, (size_t)B);
+    auto dst_ = st.out(status, (size_t)B); auto dni = st.out(n_inliers, (size_t)B);
+    auto dmask = st.out(inlier_mask, (size_t)total);
     ST_RUN(gsf_sim3_ransac_batch_rows_dev(ctx, dsrc, ddst, doff, total, B, didx, trials, min_samples, thr, min_inliers, dR, dt, ds, dst_, dmask, dni));
 }
 
@@ -416,19 +392,17 @@ int gsf_sim3_ransac_mt_batch(gsf_ctx* ctx, const double* src, const double* dst,
         if ((int32_t)n > n_max) n_max = (int32_t)n;
     }
     const size_t nidx = (size_t)B * (size_t)trials * (size_t)min_samples;
-    ST_BEGIN((size_t)total * 49 + (size_t)(B + 1) * 8 + (size_t)B * (625 * 8 + 4 + 112) + nidx * 4, 14);
-    const double* dsrc = st.in(src, (size_t)total * 3); const double* ddst = st.in(dst, (size_t)total * 3);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const int32_t* dcnt = st.in(counts.data(), (size_t)B);
-    const uint32_t* dst_in = st.in(mt_state, (size_t)B * 625);
-    uint32_t* dstate = st.out(mt_state, (size_t)B * 625);
-    double* dR = st.out(R, (size_t)B * 9); double* dt = st.out(t, (size_t)B * 3); double* ds = st.out(s, (size_t)B);
-    int32_t* dst_ = st.out(status, (size_t)B); int32_t* dni = st.out(n_inliers, (size_t)B);
-    uint8_t* dmask = st.out(inlier_mask, (size_t)total);
-    int32_t* didx = st.tmp<int32_t>(nidx + 1);
-    int rc = st.upload();
-    if (rc) return rc;
-    GSF_HIP(hipMemcpyAsync(dstate, dst_in, (size_t)B * 625 * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    Staging st(ctx);
+    auto dsrc = st.in(src, (size_t)total * 3); auto ddst = st.in(dst, (size_t)total * 3);
+    auto doff = st.in(offsets, (size_t)B + 1);
+    auto dcnt = st.in(counts.data(), (size_t)B);
+    auto dstate = st.inout(mt_state, (size_t)B * 625);
+    auto dR = st.out(R, (size_t)B * 9); auto dt = st.out(t, (size_t)B * 3); auto ds = st.out(s, (size_t)B);
+    auto dst_ = st.out(status, (size_t)B); auto dni = st.out(n_inliers, (size_t)B);
+    auto dmask = st.out(inlier_mask, (size_t)total);
+    auto didx = st.tmp<int32_t>(nidx + 1);
+    ST_UPLOAD();
+    int rc;
     if (trials > 0 && (rc = launch_mt_choice(ctx, dstate, dcnt, B, trials, min_samples, didx, n_max))) return rc;
     if ((rc = launch_sim3_ransac(ctx, dsrc, ddst, doff, nullptr, B, didx, trials, min_samples, thr, min_inliers, dR, dt, ds, dst_, dmask, dni, total))) return rc;
     return st.finish();
@@ -441,12 +415,12 @@ int gsf_apply_sim3_batch(gsf_ctx* ctx, const double* pos, const double* quat, co
     if (B == 0) return GSF_OK;
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (pos && quat && pos_out && quat_out)), "bad offsets / NULL poses");
-    ST_BEGIN((size_t)total * 112 + (size_t)(B + 1) * 8 + (size_t)B * 108, 9);
-    const double* dpos = st.in(pos, (size_t)total * 3); const double* dquat = st.in(quat, (size_t)total * 4);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const double* dR = st.in(R, (size_t)B * 9); const double* dt = st.in(t, (size_t)B * 3); const double* ds = st.in(s, (size_t)B);
-    double* dpo = st.out(pos_out, (size_t)total * 3); double* dqo = st.out(quat_out, (size_t)total * 4);
-    int32_t* dbad = st.out(bad_quat, (size_t)B);
+    Staging st(ctx);
+    auto dpos = st.in(pos, (size_t)total * 3); auto dquat = st.in(quat, (size_t)total * 4);
+    auto doff = st.in(offsets, (size_t)B + 1);
+    auto dR = st.in(R, (size_t)B * 9); auto dt = st.in(t, (size_t)B * 3); auto ds = st.in(s, (size_t)B);
+    auto dpo = st.out(pos_out, (size_t)total * 3); auto dqo = st.out(quat_out, (size_t)total * 4);
+    auto dbad = st.out(bad_quat, (size_t)B);
     ST_RUN(gsf_apply_sim3_batch_dev(ctx, dpos, dquat, doff, B, dR, dt, ds, dpo, dqo, dbad));
 }
 
@@ -458,11 +432,11 @@ int gsf_ekf_fuse_batch(gsf_ctx* ctx, int32_t layout, const double* ts, const dou
     if (B == 0 || N == 0) return GSF_OK;
     GSF_REQUIRE(ts && pos && quat && gps && valid && init_pos && init_quat && pos_out && quat_out, "NULL array");
     const size_t P = (size_t)B * (size_t)N;
-    ST_BEGIN(P * 145 + (size_t)B * 60, 10);
-    const double* dts = st.in(ts, P); const double* dpos = st.in(pos, P * 3); const double* dquat = st.in(quat, P * 4);
-    const double* dgps = st.in(gps, P * 3); const uint8_t* dval = st.in(valid, P);
-    const double* dip = st.in(init_pos, (size_t)B * 3); const double* diq = st.in(init_quat, (size_t)B * 4);
-    double* dpo = st.out(pos_out, P * 3); double* dqo = st.out(quat_out, P * 4); int32_t* dst_ = st.out(status, (size_t)B);
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dpos = st.in(pos, P * 3); auto dquat = st.in(quat, P * 4);
+    auto dgps = st.in(gps, P * 3); auto dval = st.in(valid, P);
+    auto dip = st.in(init_pos, (size_t)B * 3); auto diq = st.in(init_quat, (size_t)B * 4);
+    auto dpo = st.out(pos_out, P * 3); auto dqo = st.out(quat_out, P * 4); auto dst_ = st.out(status, (size_t)B);
     ST_RUN(gsf_ekf_fuse_batch_dev(ctx, layout, dts, dpos, dquat, dgps, dval, dip, diq, cfg, B, N, dpo, dqo, dst_));
 }
 
@@ -475,11 +449,11 @@ int gsf_fuse_pipeline_batch(gsf_ctx* ctx, int32_t layout, const double* ts, cons
     if (B == 0 || N == 0) return GSF_OK;
     GSF_REQUIRE(ts && pos && quat && gps && valid && R && t && s && pos_out && quat_out && status, "NULL array");
     const size_t P = (size_t)B * (size_t)N;
-    ST_BEGIN(P * 145 + (size_t)B * 108, 11);
-    const double* dts = st.in(ts, P); const double* dpos = st.in(pos, P * 3); const double* dquat = st.in(quat, P * 4);
-    const double* dgps = st.in(gps, P * 3); const uint8_t* dval = st.in(valid, P);
-    double* dR = st.out(R, (size_t)B * 9); double* dt = st.out(t, (size_t)B * 3); double* ds = st.out(s, (size_t)B);
-    double* dpo = st.out(pos_out, P * 3); double* dqo = st.out(quat_out, P * 4); int32_t* dst_ = st.out(status, (size_t)B);
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dpos = st.in(pos, P * 3); auto dquat = st.in(quat, P * 4);
+    auto dgps = st.in(gps, P * 3); auto dval = st.in(valid, P);
+    auto dR = st.out(R, (size_t)B * 9); auto dt = st.out(t, (size_t)B * 3); auto ds = st.out(s, (size_t)B);
+    auto dpo = st.out(pos_out, P * 3); auto dqo = st.out(quat_out, P * 4); auto dst_ = st.out(status, (size_t)B);
     ST_RUN(gsf_fuse_pipeline_batch_dev(ctx, layout, dts, dpos, dquat, dgps, dval, cfg, B, N, dR, dt, ds, dpo, dqo, dst_));
 }
 
@@ -495,10 +469,10 @@ int gsf_sim3_fit_rows_batch(gsf_ctx* ctx, const double* ts, const double* gps, c
     GSF_REQUIRE(total >= 0, "bad offsets");
     if (total == 0) { for (int64_t b = 0; b < B; ++b) { n_rows[b] = -1; if (status) status[b] = GSF_SIM3_FLAG_FEW_ROWS; } return GSF_OK; }
     const size_t P = (size_t)total;
-    ST_BEGIN(P * 34 + (size_t)B * 16 + 64, 8);
-    const double* dts = st.in(ts, P); const double* dgps = gps ? st.in(gps, P * 3) : nullptr; const uint8_t* dval = st.in(valid, P);
-    const int64_t* doff = offsets ? st.in(offsets, (size_t)B + 1) : nullptr;
-    uint8_t* dmask = st.out(row_mask, P); int32_t* dn = st.out(n_rows, (size_t)B); int32_t* dst_ = status ? st.out(status, (size_t)B) : nullptr;
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dgps = st.in_opt(gps, P * 3); auto dval = st.in(valid, P);
+    auto doff = st.in_opt(offsets, (size_t)B + 1);
+    auto dmask = st.out(row_mask, P); auto dn = st.out(n_rows, (size_t)B); auto dst_ = st.out_opt(status, (size_t)B);
     ST_RUN(gsf_sim3_fit_rows_batch_dev(ctx, dts, dgps, dval, doff, B, N, min_samples, max_gps_gap_threshold, max_initial_duration, dmask, dn, dst_));
 }
 
@@ -513,22 +487,16 @@ int gsf_fuse_pipeline_robust_batch(gsf_ctx* ctx, const double* ts, const double*
     if (B == 0 || N == 0) return GSF_OK;
     GSF_REQUIRE(ts && pos && quat && gps && valid && R && t && s && pos_out && quat_out && status && n_inliers, "NULL array");
     const size_t P = (size_t)B * (size_t)N;
-    ST_BEGIN(P * 146 + (size_t)B * (112 + 625 * 8), 15);
-    const double* dts = st.in(ts, P); const double* dpos = st.in(pos, P * 3); const double* dquat = st.in(quat, P * 4);
-    const double* dgps = st.in(gps, P * 3); const uint8_t* dval = st.in(valid, P);
-    const uint32_t* dst_in = st.in(mt_state, (size_t)B * 625);
-    uint32_t* dstate = st.out(mt_state, (size_t)B * 625);
-    double* dR = st.out(R, (size_t)B * 9); double* dt = st.out(t, (size_t)B * 3); double* ds = st.out(s, (size_t)B);
-    double* dpo = st.out(pos_out, P * 3); double* dqo = st.out(quat_out, P * 4); int32_t* dst_ = st.out(status, (size_t)B);
-    int32_t* dni = st.out(n_inliers, (size_t)B);
-    uint8_t* dmask = inlier_mask ? st.out(inlier_mask, P) : nullptr;
-    int rc = st.upload();
-    if (rc) return rc;
-    GSF_HIP(hipMemcpyAsync(dstate, dst_in, (size_t)B * 625 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = gsf_fuse_pipeline_robust_batch_dev(ctx, dts, dpos, dquat, dgps, dval, cfg, B, N, min_samples, residual_threshold, max_trials,
-                                            min_inliers_needed, dstate, dR, dt, ds, dpo, dqo, dst_, dni, dmask);
-    if (rc) return rc;
-    return st.finish();
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dpos = st.in(pos, P * 3); auto dquat = st.in(quat, P * 4);
+    auto dgps = st.in(gps, P * 3); auto dval = st.in(valid, P);
+    auto dstate = st.inout(mt_state, (size_t)B * 625);
+    auto dR = st.out(R, (size_t)B * 9); auto dt = st.out(t, (size_t)B * 3); auto ds = st.out(s, (size_t)B);
+    auto dpo = st.out(pos_out, P * 3); auto dqo = st.out(quat_out, P * 4); auto dst_ = st.out(status, (size_t)B);
+    auto dni = st.out(n_inliers, (size_t)B);
+    auto dmask = st.out_opt(inlier_mask, P);
+    ST_RUN(gsf_fuse_pipeline_robust_batch_dev(ctx, dts, dpos, dquat, dgps, dval, cfg, B, N, min_samples, residual_threshold, max_trials,
+                                              min_inliers_needed, dstate, dR, dt, ds, dpo, dqo, dst_, dni, dmask));
 }
 
 // tracks of different lengths (flat [total][C] host arrays, trajectory b = rows offsets[b]..offsets[b+1])
@@ -541,11 +509,11 @@ int gsf_ekf_fuse_ragged(gsf_ctx* ctx, const double* ts, const double* pos, const
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (ts && pos && quat && gps && valid && pos_out && quat_out)), "bad offsets / NULL arrays");
     const size_t P = (size_t)total;
-    ST_BEGIN(P * 145 + (size_t)(B + 1) * 8 + (size_t)B * 60, 11);
-    const double* dts = st.in(ts, P); const double* dpos = st.in(pos, P * 3); const double* dquat = st.in(quat, P * 4);
-    const double* dgps = st.in(gps, P * 3); const uint8_t* dval = st.in(valid, P); const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const double* dip = st.in(init_pos, (size_t)B * 3); const double* diq = st.in(init_quat, (size_t)B * 4);
-    double* dpo = st.out(pos_out, P * 3); double* dqo = st.out(quat_out, P * 4); int32_t* dst_ = st.out(status, (size_t)B);
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dpos = st.in(pos, P * 3); auto dquat = st.in(quat, P * 4);
+    auto dgps = st.in(gps, P * 3); auto dval = st.in(valid, P); auto doff = st.in(offsets, (size_t)B + 1);
+    auto dip = st.in(init_pos, (size_t)B * 3); auto diq = st.in(init_quat, (size_t)B * 4);
+    auto dpo = st.out(pos_out, P * 3); auto dqo = st.out(quat_out, P * 4); auto dst_ = st.out(status, (size_t)B);
     ST_RUN(gsf_ekf_fuse_ragged_dev(ctx, dts, dpos, dquat, dgps, dval, doff, dip, diq, cfg, B, dpo, dqo, dst_));
 }
 int gsf_fuse_pipeline_ragged(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
@@ -557,11 +525,11 @@ int gsf_fuse_pipeline_ragged(gsf_ctx* ctx, const double* ts, const double* pos, 
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (ts && pos && quat && gps && valid && pos_out && quat_out)), "bad offsets / NULL arrays");
     const size_t P = (size_t)total;
-    ST_BEGIN(P * 145 + (size_t)(B + 1) * 8 + (size_t)B * 108, 12);
-    const double* dts = st.in(ts, P); const double* dpos = st.in(pos, P * 3); const double* dquat = st.in(quat, P * 4);
-    const double* dgps = st.in(gps, P * 3); const uint8_t* dval = st.in(valid, P); const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    double* dR = st.out(R, (size_t)B * 9); double* dt = st.out(t, (size_t)B * 3); double* ds = st.out(s, (size_t)B);
-    double* dpo = st.out(pos_out, P * 3); double* dqo = st.out(quat_out, P * 4); int32_t* dst_ = st.out(status, (size_t)B);
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dpos = st.in(pos, P * 3); auto dquat = st.in(quat, P * 4);
+    auto dgps = st.in(gps, P * 3); auto dval = st.in(valid, P); auto doff = st.in(offsets, (size_t)B + 1);
+    auto dR = st.out(R, (size_t)B * 9); auto dt = st.out(t, (size_t)B * 3); auto ds = st.out(s, (size_t)B);
+    auto dpo = st.out(pos_out, P * 3); auto dqo = st.out(quat_out, P * 4); auto dst_ = st.out(status, (size_t)B);
     ST_RUN(gsf_fuse_pipeline_ragged_dev(ctx, dts, dpos, dquat, dgps, dval, doff, cfg, B, dR, dt, ds, dpo, dqo, dst_));
 }
 
@@ -575,12 +543,12 @@ int gsf_ekf_cov_ragged(gsf_ctx* ctx, const double* ts, const double* quat, const
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (ts && quat && gps && valid && cov_out)), "bad offsets / NULL arrays");
     const size_t P = (size_t)total;
-    ST_BEGIN(P * (65 + 113) + (size_t)(B + 1) * 8 + (size_t)B * 8, 10);
-    const double* dts = st.in(ts, P); const double* dquat = st.in(quat, P * 4); const double* dgps = st.in(gps, P * 3);
-    const uint8_t* dval = st.in(valid, P); const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const int32_t* drs = run_status ? st.in(run_status, (size_t)B) : nullptr;
-    double* dcf = cov_filt ? st.out(cov_filt, P * 7) : nullptr; double* dco = st.out(cov_out, P * 7);
-    uint8_t* dfl = pose_flags ? st.out(pose_flags, P) : nullptr; int32_t* dst_ = status ? st.out(status, (size_t)B) : nullptr;
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dquat = st.in(quat, P * 4); auto dgps = st.in(gps, P * 3);
+    auto dval = st.in(valid, P); auto doff = st.in(offsets, (size_t)B + 1);
+    auto drs = st.in_opt(run_status, (size_t)B);
+    auto dcf = st.out_opt(cov_filt, P * 7); auto dco = st.out(cov_out, P * 7);
+    auto dfl = st.out_opt(pose_flags, P); auto dst_ = st.out_opt(status, (size_t)B);
     ST_RUN(gsf_ekf_cov_ragged_dev(ctx, dts, dquat, dgps, dval, doff, drs, cfg, B, dcf, dco, dfl, dst_));
 }
 
@@ -592,10 +560,10 @@ int gsf_sim3_umeyama_windows(gsf_ctx* ctx, const double* src, const double* dst,
     if (B == 0) return GSF_OK;
     GSF_REQUIRE(W == 0 || (src && dst), "NULL points");
     const size_t P = (size_t)B * (size_t)W;
-    ST_BEGIN(P * 49 + (size_t)B * 108, 7);
-    const double* dsrc = st.in(src, P * 3); const double* ddst = st.in(dst, P * 3);
-    const uint8_t* dmask = mask ? st.in(mask, P) : nullptr;
-    double* dR = st.out(R, (size_t)B * 9); double* dt = st.out(t, (size_t)B * 3); double* ds = st.out(s, (size_t)B); int32_t* dst_ = st.out(status, (size_t)B);
+    Staging st(ctx);
+    auto dsrc = st.in(src, P * 3); auto ddst = st.in(dst, P * 3);
+    auto dmask = st.in_opt(mask, P);
+    auto dR = st.out(R, (size_t)B * 9); auto dt = st.out(t, (size_t)B * 3); auto ds = st.out(s, (size_t)B); auto dst_ = st.out(status, (size_t)B);
     ST_RUN(gsf_sim3_umeyama_windows_dev(ctx, dsrc, ddst, dmask, B, W, dR, dt, ds, dst_));
 }
 
@@ -608,10 +576,10 @@ int gsf_geodetic_to_enu_batch(gsf_ctx* ctx, const double* lat_deg, const double*
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (lat_deg && lon_deg && alt && east && north && up)), "bad offsets / NULL arrays");
     const size_t P = (size_t)total;
-    ST_BEGIN(P * 48 + (size_t)(B + 1) * 8 + (size_t)B * 24, 8);
-    const double* dla = st.in(lat_deg, P); const double* dlo = st.in(lon_deg, P); const double* dal = st.in(alt, P);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1); const double* dref = st.in(ref_llh, (size_t)B * 3);
-    double* de = st.out(east, P); double* dn = st.out(north, P); double* du = st.out(up, P);
+    Staging st(ctx);
+    auto dla = st.in(lat_deg, P); auto dlo = st.in(lon_deg, P); auto dal = st.in(alt, P);
+    auto doff = st.in(offsets, (size_t)B + 1); auto dref = st.in(ref_llh, (size_t)B * 3);
+    auto de = st.out(east, P); auto dn = st.out(north, P); auto du = st.out(up, P);
     ST_RUN(gsf_geodetic_to_enu_batch_dev(ctx, dla, dlo, dal, doff, dref, B, de, dn, du));
 }
 
@@ -622,9 +590,9 @@ int gsf_gps_rows_to_utm_batch(gsf_ctx* ctx, const double* llh, const int64_t* of
     if (B == 0) return GSF_OK;
     const int64_t total = offsets[B];
     GSF_REQUIRE(total >= 0 && (total == 0 || (llh && utm_rows)), "bad offsets / NULL rows");
-    ST_BEGIN((size_t)total * 48 + (size_t)(B + 1) * 8 + (size_t)B * 8, 5);
-    const double* dllh = st.in(llh, (size_t)total * 3); const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    double* dutm = st.out(utm_rows, (size_t)total * 3); int32_t* dz = st.out(zone, (size_t)B); int32_t* dso = st.out(south, (size_t)B);
+    Staging st(ctx);
+    auto dllh = st.in(llh, (size_t)total * 3); auto doff = st.in(offsets, (size_t)B + 1);
+    auto dutm = st.out(utm_rows, (size_t)total * 3); auto dz = st.out(zone, (size_t)B); auto dso = st.out(south, (size_t)B);
     ST_RUN(gsf_gps_rows_to_utm_batch_dev(ctx, dllh, doff, B, dutm, dz, dso));
 }
 
@@ -639,11 +607,11 @@ int gsf_ransac_poly_batch(gsf_ctx* ctx, const double* t, const double* y, const 
     const int64_t total = offsets[P];
     GSF_REQUIRE(total >= 0 && (total == 0 || (t && y && inlier_mask)) && sample_idx, "bad offsets / NULL arrays");
     const size_t nidx = (size_t)P * (size_t)max_trials * (size_t)min_samples;
-    ST_BEGIN((size_t)total * 17 + (size_t)(P + 1) * 8 + nidx * 4 + (size_t)P * 12, 8);
-    const double* dt = st.in(t, (size_t)total); const double* dy = st.in(y, (size_t)total); const int64_t* doff = st.in(offsets, (size_t)P + 1);
-    const int32_t* didx = st.in(sample_idx, nidx);
-    uint8_t* dmask = st.out(inlier_mask, (size_t)total); int32_t* dnt = st.out(n_trials, (size_t)P); int32_t* dni = st.out(n_inliers, (size_t)P);
-    int32_t* dst_ = st.out(status, (size_t)P);
+    Staging st(ctx);
+    auto dt = st.in(t, (size_t)total); auto dy = st.in(y, (size_t)total); auto doff = st.in(offsets, (size_t)P + 1);
+    auto didx = st.in(sample_idx, nidx);
+    auto dmask = st.out(inlier_mask, (size_t)total); auto dnt = st.out(n_trials, (size_t)P); auto dni = st.out(n_inliers, (size_t)P);
+    auto dst_ = st.out(status, (size_t)P);
     ST_RUN(gsf_ransac_poly_batch_dev(ctx, dt, dy, doff, P, didx, max_trials, min_samples, degree, residual_threshold, stop_probability, dmask, dnt, dni, dst_));
 }
 
@@ -659,15 +627,15 @@ int gsf_pose_query(gsf_ctx* ctx, const double* ts, const double* pos, const doub
     GSF_REQUIRE(total >= 0 && (total == 0 || (ts && pos && quat)), "bad offsets / NULL arrays");
     const size_t P = total > 0 ? (size_t)total : 1, Mq = (size_t)M;      // (no poses at all: one unread row stands in for the arrays)
     const double zero_row[8] = { 0.0 };
-    ST_BEGIN(P * 65 + Mq * 78 + (size_t)(B + 1) * 16 + (size_t)B * 8 + 64, 14);
-    const double* dts = st.in(total > 0 ? ts : zero_row, P); const double* dpos = st.in(total > 0 ? pos : zero_row, P * 3);
-    const double* dquat = st.in(total > 0 ? quat : zero_row, P * 4); const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const int32_t* drs = run_status ? st.in(run_status, (size_t)B) : nullptr;
-    const uint8_t* dpf = (pose_flags && total > 0) ? st.in(pose_flags, P) : nullptr;
-    const double* dqt = st.in(q_t, Mq); const int64_t* dqo = st.in(q_offsets, (size_t)B + 1);
-    double* dop = st.out(out_pos, Mq * 3); double* doq = st.out(out_quat, Mq * 4); uint8_t* dfl = st.out(q_flags, Mq);
-    int32_t* dqi = q_index ? st.out(q_index, Mq) : nullptr; uint8_t* dqp = q_pose_flags ? st.out(q_pose_flags, Mq) : nullptr;
-    int32_t* dst_ = st.out(track_state, (size_t)B);
+    Staging st(ctx);
+    auto dts = st.in(total > 0 ? ts : zero_row, P); auto dpos = st.in(total > 0 ? pos : zero_row, P * 3);
+    auto dquat = st.in(total > 0 ? quat : zero_row, P * 4); auto doff = st.in(offsets, (size_t)B + 1);
+    auto drs = st.in_opt(run_status, (size_t)B);
+    auto dpf = st.in_opt(total > 0 ? pose_flags : nullptr, P);
+    auto dqt = st.in(q_t, Mq); auto dqo = st.in(q_offsets, (size_t)B + 1);
+    auto dop = st.out(out_pos, Mq * 3); auto doq = st.out(out_quat, Mq * 4); auto dfl = st.out(q_flags, Mq);
+    auto dqi = st.out_opt(q_index, Mq); auto dqp = st.out_opt(q_pose_flags, Mq);
+    auto dst_ = st.out(track_state, (size_t)B);
     ST_RUN(gsf_pose_query_dev(ctx, dts, dpos, dquat, doff, drs, dpf, B, dqt, dqo, M, max_gap, dop, doq, dfl, dqi, dqp, dst_));
 }
 
@@ -684,17 +652,17 @@ int gsf_georef_points(gsf_ctx* ctx, const double* ts, const double* pos, const d
     GSF_REQUIRE(total >= 0 && (total == 0 || (ts && pos && quat)), "bad offsets / NULL arrays");
     const size_t P = total > 0 ? (size_t)total : 1, Mq = (size_t)M;
     const double zero_row[8] = { 0.0 };
-    ST_BEGIN(P * 65 + Mq * 70 + (size_t)(B + 1) * 16 + (size_t)B * 72 + 64, 17);
-    const double* dts = st.in(total > 0 ? ts : zero_row, P); const double* dpos = st.in(total > 0 ? pos : zero_row, P * 3);
-    const double* dquat = st.in(total > 0 ? quat : zero_row, P * 4); const int64_t* doff = st.in(offsets, (size_t)B + 1);
-    const int32_t* drs = run_status ? st.in(run_status, (size_t)B) : nullptr;
-    const uint8_t* dpf = (pose_flags && total > 0) ? st.in(pose_flags, P) : nullptr;
-    const double* dqt = st.in(q_t, Mq); const int64_t* dqo = st.in(q_offsets, (size_t)B + 1); const double* dx = st.in(x, Mq * 3);
-    const double* deq = ext_q ? st.in(ext_q, (size_t)B * 4) : nullptr; const double* det = ext_t ? st.in(ext_t, (size_t)B * 3) : nullptr;
-    const double* dsc = scale ? st.in(scale, (size_t)B) : nullptr;
-    double* dxyz = st.out(out_xyz, Mq * 3); uint8_t* dfl = st.out(q_flags, Mq);
-    int32_t* dqi = q_index ? st.out(q_index, Mq) : nullptr; uint8_t* dqp = q_pose_flags ? st.out(q_pose_flags, Mq) : nullptr;
-    int32_t* dst_ = st.out(track_state, (size_t)B);
+    Staging st(ctx);
+    auto dts = st.in(total > 0 ? ts : zero_row, P); auto dpos = st.in(total > 0 ? pos : zero_row, P * 3);
+    auto dquat = st.in(total > 0 ? quat : zero_row, P * 4); auto doff = st.in(offsets, (size_t)B + 1);
+    auto drs = st.in_opt(run_status, (size_t)B);
+    auto dpf = st.in_opt(total > 0 ? pose_flags : nullptr, P);
+    auto dqt = st.in(q_t, Mq); auto dqo = st.in(q_offsets, (size_t)B + 1); auto dx = st.in(x, Mq * 3);
+    auto deq = st.in_opt(ext_q, (size_t)B * 4); auto det = st.in_opt(ext_t, (size_t)B * 3);
+    auto dsc = st.in_opt(scale, (size_t)B);
+    auto dxyz = st.out(out_xyz, Mq * 3); auto dfl = st.out(q_flags, Mq);
+    auto dqi = st.out_opt(q_index, Mq); auto dqp = st.out_opt(q_pose_flags, Mq);
+    auto dst_ = st.out(track_state, (size_t)B);
     ST_RUN(gsf_georef_points_dev(ctx, dts, dpos, dquat, doff, drs, dpf, B, dqt, dqo, M, max_gap, dx, deq, det, dsc, dxyz, dfl, dqi, dqp, dst_));
 }
 

@@ -498,16 +498,11 @@ int gsf_eval_errors_batch(gsf_ctx* ctx, const double* ts, const double* traj_pos
     if (B == 0 || N == 0) return GSF_OK;
     GSF_REQUIRE(ts && traj_pos && aligned_gps && valid && stats, "NULL array");
     const size_t P = (size_t)B * (size_t)N;
-    Staging st(ctx, P * 65 + (size_t)B * 32, 6);
-    if (st.rc()) return st.rc();
-    const double* dts = st.in(ts, P); const double* dp = st.in(traj_pos, P * 3); const double* dg = st.in(aligned_gps, P * 3);
-    const uint8_t* dv = st.in(valid, P);
-    double* dst = st.out(stats, (size_t)B * 4); double* de = st.out(errors, P);
-    int rc = st.upload();
-    if (rc) return rc;
-    rc = gsf_eval_errors_batch_dev(ctx, dts, dp, dg, dv, B, N, skip_seconds, dst, de);
-    if (rc) return rc;
-    return st.finish();
+    Staging st(ctx);
+    auto dts = st.in(ts, P); auto dp = st.in(traj_pos, P * 3); auto dg = st.in(aligned_gps, P * 3);
+    auto dv = st.in(valid, P);
+    auto dst = st.out(stats, (size_t)B * 4); auto de = st.out(errors, P);
+    ST_RUN(gsf_eval_errors_batch_dev(ctx, dts, dp, dg, dv, B, N, skip_seconds, dst, de));
 }
 
 }  // extern "C"

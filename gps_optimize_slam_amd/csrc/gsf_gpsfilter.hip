@@ -931,21 +931,14 @@ int gsf_gps_prefilter_chain(gsf_ctx* ctx, const double* t, const double* pos, co
     if (B == 0) return GSF_OK;
     const int64_t total = offsets[B], nw = win_offsets[B];
     GSF_REQUIRE(total >= 0 && nw >= 0 && (total == 0 || (t && pos)) && (nw == 0 || (win_rows && win_status)), "bad offsets / NULL arrays");
-    Staging st(ctx, (size_t)total * 33 + (size_t)(B + 1) * 16 + (size_t)nw * 12 + (size_t)B * (625 * 8 + 4), 12);
-    if (st.rc()) return st.rc();
-    const double* dt = st.in(t, (size_t)total); const double* dp = st.in(pos, (size_t)total * 3);
-    const int64_t* doff = st.in(offsets, (size_t)B + 1); const int32_t* dwr = st.in(win_rows, (size_t)nw * 2);
-    const int64_t* dwo = st.in(win_offsets, (size_t)B + 1);
-    const uint32_t* dst_in = st.in(mt_state, (size_t)B * 625);
-    uint32_t* dstate = st.out(mt_state, (size_t)B * 625);
-    uint8_t* dkeep = st.out(keep, (size_t)total); int32_t* dws = st.out(win_status, (size_t)nw); int32_t* dls = st.out(log_status, (size_t)B);
-    int rc = st.upload();
-    if (rc) return rc;
-    GSF_HIP(hipMemcpyAsync(dstate, dst_in, (size_t)B * 625 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    rc = gsf_gps_prefilter_chain_dev(ctx, dt, dp, doff, B, dwr, dwo, max_window_rows, max_trials, min_samples, degree, residual_threshold, stop_probability,
-                                     dstate, dkeep, dws, dls);
-    if (rc) return rc;
-    return st.finish();
+    Staging st(ctx);
+    auto dt = st.in(t, (size_t)total); auto dp = st.in(pos, (size_t)total * 3);
+    auto doff = st.in(offsets, (size_t)B + 1); auto dwr = st.in(win_rows, (size_t)nw * 2);
+    auto dwo = st.in(win_offsets, (size_t)B + 1);
+    auto dstate = st.inout(mt_state, (size_t)B * 625);
+    auto dkeep = st.out(keep, (size_t)total); auto dws = st.out(win_status, (size_t)nw); auto dls = st.out(log_status, (size_t)B);
+    ST_RUN(gsf_gps_prefilter_chain_dev(ctx, dt, dp, doff, B, dwr, dwo, max_window_rows, max_trials, min_samples, degree, residual_threshold, stop_probability,
+                                       dstate, dkeep, dws, dls));
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 
 #include "../../include/gsf.h"
 #include "gsf_ekf_core.hpp"
+#include "gsf_stage_plan.hpp"
 
 // The grow-only device workspaces of a context, one slot each.  They are separate allocations because a slot may grow (free + malloc) while a
 // caller further up the chain still holds pointers into another one; no two of them may be merged.
@@ -166,27 +167,41 @@ int launch_mt_tape(gsf_ctx* ctx, uint32_t* state, const int32_t* counts, int64_t
 // inputs of a call are packed into the mirror and cross PCIe in one hipMemcpyAsync, the outputs come back in one, and no call
 // pays hipMalloc/hipFree (which synchronise the device).  Calls whose arrays exceed PINNED_MAX copy straight from/to the caller's
 // pageable arrays instead (a bulk transfer, where the extra host memcpy would cost more than the runtime's own staging).
-// Order of use: every in() before the first out()/tmp(); upload(); launches; finish().
+// Declare, then commit: an entry declares its arrays (in any order) and gets a handle for each; upload() lays the arena out from what was
+// declared (stage_plan, gsf_stage_plan.hpp), grows it, packs and sends the inputs, and a handle converts to its device pointer only after
+// that: nothing is sized by hand.  The host arrays an entry declares are read in upload(), so they must live until then.
+//   in / out: a caller's array of n elements; a NULL host pointer still gets a device block (an input that is not copied in, an output that is
+//   scratch and not copied back).  in_opt / out_opt: a NULL host pointer gives a NULL device pointer.  tmp: scratch.  inout: staged as an input
+//   and as an output, upload() copies the one onto the other on the device; the handle is the output's.  bind: upload() writes the handle's
+//   device pointer into a field (entries that hand a struct of pointers on).
+// Order of use: declarations; upload(); launches; finish().  A full table makes upload() fail with GSF_ERR_INVALID_ARG.
 class Staging {
 public:
     static constexpr size_t PINNED_MAX = (size_t)32 << 20;
-    Staging(gsf_ctx* ctx, size_t payload_bytes, int n_arrays);
-    int rc() const { return rc_; }
-    template <class T> T* in(const T* host, size_t n) { return (T*)in_bytes(host, n * sizeof(T)); }
-    template <class T> T* out(T* host, size_t n) { return (T*)out_bytes(host, n * sizeof(T)); }
-    template <class T> T* tmp(size_t n) { return (T*)out_bytes(nullptr, n * sizeof(T)); }
-    int upload();
+    template <class T> struct Handle {
+        const Staging* st = nullptr; int idx = -1;
+        operator T*() const { return idx < 0 ? nullptr : (T*)(st->d_ + st->tab_.b[idx].off); }
+    };
+    explicit Staging(gsf_ctx* ctx) : ctx_(ctx) {}
+    template <class T> Handle<const T> in(const T* host, size_t n) { return { this, add((void*)host, n * sizeof(T), STAGE_IN) }; }
+    template <class T> Handle<const T> in_opt(const T* host, size_t n) { return host ? in(host, n) : Handle<const T>{}; }
+    template <class T> Handle<T> out(T* host, size_t n) { return { this, add(host, n * sizeof(T), STAGE_OUT) }; }
+    template <class T> Handle<T> out_opt(T* host, size_t n) { return host ? out(host, n) : Handle<T>{}; }
+    template <class T> Handle<T> tmp(size_t n) { return { this, add(nullptr, n * sizeof(T), STAGE_TMP) }; }
+    template <class T> Handle<T> inout(T* host, size_t n) { return { this, add(host, n * sizeof(T), STAGE_OUT, add(host, n * sizeof(T), STAGE_IN)) }; }
+    template <class T> void bind(T*& field, Handle<T> h) { if (h.idx >= 0) bind_[h.idx] = (void**)&field; else field = nullptr; }
+    int upload();      // lay out, grow, pack, one H2D (+ the in-out copies); handles are valid afterwards
     int finish();      // device -> caller arrays, then hipStreamSynchronize
 
 private:
-    struct Out { void* host; size_t off, bytes; };
-    static constexpr int MAX_OUT = 32;
-    void* take(size_t bytes, size_t& at);
-    void* in_bytes(const void* host, size_t bytes);
-    void* out_bytes(void* host, size_t bytes);
-    gsf_ctx* ctx_; char* d_ = nullptr; char* h_ = nullptr; size_t cap_ = 0, off_ = 0, in_end_ = 0, out_lo_ = 0; bool direct_ = false, has_out_ = false;
-    int rc_ = GSF_OK; Out outs_[MAX_OUT]; int n_out_ = 0;
+    int add(void* host, size_t bytes, int kind, int from = -1);   // from: the block that upload() copies onto this one (inout)
+    gsf_ctx* ctx_; char* d_ = nullptr; char* h_ = nullptr; bool direct_ = false; int rc_ = GSF_OK;
+    StageTable tab_; StagePlan plan_{}; void* host_[STAGE_MAX_BLOCKS]; void** bind_[STAGE_MAX_BLOCKS]; int from_[STAGE_MAX_BLOCKS];
 };
+
+// host-pointer forms: declare -> upload (pack, one H2D) -> *_dev launch -> finish (one D2H, synchronise)
+#define ST_UPLOAD() do { int rc__ = st.upload(); if (rc__) return rc__; } while (0)
+#define ST_RUN(call) do { ST_UPLOAD(); int rc__ = (call); if (rc__) return rc__; return st.finish(); } while (0)
 
 int launch_transpose_set(gsf_ctx* ctx, bool to_time, int n, const void* const* src, void* const* dst, const int* C, const int* elem_bytes, int64_t B, int64_t N);
 }  // namespace gsf

@@ -309,50 +309,28 @@ int run_fusion_ragged_dev(gsf_ctx* ctx, const RunIO& io)
 }
 
 // the host-pointer entries: h holds host pointers (checked by the entry); one staged upload, `dev` on the device copies, one download.
-// The arena is sized from the list of arrays below, walked twice: once to add up the bytes, once to stage them
+// d starts as a copy of h; every array in the list below is declared to the staging and its field of d bound to the device copy
 int run_staged(gsf_ctx* ctx, const RunIO& h, int (*dev)(gsf_ctx*, const RunIO&))
 {
     const bool ragged = h.slam_offsets != nullptr, gt = h.gt.offsets != nullptr;
     const size_t nb = (size_t)h.B, P = (size_t)h.total_poses, T = (size_t)h.gps.total, Tg = (size_t)h.gt.total;
-    Staging* st = nullptr;
-    size_t bytes = 0; int n = 0;
-    auto in = [&](auto* host, size_t count, bool want = true) -> decltype(host) {
-        if (!want) return nullptr;
-        if (!st) { bytes += count * sizeof(*host); ++n; return nullptr; }
-        return st->in(host, count);
-    };
-    auto out = [&](auto* host, size_t count, bool want = true) -> decltype(host) {
-        if (!want) return nullptr;
-        if (!st) { bytes += count * sizeof(*host); ++n; return nullptr; }
-        return st->out(host, count);
-    };
+    Staging st(ctx);
     RunIO d = h;
-    const uint32_t* state_in = nullptr;
-    auto arrays = [&]() {
-        d.ts = in(h.ts, P); d.pos = in(h.pos, P * 3); d.quat = in(h.quat, P * 4); d.slam_offsets = in(h.slam_offsets, nb + 1, ragged);
-        d.gps.t = in(h.gps.t, T); d.gps.llh = in(h.gps.llh, T * 3); d.gps.offsets = in(h.gps.offsets, nb + 1);
-        d.gt.t = in(h.gt.t, Tg, gt); d.gt.llh = in(h.gt.llh, Tg * 3, gt); d.gt.offsets = in(h.gt.offsets, nb + 1, gt);
-        state_in = in((const uint32_t*)h.mt_state, nb * 625);
-        d.mt_state = out(h.mt_state, nb * 625);
-        d.R = out(h.R, nb * 9); d.t = out(h.t, nb * 3); d.s = out(h.s, nb); d.pos_out = out(h.pos_out, P * 3); d.quat_out = out(h.quat_out, P * 4);
-        d.status = out(h.status, nb); d.n_inliers = out(h.n_inliers, nb); d.gps.zone = out(h.gps.zone, nb); d.gps.south = out(h.gps.south, nb);
-        d.gps.utm = out(h.gps.utm, T * 3); d.gps.keep = out(h.gps.keep, T); d.aligned = out(h.aligned, P * 3); d.valid = out(h.valid, P);
-        d.sim3_pos = out(h.sim3_pos, P * 3, h.sim3_pos != nullptr);
-        d.gt.zone = out(h.gt.zone, nb, gt); d.gt.south = out(h.gt.south, nb, gt); d.gt.utm = out(h.gt.utm, Tg * 3, gt); d.gt.keep = out(h.gt.keep, Tg, gt);
-        d.gt_aligned = out(h.gt_aligned, P * 3, gt); d.gt_valid = out(h.gt_valid, P, gt);
-        d.err_stats = out(h.err_stats, nb * (ragged ? 24 : 12)); d.plot_ref = out(h.plot_ref, nb, h.plot_ref != nullptr); d.run_status = out(h.run_status, nb);
-        d.inlier_mask = out(h.inlier_mask, P, h.inlier_mask != nullptr); d.trial_info = out(h.trial_info, nb * 2, h.trial_info != nullptr);
-    };
-    arrays();
-    Staging staging(ctx, bytes, n);
-    if (staging.rc()) return staging.rc();
-    st = &staging;
-    arrays();
-    int rc = staging.upload();
-    if (rc) return rc;
-    GSF_HIP(hipMemcpyAsync(d.mt_state, state_in, nb * 625 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    if ((rc = dev(ctx, d))) return rc;
-    return staging.finish();
+    auto in = [&](auto*& p, size_t count, bool want = true) { if (want) st.bind(p, st.in(p, count)); else p = nullptr; };
+    auto out = [&](auto*& p, size_t count, bool want = true) { if (want) st.bind(p, st.out(p, count)); else p = nullptr; };
+    in(d.ts, P); in(d.pos, P * 3); in(d.quat, P * 4); in(d.slam_offsets, nb + 1, ragged);
+    in(d.gps.t, T); in(d.gps.llh, T * 3); in(d.gps.offsets, nb + 1);
+    in(d.gt.t, Tg, gt); in(d.gt.llh, Tg * 3, gt); in(d.gt.offsets, nb + 1, gt);
+    st.bind(d.mt_state, st.inout(d.mt_state, nb * 625));
+    out(d.R, nb * 9); out(d.t, nb * 3); out(d.s, nb); out(d.pos_out, P * 3); out(d.quat_out, P * 4);
+    out(d.status, nb); out(d.n_inliers, nb); out(d.gps.zone, nb); out(d.gps.south, nb);
+    out(d.gps.utm, T * 3); out(d.gps.keep, T); out(d.aligned, P * 3); out(d.valid, P);
+    out(d.sim3_pos, P * 3, h.sim3_pos != nullptr);
+    out(d.gt.zone, nb, gt); out(d.gt.south, nb, gt); out(d.gt.utm, Tg * 3, gt); out(d.gt.keep, Tg, gt);
+    out(d.gt_aligned, P * 3, gt); out(d.gt_valid, P, gt);
+    out(d.err_stats, nb * (ragged ? 24 : 12)); out(d.plot_ref, nb, h.plot_ref != nullptr); out(d.run_status, nb);
+    out(d.inlier_mask, P, h.inlier_mask != nullptr); out(d.trial_info, nb * 2, h.trial_info != nullptr);
+    ST_RUN(dev(ctx, d));
 }
 
 }  // namespace
