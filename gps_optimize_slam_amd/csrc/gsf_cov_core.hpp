@@ -59,13 +59,13 @@ GSF_HD OutageMasks outage_masks(cov_mask act, cov_mask av, bool first_chunk, boo
 
 // The outage that the recovery at lane r of the chunk closes.  start: OutageMasks::start; sharp_pairs: lanes of OutageMasks::pair whose
 // pair exceeds the yaw-rate threshold; c0: index of lane 0's pose; ostart / seg_sharp: the open outage carried in (used if no outage
-// starts before r in this chunk).
+// starts before r in this chunk); neg_thr: the threshold is negative, so the maximum rate of :813 -- 0 where no pair was evaluated -- exceeds it.
 struct OutageSeg {
     int start_lane;                // first lane of the outage, -1: it began in an earlier chunk, at pose `first`
     int64_t first;                 // index of its first pose (a)
-    bool sharp;                    // judged a sharp turn: >= 2 poses and a pair above the threshold (:882-889)
+    bool sharp;                    // judged a sharp turn: >= 2 poses and a pair above the threshold, or a negative threshold (:882-889, :826)
 };
-GSF_HD OutageSeg outage_closed_at(cov_mask start, cov_mask sharp_pairs, int r, int64_t c0, int64_t ostart, bool seg_sharp)
+GSF_HD OutageSeg outage_closed_at(cov_mask start, cov_mask sharp_pairs, int r, int64_t c0, int64_t ostart, bool seg_sharp, bool neg_thr = false)
 {
     OutageSeg o;
     const cov_mask sm = start & cov_bits(0, r - 1);
@@ -79,7 +79,7 @@ GSF_HD OutageSeg outage_closed_at(cov_mask start, cov_mask sharp_pairs, int r, i
         o.first = ostart;
         seg = seg_sharp || (sharp_pairs & cov_bits(0, r - 1)) != 0ull;
     }
-    o.sharp = (c0 + r - o.first >= 2) && seg;
+    o.sharp = (c0 + r - o.first >= 2) && (seg || neg_thr);
     return o;
 }
 

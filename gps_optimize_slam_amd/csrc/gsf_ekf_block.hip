@@ -229,7 +229,7 @@ struct Chunk {
                 s_glob = c_ostart;
                 seg = c_seg_sharp || (f_mask & bits(0, lane - 1)) != 0ull;
             }
-            sharp = (i - s_glob >= 2) && seg;
+            sharp = (i - s_glob >= 2) && (seg || cfg.yaw_thr_rad < 0.0);   // (:813, :826: a negative threshold needs no evaluated pair)
         }
         const u64 sharp_mask = __ballot(sharp);
         rts_mask = rec_mask & ~sharp_mask;                               // recoveries that run the RTS back-pass

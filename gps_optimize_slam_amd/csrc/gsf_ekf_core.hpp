@@ -18,8 +18,11 @@
 //    back-pass re-reads the already-written output rows (they hold x_f) and rebuilds
 //    P_p[k] = P_p[k+1] - Q*dt[k+1] on the way down (<=1 ulp per step; gate 1e-6 m).
 //  * The sharp-turn gate is accumulated forward during the outage.  max|dyaw|/dt > thr is
-//    evaluated per pair as cos(dyaw) < cos(thr*dt) with cos(dyaw) from the two headings'
-//    (cos,sin) -- one cos() per pair instead of three atan2 + sin + cos.
+//    evaluated per pair from the dot and cross products of the two heading vectors against
+//    sin(thr*dt) / cos(thr*dt) -- no angle is formed (yaw_rate_exceeds_body below).
+//    Domain (DESIGN.md "K4"): thr < 0 -- every outage of >= 2 poses is a sharp turn, whether or
+//    not a pair was evaluated (:813, :826); thr*dt >= pi -- the pair never exceeds; between, the
+//    pair is decided like the reference's atan2 form down to thr*dt = 1e-7.
 #pragma once
 #include "gsf_math.hpp"
 
@@ -65,49 +68,57 @@ GSF_HD void yaw_vec(const Quat& q, double& a, double& b)
     b = -2.0 * (q.x * q.y - q.z * q.w);                      // -m01
 }
 
-// |wrap(yaw2 - yaw1)| / dt > thr  (ref :819-826), without forming the angles:
-//   |wrap(d)| > c  <=>  cos(d) < cos(c)  for c in [0, pi);  never for c >= pi.
-// atan2(0,0) = 0 in the reference, i.e. a degenerate heading vector counts as (1, 0).
-GSF_HD_COLD bool yaw_rate_exceeds(Quat r1, Quat r2, double dt, double thr)   // by value: by-reference args of a noinline call live in scratch
+// sin(c) for 0 <= c <= 0.785: the kernel polynomial of fdlibm's sin (degree 13, odd), whose approximation error on |c| <= pi/4 is below
+// 2^-58 relative; as evaluated here the result is within 1 ulp of sin(c) (tests/test_sharp_turn_gate_host.py sweeps it against a 50-digit
+// sine: 0.7 ulp at most)
+GSF_HD double gate_sin_poly(double c)
 {
-    double a1, b1, a2, b2;
-    yaw_vec(r1, a1, b1); yaw_vec(r2, a2, b2);
-    double h1 = a1 * a1 + b1 * b1, h2 = a2 * a2 + b2 * b2;
-    if (!(h1 > 0.0)) { a1 = 1.0; b1 = 0.0; h1 = 1.0; }
-    if (!(h2 > 0.0)) { a2 = 1.0; b2 = 0.0; h2 = 1.0; }
-    double c = thr * dt;
-    if (!(c < 3.141592653589793)) return false;
-    if (c < 0.0) return true;                                // any rate >= 0 exceeds a negative threshold
-    double cosd = (a1 * a2 + b1 * b2) * fast_rsqrt(h1 * h2);
-    return cosd < cos(c);
+    const double z = c * c;
+    const double r = 8.33333333332248946124e-03 + z * (-1.98412698298579493134e-04 + z * (2.75573137070700676789e-06 +
+                     z * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10)));
+    return c + (z * c) * (-1.66666666666666324348e-01 + z * r);
 }
 
-// The same test without a libm call on the usual range (c = thr dt <= pi/4: degree-14 kernel polynomial of cos) -- for the wave
-// kernels, where the cold blocks of a launch start with a cold instruction cache: the call into yaw_rate_exceeds and on into
-// libm's cos costs ~1 us of instruction-fetch misses per wave that meets an outage, and at small batches the slowest wave IS the
-// launch time.  Two wrappers around one body: a CALL for big batches (inlined it costs the hot loop 27 registers, i.e. one wave
-// per SIMD) and an INLINE form for small batches, where registers are free and even the one far call is worth avoiding.
+// |wrap(yaw2 - yaw1)| / dt > thr  (ref :819-826), without forming the angles.  With d = wrap(yaw2 - yaw1), c = thr dt and the two heading
+// vectors v1, v2 (lengths^2 h1, h2):  dot = v1.v2 = sqrt(h1 h2) cos d,  cross = v1 x v2 = sqrt(h1 h2) sin d, and
+//   c < 0:         always (any rate >= 0 exceeds a negative threshold);       c >= pi:  never (|d| <= pi);
+//   0 <= c <= 0.785:  |d| > c  <=>  dot <= 0  or  cross^2 > sin^2(c) h1 h2       (|d| >= pi/2 > c, or sin is increasing on [0, pi/2])
+//   0.785 < c < pi:   |d| > c  <=>  cos d < cos c, as squares with the signs of dot and cos c taken apart.
+// The sine form keeps the RELATIVE accuracy of a small angle (cross is a difference of two products of size h, so its error is
+// ~1e-16 / c relative: 1e-9 at c = 1e-7), where cos(d) < cos(c) loses the decision once 1 - cos c ~ c^2 / 2 falls under the rounding of
+// cos d (c ~ 1e-5).  No rsqrt, no division; sin(c) from the polynomial above, so libm (cos) is called for c > 0.785 only: the cold blocks
+// of a wave-kernel launch start with a cold instruction cache, and a call on into libm costs ~1 us of instruction-fetch misses per wave
+// that meets an outage.  cross is formed WITHOUT fma contraction: two bit-equal poses must give exactly 0 (a pose logged twice, thr = 0).
+// atan2(0,0) = 0 in the reference, i.e. a degenerate heading vector counts as (1, 0).
+// The gate's domain is stated in DESIGN.md "K4": every pair whose rate differs from the threshold by more than the reference's own float64
+// error (a few ulp of the yaw angles) is decided like the reference, for thr dt from 1e-7 up.
+// ONE body behind three names: yaw_rate_exceeds / yaw_rate_exceeds_poly are CALLS (the sequential kernel and the big-batch wave kernels:
+// inlined it costs the hot loop its registers, i.e. one wave per SIMD), yaw_rate_exceeds_body the INLINE form for small batches, where
+// registers are free and even the one far call is worth avoiding.
 GSF_HD bool yaw_rate_exceeds_body(const Quat& r1, const Quat& r2, double dt, double thr)
 {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     double a1, b1, a2, b2;
     yaw_vec(r1, a1, b1); yaw_vec(r2, a2, b2);
     double h1 = a1 * a1 + b1 * b1, h2 = a2 * a2 + b2 * b2;
     if (!(h1 > 0.0)) { a1 = 1.0; b1 = 0.0; h1 = 1.0; }
     if (!(h2 > 0.0)) { a2 = 1.0; b2 = 0.0; h2 = 1.0; }
     const double c = thr * dt;
-    const double cosd = (a1 * a2 + b1 * b2) * fast_rsqrt(h1 * h2);
-    double cc;
+    const double dot = a1 * a2 + b1 * b2, cross = a1 * b2 - b1 * a2, hh = h1 * h2;
+    bool exceeds;
     if (c <= 0.785) {
-        const double z = c * c;
-        const double pc = 4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * (2.48015872894767294178e-05 +
-                          z * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11))));
-        cc = fma(z * z, pc, fma(-0.5, z, 1.0));
+        const double s = gate_sin_poly(c);
+        exceeds = !(dot > 0.0) || cross * cross > (s * s) * hh;
     } else {
-        cc = cos(c);
+        const double cc = cos(c);
+        const double lhs = dot * dot, rhs = (cc * cc) * hh;
+        exceeds = (cc > 0.0) ? (!(dot > 0.0) || lhs < rhs) : (dot < 0.0 && lhs > rhs);
     }
-    const bool exceeds = cosd < cc;
     return (c < 0.0) ? true : ((c < 3.141592653589793) ? exceeds : false);
 }
+GSF_HD_COLD bool yaw_rate_exceeds(Quat r1, Quat r2, double dt, double thr) { return yaw_rate_exceeds_body(r1, r2, dt, thr); }   // by value: by-reference args of a noinline call live in scratch
 GSF_HD_COLD bool yaw_rate_exceeds_poly(Quat r1, Quat r2, double dt, double thr) { return yaw_rate_exceeds_body(r1, r2, dt, thr); }
 
 // Out must provide:
@@ -190,7 +201,7 @@ struct EkfTraj {
                 if (t > t_prev && !seg_sharp)                            // :817
                     seg_sharp = !both_ok || yaw_rate_exceeds(r_prev, r_cur, t - t_prev, cfg.yaw_thr_rad);   // :821-824
             } else if (avail && was_outage) {                            // recovery, ref :879-928
-                const bool sharp = (i - ostart >= 2) && seg_sharp;       // :882-894
+                const bool sharp = (i - ostart >= 2) && (seg_sharp || cfg.yaw_thr_rad < 0.0);   // :882-894; :813, :826: max rate 0 > thr < 0 with no pair evaluated
                 if (sharp) {
                     status |= ST_SHARP_TURN;
                     const int eff = cfg.sharp_turn_steps;                // :889

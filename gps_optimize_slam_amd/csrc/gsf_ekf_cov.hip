@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void ekf_cov_kernel(const CovArgs a, const EkfC
         double Po[3] = { Pf[0], Pf[1], Pf[2] };
         for (u64 rm = om.rec; rm != 0ull; rm &= rm - 1ull) {
             const int r = __builtin_ctzll(rm);
-            const OutageSeg sg = outage_closed_at(om.start, f_mask, r, c0, oc.ostart, oc.seg_sharp);
+            const OutageSeg sg = outage_closed_at(om.start, f_mask, r, c0, oc.ostart, oc.seg_sharp, cfg.yaw_thr_rad < 0.0);
             status |= sg.sharp ? ST_SHARP_TURN : ST_RTS_APPLIED;
             const int mark = POSE_IN_OUTAGE | (sg.sharp ? POSE_SHARP_TURN : POSE_SMOOTHED);
             const double Ppb[3] = { lane_bcast(Pm[0], r), lane_bcast(Pm[1], r), lane_bcast(Pm[2], r) };

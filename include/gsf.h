@@ -61,7 +61,11 @@ typedef enum {
    Inside it every route -- wave, two-wave, big-batch, early-variance, block, lane kernel, the covariance entry -- agrees with the oracle to
    the stated gates (1e-6 m, status words exact; variances 1e-10 relative): tests/test_ekf_noise_domain.py.  The scan-based routes scale
    every step matrix of their variance scans by a power of two, so the range does not depend on how Q dt and R compare or on the time unit
-   of the stamps.  Outside the range the behaviour is undocumented. */
+   of the stamps.  Outside the range the behaviour is undocumented.
+   The sharp-turn threshold thr (rad/s after deg2rad), with dt the step between two poses of an outage: thr < 0 makes every outage of two or
+   more poses a sharp turn (no RTS), also one whose stamps all repeat (:813, :826); thr dt >= pi can never be exceeded; between, every route
+   decides a pair like the reference's atan2 form down to thr dt = 1e-7, unless its rate is closer to thr than the float64 error of the yaw
+   angles themselves ("Domain of the sharp-turn gate"; tests/test_sharp_turn_gate.py). */
 typedef struct {
     double initial_cov_diag[7];        /* :25 */
     double process_noise_diag[7];      /* :26  per second, used as variances */

@@ -46,6 +46,20 @@ int hh_ekf_fuse(const double* ts, const double* pos, const double* quat, const d
     return f.finish();
 }
 
+// The sharp-turn gate on n pairs: q1, q2 (n,4) raw quaternions, made unit as the kernels make them (quat_unit) before the call.
+// out[i]: bit 0 = yaw_rate_exceeds, bit 1 = yaw_rate_exceeds_body, bit 2 = a quaternion is invalid (the callers then count the pair as sharp)
+void hh_yaw_gate(const double* q1, const double* q2, const double* dt, const double* thr, int64_t n, uint8_t* out)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        Quat r1, r2;
+        const bool ok1 = quat_unit(Quat{ q1[i * 4], q1[i * 4 + 1], q1[i * 4 + 2], q1[i * 4 + 3] }, r1);
+        const bool ok2 = quat_unit(Quat{ q2[i * 4], q2[i * 4 + 1], q2[i * 4 + 2], q2[i * 4 + 3] }, r2);
+        out[i] = (uint8_t)((yaw_rate_exceeds(r1, r2, dt[i], thr[i]) ? 1 : 0) | (yaw_rate_exceeds_body(r1, r2, dt[i], thr[i]) ? 2 : 0) | ((ok1 && ok2) ? 0 : 4));
+    }
+}
+// the gate's polynomial sine (0 <= c <= 0.785)
+void hh_gate_sin_poly(const double* c, int64_t n, double* s) { for (int64_t i = 0; i < n; ++i) s[i] = gate_sin_poly(c[i]); }
+
 static int umeyama_impl(const double* src, const double* dst, int64_t n, double* R, double* t, double* s, bool polar)
 {
     if (n < 3) return SIM3_NONE;

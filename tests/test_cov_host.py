@@ -31,10 +31,15 @@ def yaw_of(q):
 
 
 def max_yaw_rate(ts, quat, a, b):
-    """is_sharp_turn_in_segment's max_observed_yaw_rate over the poses a..b-1 (:813-824)"""
+    """is_sharp_turn_in_segment's max_observed_yaw_rate over the poses a..b-1 (:813-824): 0.0 where :817 skips every pair -- which :826
+    still compares with the threshold, so that a NEGATIVE threshold makes every outage of >= 2 poses sharp, repeated stamps or not; inf
+    where an evaluated pair holds a quaternion Rotation.from_quat refuses (:821 returns True whatever the threshold)"""
     rate = 0.0
     for k in range(a + 1, b):
         if ts[k] > ts[k - 1]:
+            n1, n2 = np.linalg.norm(quat[k - 1]), np.linalg.norm(quat[k])
+            if not (np.isfinite(n1) and np.isfinite(n2) and n1 > 0.0 and n2 > 0.0):
+                return np.inf
             d = yaw_of(quat[k]) - yaw_of(quat[k - 1])
             rate = max(rate, abs(np.arctan2(np.sin(d), np.cos(d)) / (ts[k] - ts[k - 1])))
     return rate
@@ -72,7 +77,7 @@ def restate(ts, quat, aligned, valid, cfg):
             if i - start >= 2:                                          # :882
                 rate = max_yaw_rate(ts, quat, start, i)
                 rates.append((rate, thr))
-                is_sharp = rate > thr
+                is_sharp = rate > thr                                   # :826 (rate 0.0 with no pair evaluated: sharp iff thr < 0)
             if is_sharp:
                 sharp.append((start, i)); status |= ST_SHARP
                 flags[start:i] |= SHARP_TURN
