@@ -227,17 +227,6 @@ __global__ __launch_bounds__(64, OCC) void fuse_pipeline_kernel(const double* __
     if (status) status[b] = f.finish() | (fit << 8);
 }
 
-EkfConfig to_core(const gsf_ekf_config* c)
-{
-    EkfConfig k;
-    for (int i = 0; i < 7; ++i) { k.P0[i] = c->initial_cov_diag[i]; k.Qps[i] = c->process_noise_diag[i]; }
-    for (int i = 0; i < 3; ++i) k.Rm[i] = c->meas_noise_diag[i];
-    k.yaw_thr_rad = c->sharp_turn_yaw_rate_threshold_deg_per_sec * (M_PI / 180.0);     // np.deg2rad, ref :886
-    k.sharp_turn_steps = c->default_ekf_transition_steps_on_sharp_turn;
-    k._pad = 0;
-    return k;
-}
-
 }  // namespace
 
 // A time-major batch with fewer trajectories than ctx->lane_min_traj cannot fill the chip with one lane per trajectory (64 tracks per

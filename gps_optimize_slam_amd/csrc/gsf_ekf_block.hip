@@ -578,58 +578,37 @@ __global__ __launch_bounds__(MAXT, OCC) void ekf_block_kernel(WaveArgs a, EkfCon
     c1.finish(k, sh, p0);
 }
 
-EkfConfig to_core_block(const gsf_ekf_config* c)
-{
-    EkfConfig k;
-    for (int i = 0; i < 7; ++i) { k.P0[i] = c->initial_cov_diag[i]; k.Qps[i] = c->process_noise_diag[i]; }
-    for (int i = 0; i < 3; ++i) k.Rm[i] = c->meas_noise_diag[i];
-    k.yaw_thr_rad = c->sharp_turn_yaw_rate_threshold_deg_per_sec * (M_PI / 180.0);
-    k.sharp_turn_steps = c->default_ekf_transition_steps_on_sharp_turn;
-    k._pad = 0;
-    return k;
-}
-
 }  // namespace
 
 namespace gsf {
 
-bool ekf_block_applies(int64_t N, const int64_t* offsets) { return !offsets && N > 64 && N <= 1024; }
-
-int launch_ekf_block(gsf_ctx* ctx, bool pipeline, const double* ts, const double* pos, const double* quat, const double* gps,
-                     const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B,
-                     int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status)
+// wave_route()'s BLOCK: trajectory-major layout, one N for the batch, 64 < N <= 1024
+int launch_ekf_block(gsf_ctx* ctx, const WaveRoute& r, const WaveArgs& a, const EkfConfig& k)
 {
-    GSF_REQUIRE(B <= 0x7fffffff && ekf_block_applies(N, nullptr), "launch_ekf_block: needs 64 < N <= 1024");
-    WaveArgs a{ ts, pos, quat, gps, valid, init_pos, init_quat, R, t, s, pos_out, quat_out, status, B, N, nullptr, FitRows{ 0, 0, 0.0, 0.0 } };
-    const EkfConfig k = to_core_block(cfg);
-    const bool xy = k.P0[1] == k.P0[0] && k.Qps[1] == k.Qps[0] && k.Rm[1] == k.Rm[0] &&
-                    !(k.P0[2] == k.P0[0] && k.Qps[2] == k.Qps[0] && k.Rm[2] == k.Rm[0]);
-    const int W = (int)((N + 63) / 64);
+    const int64_t B = a.B, N = a.N;                                      // (B fits a grid: launch_ekf_wave has checked)
+    WaveArgs wa = a; wa.offsets = nullptr; wa.rows = FitRows{ 0, 0, 0.0, 0.0 };   // the row choice comes as a mask (below), not as a rule
+    const int W = r.nch;                                                  // one wave per chunk
     const dim3 grid((unsigned)B), block((unsigned)(W * 64));
     // the fit under the reference's row choice (gsf_set_sim3_rows mode 1, ref :973-998): the rows are marked by a launch of their own (the
     // rule is a serial walk over the valid rows of a track; here every chunk has its own wave) and the moments take the marked rows only
     const uint8_t* rowsel = nullptr; const int32_t* rows_status = nullptr;
-    if (pipeline && ctx->fit_rows.mode != 0) {
+    if (r.pipeline && ctx->fit_rows.mode != 0) {
         const size_t P = (size_t)B * (size_t)N, o_st = (P + 255) & ~(size_t)255, o_n = o_st + (((size_t)B * 4 + 255) & ~(size_t)255);
         int rc = ensure_workspace(ctx, GSF_WS_ROWS, o_n + (size_t)B * 4);
         if (rc) return rc;
         char* w = workspace(ctx, GSF_WS_ROWS);
-        if ((rc = launch_sim3_rows(ctx, ts, gps, valid, nullptr, B, N, ctx->fit_rows, (uint8_t*)w, (int32_t*)(w + o_n), (int32_t*)(w + o_st)))) return rc;
+        if ((rc = launch_sim3_rows(ctx, a.ts, a.gps, a.valid, nullptr, B, N, ctx->fit_rows, (uint8_t*)w, (int32_t*)(w + o_n), (int32_t*)(w + o_st)))) return rc;
         rowsel = (const uint8_t*)w; rows_status = (const int32_t*)(w + o_st);
     }
-#define GSF_LAUNCH_BLOCK(P_, X_, T_, O_, I_) hipLaunchKernelGGL((ekf_block_kernel<P_, X_, T_, O_, I_>), grid, block, 0, ctx->stream, a, k, rowsel, rows_status)
-#define GSF_LAUNCH_BLOCK_T(P_, X_) do { \
-        if (W <= 5) GSF_LAUNCH_BLOCK(P_, X_, 320, 5, true); \
-        else if (W <= 8) GSF_LAUNCH_BLOCK(P_, X_, 512, 4, true); \
-        else GSF_LAUNCH_BLOCK(P_, X_, 1024, 4, false); } while (0)
-    if (pipeline) { if (xy) GSF_LAUNCH_BLOCK_T(true, 1); else GSF_LAUNCH_BLOCK_T(true, 0); }
-    else { if (xy) GSF_LAUNCH_BLOCK_T(false, 1); else GSF_LAUNCH_BLOCK_T(false, 0); }
-#undef GSF_LAUNCH_BLOCK_T
-#undef GSF_LAUNCH_BLOCK
+    // up to 5 | 8 | 16 waves: MAXT threads at most, 5 | 4 | 4 waves per SIMD, cold blocks inlined up to 8 waves
+    wave_lift<1, 0>(r.pipeline, [&](auto p) { wave_lift<1, 0>(r.xy, [&](auto x) { wave_lift<320, 512, 1024>(W <= 5 ? 320 : (W <= 8 ? 512 : 1024), [&](auto mt) {
+        constexpr int MAXT = decltype(mt)::value;
+        hipLaunchKernelGGL((ekf_block_kernel<decltype(p)::value != 0, decltype(x)::value, MAXT, MAXT == 320 ? 5 : 4, MAXT != 1024>), grid, block, 0,
+                           ctx->stream, wa, k, rowsel, rows_status); }); }); });
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }
 
-}  // namespace gsf
+const char* wave_block_build_info() { return GSF_TU_BUILD_INFO("gsf_ekf_block.hip"); }
 
-namespace gsf { const char* wave_block_build_info() { return GSF_TU_BUILD_INFO("gsf_ekf_block.hip"); } }
+}  // namespace gsf

@@ -57,14 +57,6 @@ GSF_WAVE_TAIL_KERNEL(WAVE_TAIL_FULL)
 // mostly idle -- wave 1 computes the variances of EVERY chunk (they depend on stamps and availability only, not on the fit) into
 // LDS; after one block barrier wave 0 runs the chunk loop without its two Moebius scans (-28 % instructions per chunk).
 // Same functions, same operands, same order as the one-wave kernel: bit-identical results.
-// Where the early-variance build is taken without being asked for: 1 000..1 024 tracks of 256..384 poses.  The bounds come from a sweep
-// of plain bench runs with the option at 0 and at 1 (HISTORY.md, "Early variances", holds every figure): below 1 000 tracks nothing was
-// gained (the launch does not fill the chip and does not end with a wave that gained); at 1 000 tracks lengths below 256 poses gained
-// 0.05-0.13 us, at or inside the run-to-run spread; 1 000 and 1 024 tracks gained 0.17-0.55 us over 256..384 poses; 1 536 tracks gained at
-// 271 poses but were measured at that length only.  Everything outside the measured wins stays on the one-wave kernel.
-#ifndef GSF_EARLY_AUTO_RULE
-#define GSF_EARLY_AUTO_RULE(B_, N_) ((B_) >= 1000 && (B_) <= 1024 && (N_) >= 256 && (N_) <= 384)
-#endif
 #ifndef GSF_DUO_ROLE_SHIFT
 #define GSF_DUO_ROLE_SHIFT 2        // measured best of 0..3 at 1 000 tracks (22.6 vs 23.1-23.2 us; 23.6 us without the helper)
 #endif
@@ -95,74 +87,42 @@ __global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgsTail<5> w, Ek
 template <bool PIPELINE, int AXMODE>
 __global__ __launch_bounds__(128) void ekf_wave_duo_kernel(WaveArgsTail<WAVE_TAIL_FULL> w, EkfConfig cfg, int pv_stride) { wave_duo_body<PIPELINE, AXMODE, WAVE_TAIL_FULL>(w.a, cfg, pv_stride); }
 
+// the kernel argument of the build whose last chunk's scans run T stages: the build travels in its type (see WaveArgsTail)
+template <int T> auto tail_args(const WaveArgs& a) { if constexpr (T == 6) return a; else return WaveArgsTail<T>{ a }; }
+
 }  // namespace
 
 namespace gsf {
 
-// trajectory-major launches (called from gsf_ekf.hip's C entry points)
+// trajectory-major launches (called from gsf_ekf.hip's C entry points): the arguments and the config once, the build from wave_route()
 int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double* pos, const double* quat, const double* gps,
                     const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B,
                     int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status,
                     const int64_t* offsets)
 {
     GSF_REQUIRE(B <= 0x7fffffff, "B too large for one launch");
-    // tracks of 65..1024 poses: one workgroup per trajectory, one wave per chunk (gsf_ekf_block.hip).  The choice depends on N and the
-    // layout only, never on B, so a shard of a batch produces the same bits as the whole batch.
-    // (under the reference's row choice its launcher marks the rows of the fit with a launch of sim3_rows_kernel first)
-    if (ctx->block_kernel == 1 && ekf_block_applies(N, offsets))
-        return launch_ekf_block(ctx, pipeline, ts, pos, quat, gps, valid, init_pos, init_quat, cfg, B, N, R, t, s, pos_out, quat_out, status);
-    WaveArgs a{ ts, pos, quat, gps, valid, init_pos, init_quat, R, t, s, pos_out, quat_out, status, B, N, offsets, pipeline ? ctx->fit_rows : FitRows{ 0, 0, 0.0, 0.0 } };
+    const WaveArgs a{ ts, pos, quat, gps, valid, init_pos, init_quat, R, t, s, pos_out, quat_out, status, B, N, offsets, pipeline ? ctx->fit_rows : FitRows{ 0, 0, 0.0, 0.0 } };
     const EkfConfig k = to_core(cfg);
-    // the build whose last chunk runs only the scan stages that reach its lanes, or that knows every chunk to be full (gsf_set_option
-    // "tail_scan_stages").  Uniform track
-    // length only: a ragged batch has no single last-chunk length, and the big-batch build has no registers for a second instance of the
-    // chunk body (it would spill at three waves per SIMD).  Same bits from every build, so the choice breaks no shard invariance.
-    const int tail = (ctx->tail_scan_stages != 0 && !offsets) ? wave_tail_stages(N) : 6;
-    // x and y share their (P0, Q, R) and z does not (the default CONFIG): the build with that choice of scans compiled in
-    const bool xy = k.P0[1] == k.P0[0] && k.Qps[1] == k.Qps[0] && k.Rm[1] == k.Rm[0] &&
-                    !(k.P0[2] == k.P0[0] && k.Qps[2] == k.Qps[0] && k.Rm[2] == k.Rm[0]);
-    // small batches of the fused pipeline: two waves per trajectory (see ekf_wave_duo_kernel).  Bit-identical to the one-wave
-    // kernel, so choosing by batch size does not break shard invariance.  gsf_set_option "duo_kernel": -1 automatic, 0 never, 1 always.
-    // Measured with the polar-iteration fit (pipeline, N = 271; tools/duo_sweep.py): 15.5 vs 17.8 us at 256 tracks,
-    // 19.4 vs 18.9 us at 512, 20.9 vs 19.5 us at 1 000 (every SIMD then holds a main wave and the helper only competes with it)
-    // -- automatic = up to 256 tracks.  The four-trajectory-per-block form of round 2 (main and helper of a trajectory forced onto
-    // one SIMD) lost its edge with the shorter fit (20.2 vs 19.5 us at 1 000) and lives in tools/experiments/ now.
-    // Short tracks of the fused pipeline under the default noise layout: the one-wave build that forms the FIRST chunk's variances while
-    // the track's rows are still in flight, so that this chunk runs without its Moebius scans (gsf_ekf_wave_early.hip).  Bit-identical to
-    // the kernel below, so the choice may depend on B.  gsf_set_option "early_variances": -1 automatic, 0 never, 1 always where the build
-    // applies (a forced two-wave build goes first; the automatic two-wave range, B <= 256, is kept by the automatic rule).
-    const bool ev_applies = pipeline && xy && !offsets && N > 64 && N <= 384 && B <= 2048;
-    const bool ev_forced = ev_applies && ctx->early_variances == 1 && ctx->duo_kernel != 1;
-    const bool ev_auto = ev_applies && ctx->early_variances == -1 && ctx->duo_kernel != 1 && !(ctx->duo_kernel == -1 && B <= 256) &&
-                         GSF_EARLY_AUTO_RULE(B, N);
-    if (!ev_forced && pipeline && !offsets && ctx->duo_kernel != 0 && N > 64 && N <= 640 && (ctx->duo_kernel == 1 || (ctx->duo_kernel == -1 && B <= 256))) {
-        const int stride = (int)((N + 1) & ~(int64_t)1);
-#define GSF_LAUNCH_DUO_A(X_, A_) hipLaunchKernelGGL((ekf_wave_duo_kernel<true, X_>), dim3((unsigned)B), dim3(128), (size_t)stride * 9 * sizeof(double), ctx->stream, A_, k, stride)
-#define GSF_LAUNCH_DUO(X_) do { if (tail == 4) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<4>{ a }); else if (tail == 5) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<5>{ a }); else if (tail == WAVE_TAIL_FULL) GSF_LAUNCH_DUO_A(X_, WaveArgsTail<WAVE_TAIL_FULL>{ a }); else GSF_LAUNCH_DUO_A(X_, a); } while (0)
-        if (xy) GSF_LAUNCH_DUO(1); else GSF_LAUNCH_DUO(0);
-#undef GSF_LAUNCH_DUO
-#undef GSF_LAUNCH_DUO_A
-        GSF_HIP(hipGetLastError());
-        return GSF_OK;
-    }
-    if (ev_forced || ev_auto)
-        return launch_ekf_wave_early(ctx, tail, ts, pos, quat, gps, valid, cfg, B, N, R, t, s, pos_out, quat_out, status);
-    {
-        // up to 2 048 waves (two per SIMD) the build with inlined cold blocks costs no occupancy; same arithmetic, same bits
-        const bool small = B <= 2048;
-        if (!small)
-            return launch_ekf_wave_big(ctx, pipeline, xy, ts, pos, quat, gps, valid, init_pos, init_quat, cfg, B, N, R, t, s, pos_out, quat_out, status, offsets);
-#define GSF_LAUNCH_WAVE_A(P_, X_, A_) hipLaunchKernelGGL((ekf_wave_kernel<P_, true, X_>), dim3((unsigned)B), dim3(64), 0, ctx->stream, A_, k)
-#define GSF_LAUNCH_WAVE(P_, X_) do { if (tail == 4) GSF_LAUNCH_WAVE_A(P_, X_, WaveArgsTail<4>{ a }); else if (tail == 5) GSF_LAUNCH_WAVE_A(P_, X_, WaveArgsTail<5>{ a }); else if (tail == WAVE_TAIL_FULL) GSF_LAUNCH_WAVE_A(P_, X_, WaveArgsTail<WAVE_TAIL_FULL>{ a }); else GSF_LAUNCH_WAVE_A(P_, X_, a); } while (0)
-        if (pipeline) { if (xy) GSF_LAUNCH_WAVE(true, 1); else GSF_LAUNCH_WAVE(true, 0); }
-        else { if (xy) GSF_LAUNCH_WAVE(false, 1); else GSF_LAUNCH_WAVE(false, 0); }
-#undef GSF_LAUNCH_WAVE
-#undef GSF_LAUNCH_WAVE_A
+    const WaveRoute r = wave_route({ ctx->block_kernel, ctx->duo_kernel, ctx->early_variances, ctx->tail_scan_stages, pipeline, wave_xy_layout(k), offsets != nullptr, B, N });
+    switch (r.family) {
+    case WAVE_BLOCK: return launch_ekf_block(ctx, r, a, k);
+    case WAVE_EARLY: return launch_ekf_wave_early(ctx, r, a, k);
+    case WAVE_BIG: return launch_ekf_wave_big(ctx, r, a, k);
+    case WAVE_DUO:
+        wave_lift<1, 0>(r.xy, [&](auto x) { wave_lift<4, 5, WAVE_TAIL_FULL, 6>(r.tail, [&](auto tl) {
+            hipLaunchKernelGGL((ekf_wave_duo_kernel<true, decltype(x)::value>), dim3((unsigned)B), dim3(128), (size_t)r.pv_stride * 9 * sizeof(double), ctx->stream,
+                               tail_args<decltype(tl)::value>(a), k, r.pv_stride); }); });
+        break;
+    case WAVE_ONE:
+        wave_lift<1, 0>(r.pipeline, [&](auto p) { wave_lift<1, 0>(r.xy, [&](auto x) { wave_lift<4, 5, WAVE_TAIL_FULL, 6>(r.tail, [&](auto tl) {
+            hipLaunchKernelGGL((ekf_wave_kernel<decltype(p)::value != 0, true, decltype(x)::value>), dim3((unsigned)B), dim3(64), 0, ctx->stream,
+                               tail_args<decltype(tl)::value>(a), k); }); }); });
+        break;
     }
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }
 
-}  // namespace gsf
+const char* wave_small_build_info() { return GSF_TU_BUILD_INFO("gsf_ekf_wave.hip"); }
 
-namespace gsf { const char* wave_small_build_info() { return GSF_TU_BUILD_INFO("gsf_ekf_wave.hip"); } }
+}  // namespace gsf

@@ -25,20 +25,14 @@ __global__ __launch_bounds__(64, GSF_BIG_OCC) void ekf_wave_big_kernel(WaveArgs 
 
 namespace gsf {
 
-int launch_ekf_wave_big(gsf_ctx* ctx, bool pipeline, bool xy, const double* ts, const double* pos, const double* quat, const double* gps,
-                        const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B, int64_t N,
-                        double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status, const int64_t* offsets)
+int launch_ekf_wave_big(gsf_ctx* ctx, const WaveRoute& r, const WaveArgs& a, const EkfConfig& k)
 {
-    WaveArgs a{ ts, pos, quat, gps, valid, init_pos, init_quat, R, t, s, pos_out, quat_out, status, B, N, offsets, pipeline ? ctx->fit_rows : FitRows{ 0, 0, 0.0, 0.0 } };
-    const EkfConfig k = to_core(cfg);
-#define GSF_LAUNCH_BIG(P_, X_) hipLaunchKernelGGL((ekf_wave_big_kernel<P_, X_>), dim3((unsigned)B), dim3(64), 0, ctx->stream, a, k)
-    if (pipeline) { if (xy) GSF_LAUNCH_BIG(true, 1); else GSF_LAUNCH_BIG(true, 0); }
-    else { if (xy) GSF_LAUNCH_BIG(false, 1); else GSF_LAUNCH_BIG(false, 0); }
-#undef GSF_LAUNCH_BIG
+    wave_lift<1, 0>(r.pipeline, [&](auto p) { wave_lift<1, 0>(r.xy, [&](auto x) {
+        hipLaunchKernelGGL((ekf_wave_big_kernel<decltype(p)::value != 0, decltype(x)::value>), dim3((unsigned)a.B), dim3(64), 0, ctx->stream, a, k); }); });
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }
 
-}  // namespace gsf
+const char* wave_big_build_info() { return GSF_TU_BUILD_INFO("gsf_ekf_wave_big.hip"); }
 
-namespace gsf { const char* wave_big_build_info() { return GSF_TU_BUILD_INFO("gsf_ekf_wave_big.hip"); } }
+}  // namespace gsf

@@ -30,11 +30,7 @@ namespace {
 
 static_assert(GSF_ROWS_ROUND == 6, "the early-variance build hands the fit passes ONE round of six chunks");
 
-// How many chunks' variances are formed early (never the last chunk's).  Measured at 1 000 x 271, plain bench, us per step: parent 17.38,
-// one chunk 16.94, two 17.65, three 18.86, all five 18.8 (HISTORY.md, "Early variances").
-#ifndef GSF_EARLY_CHUNKS
-#define GSF_EARLY_CHUNKS 1
-#endif
+// (GSF_EARLY_CHUNKS, how many chunks' variances are formed early: gsf_wave_route.hpp, with the bounds of this build)
 template <int NCH, int TAILNS> struct WaveArgsEarly { WaveArgs a; int pv_stride; };
 
 template <bool PIPELINE, int AXMODE, int NCH, int TAILNS>
@@ -177,31 +173,15 @@ GSF_WAVE_EARLY_KERNELS(6)
 
 namespace gsf {
 
-
-// fused pipeline, x and y sharing their noise and z not, equal lengths, 64 < N <= 384 (launch_ekf_wave has checked all of it);
-// tail = wave_tail_stages(N), or 6 for the build without sized scans
-int launch_ekf_wave_early(gsf_ctx* ctx, int tail, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
-                          const gsf_ekf_config* cfg, int64_t B, int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out,
-                          int32_t* status)
+// fused pipeline, x and y sharing their noise and z not, equal lengths, 64 < N <= 384: wave_route()'s EARLY, taken as it comes
+int launch_ekf_wave_early(gsf_ctx* ctx, const WaveRoute& r, const WaveArgs& a, const EkfConfig& k)
 {
-    GSF_REQUIRE(N > 64 && N <= 384 && B > 0 && B <= 0x7fffffff, "the early-variance build takes equal-length tracks of 65..384 poses");
-    const WaveArgs a{ ts, pos, quat, gps, valid, nullptr, nullptr, R, t, s, pos_out, quat_out, status, B, N, nullptr, ctx->fit_rows };
-    const EkfConfig k = to_core(cfg);
-    const int nch = (int)((N + 63) / 64);
-    GSF_REQUIRE(tail == 6 || tail == wave_tail_stages(N), "scan sizing does not belong to the track length");
-    const int stride = 64 * (GSF_EARLY_CHUNKS < nch - 1 ? GSF_EARLY_CHUNKS : nch - 1);   // poses the table holds (the kernel's NE chunks)
-    const size_t lds = (size_t)stride * 9 * sizeof(double);
-#define GSF_LAUNCH_EARLY_A(C_, T_) hipLaunchKernelGGL((ekf_wave_kernel<true, true, 1>), dim3((unsigned)B), dim3(64), lds, ctx->stream, WaveArgsEarly<C_, T_>{ a, stride }, k)
-#define GSF_LAUNCH_EARLY(C_) do { if (tail == 4) GSF_LAUNCH_EARLY_A(C_, 4); else if (tail == 5) GSF_LAUNCH_EARLY_A(C_, 5); else if (tail == WAVE_TAIL_FULL) GSF_LAUNCH_EARLY_A(C_, WAVE_TAIL_FULL); else GSF_LAUNCH_EARLY_A(C_, 6); } while (0)
-    switch (nch) {
-    case 2: GSF_LAUNCH_EARLY(2); break;
-    case 3: GSF_LAUNCH_EARLY(3); break;
-    case 4: GSF_LAUNCH_EARLY(4); break;
-    case 5: GSF_LAUNCH_EARLY(5); break;
-    default: GSF_LAUNCH_EARLY(6); break;
-    }
-#undef GSF_LAUNCH_EARLY
-#undef GSF_LAUNCH_EARLY_A
+    GSF_REQUIRE(a.B > 0 && a.B <= 0x7fffffff, "B out of range for one launch");
+    WaveArgs e = a; e.init_pos = nullptr; e.init_quat = nullptr;           // the fit gives the initial pose
+    const size_t lds = (size_t)r.pv_stride * 9 * sizeof(double);
+    wave_lift<2, 3, 4, 5, 6>(r.nch, [&](auto c) { wave_lift<4, 5, WAVE_TAIL_FULL, 6>(r.tail, [&](auto tl) {
+        hipLaunchKernelGGL((ekf_wave_kernel<true, true, 1>), dim3((unsigned)a.B), dim3(64), lds, ctx->stream,
+                           WaveArgsEarly<decltype(c)::value, decltype(tl)::value>{ e, r.pv_stride }, k); }); });
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }

@@ -98,27 +98,24 @@ template <class T = char> inline T* workspace(const gsf_ctx* ctx, int slot) { re
 // `bytes` at p (device memory, 8-byte aligned) <- the 64-bit word repeated, on the context's stream (gsf_util.hip)
 int launch_fill_words(gsf_ctx* ctx, void* p, size_t bytes, uint64_t word);
 
-// wave-per-trajectory K4 / fused pipeline for the trajectory-major layout (gsf_ekf_wave.hip)
+// gsf_ekf_config -> the kernels' form of it (np.deg2rad, ref :886)
+inline EkfConfig to_core(const gsf_ekf_config* c)
+{
+    EkfConfig k;
+    for (int i = 0; i < 7; ++i) { k.P0[i] = c->initial_cov_diag[i]; k.Qps[i] = c->process_noise_diag[i]; }
+    for (int i = 0; i < 3; ++i) k.Rm[i] = c->meas_noise_diag[i];
+    k.yaw_thr_rad = c->sharp_turn_yaw_rate_threshold_deg_per_sec * (M_PI / 180.0);
+    k.sharp_turn_steps = c->default_ekf_transition_steps_on_sharp_turn;
+    k._pad = 0;
+    return k;
+}
+
+// wave-per-trajectory K4 / fused pipeline for the trajectory-major layout (gsf_ekf_wave.hip), by the build that wave_route() names
+// (gsf_wave_route.hpp): one wave, two waves, early variances, big batch or a workgroup per trajectory -- the same bits from each
 int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double* pos, const double* quat, const double* gps,
                     const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B,
                     int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status,
                     const int64_t* offsets = nullptr);
-
-// the big-batch builds of the wave kernels (gsf_ekf_wave_big.hip): B > 2 048
-int launch_ekf_wave_big(gsf_ctx* ctx, bool pipeline, bool xy, const double* ts, const double* pos, const double* quat, const double* gps,
-                        const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B, int64_t N,
-                        double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status, const int64_t* offsets);
-
-// the early-variance builds of the fused pipeline's one-wave kernel (gsf_ekf_wave_early.hip): equal lengths, 64 < N <= 384, default noise layout
-int launch_ekf_wave_early(gsf_ctx* ctx, int tail, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
-                          const gsf_ekf_config* cfg, int64_t B, int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out,
-                          int32_t* status);
-
-// workgroup-per-trajectory K4 / fused pipeline (gsf_ekf_block.hip): one wave per 64-pose chunk, every input byte read once
-bool ekf_block_applies(int64_t N, const int64_t* offsets);
-int launch_ekf_block(gsf_ctx* ctx, bool pipeline, const double* ts, const double* pos, const double* quat, const double* gps,
-                     const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B,
-                     int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status);
 
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
 int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);

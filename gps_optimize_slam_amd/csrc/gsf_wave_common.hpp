@@ -2,6 +2,7 @@
 // (gsf_ekf_wave.hip: one wave per trajectory; gsf_ekf_block.hip: one wave per 64-pose chunk, a block per trajectory).
 #pragma once
 #include "gsf_internal.hpp"
+#include "gsf_wave_route.hpp"
 
 namespace {
 
@@ -75,16 +76,7 @@ __device__ __forceinline__ double shidx(double v, int src) { return __shfl(v, sr
                                if constexpr ((NS) >= 5) STAGE(DPP_ROW_BCAST15, 0xa) else STAGE(DPP_NO_SOURCE, 0x0)                      \
                                if constexpr ((NS) >= 6) STAGE(DPP_ROW_BCAST31, 0xc) else STAGE(DPP_NO_SOURCE, 0x0)
 template <int V> struct ScanStages { static constexpr int value = V; };
-// TAILNS of a kernel instance: the stages the scans of the track's LAST chunk run.  The launcher picks the instance from the track
-// length (wave_tail_stages), so the kernel itself carries no test: TAILNS = 6 is the kernel without sized scans, for any length;
-// WAVE_TAIL_FULL says that the length is a multiple of 64, i.e. that EVERY chunk is a full one (six stages, no partial chunk at all).
-constexpr int WAVE_TAIL_FULL = 7;
-__host__ __device__ inline int wave_tail_stages(const int64_t N)
-{
-    if (N <= 0) return 6;
-    const int last = (int)((N - 1) & 63);                                 // last active lane of the last chunk
-    return last == 63 ? WAVE_TAIL_FULL : (last < 16 ? 4 : (last < 32 ? 5 : 6));
-}
+// (TAILNS of a kernel instance, WAVE_TAIL_FULL and wave_tail_stages: gsf_wave_route.hpp)
 // sum over the wave: inclusive DPP scan, total read from lane 63 (wave-uniform result)
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -238,17 +230,6 @@ __device__ __forceinline__ int32_t* gsf_stamp_buf() { __shared__ int32_t buf[64]
 #ifndef GSF_WIDE_STORES
 #define GSF_WIDE_STORES 1                                                 // big-batch builds store whole output slabs through LDS (see the chunk loop's store site)
 #endif
-
-inline EkfConfig to_core(const gsf_ekf_config* c)
-{
-    EkfConfig k;
-    for (int i = 0; i < 7; ++i) { k.P0[i] = c->initial_cov_diag[i]; k.Qps[i] = c->process_noise_diag[i]; }
-    for (int i = 0; i < 3; ++i) k.Rm[i] = c->meas_noise_diag[i];
-    k.yaw_thr_rad = c->sharp_turn_yaw_rate_threshold_deg_per_sec * (M_PI / 180.0);
-    k.sharp_turn_steps = c->default_ekf_transition_steps_on_sharp_turn;
-    k._pad = 0;
-    return k;
-}
 
 struct ChunkIn { double t; Vec3 p; Quat q; Vec3 z; uint32_t v; };
 
@@ -1333,5 +1314,15 @@ __device__ __forceinline__ void wave_serial_body(const WaveArgs& a, const EkfCon
     wave_serial_chunks<PIPELINE, PREVAR, SMALLBATCH, RINGS, AXMODE, TAILNS>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, pv, pv_stride, ring_slot);
 }
 
-
 }  // namespace
+
+// The family launchers behind launch_ekf_wave (gsf_ekf_wave.hip), which builds the arguments and the config once and hands them on with
+// the route (gsf_wave_route.hpp); none of them derives or checks the route again.  C linkage: WaveArgs lives in the unnamed namespace (its
+// name is part of the kernels' symbol names), and a C++ function with such a parameter would be local to its translation unit.
+namespace gsf {
+extern "C" {
+int launch_ekf_wave_big(gsf_ctx* ctx, const WaveRoute& r, const WaveArgs& a, const EkfConfig& k);     // gsf_ekf_wave_big.hip
+int launch_ekf_wave_early(gsf_ctx* ctx, const WaveRoute& r, const WaveArgs& a, const EkfConfig& k);   // gsf_ekf_wave_early.hip
+int launch_ekf_block(gsf_ctx* ctx, const WaveRoute& r, const WaveArgs& a, const EkfConfig& k);        // gsf_ekf_block.hip
+}
+}  // namespace gsf

@@ -179,7 +179,7 @@ GSF_API int gsf_trim(gsf_ctx *ctx);
      "early_variances"  -1 automatic (default) / 0 never / 1 always where the build applies: the one-wave build of the fused pipeline that computes
                       its first chunk's variances from stamps and mask bytes while the rest of the track's rows are still in flight (equal-length
                       batches of up to 2 048 tracks of 65..384 poses, x and y sharing their noise and z not -- the default CONFIG; a forced
-                      "duo_kernel" 1 goes first).  Bit-identical results; -1 takes the build for 1 000..1 024 tracks of 256..384 poses (measured, see launch_ekf_wave)
+                      "duo_kernel" 1 goes first).  Bit-identical results; -1 takes the build for 1 000..1 024 tracks of 256..384 poses (measured, see wave_route() in csrc/gsf_wave_route.hpp)
      "lane_min_traj"  time-major batches with fewer trajectories than this (default 32768) are transposed and run by the
                       wave-per-trajectory kernel; 0 = always the lane-per-trajectory kernel
      "block_kernel"   -1 / 0 never (what -1 means today) / 1 whenever it applies: workgroup-per-trajectory EKF kernel for 64 < N <= 1024

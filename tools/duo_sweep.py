@@ -1,5 +1,5 @@
 """One-wave vs two-wave build of the fused pipeline over batch sizes and track lengths (the data behind the automatic choice in
-gsf_ekf_wave.hip: launch_ekf_wave).  usage (GPU box): python tools/duo_sweep.py"""
+gsf_wave_route.hpp: wave_route).  usage (GPU box): python tools/duo_sweep.py"""
 import os
 import sys
 
