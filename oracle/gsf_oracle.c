@@ -968,6 +968,7 @@ static int cmp_idx_by_time(const void *pa, const void *pb, void *ctx)
     int64_t a = *(const int64_t *)pa, b = *(const int64_t *)pb;
     if (t[a] < t[b]) return -1;
     if (t[a] > t[b]) return 1;
+    if (isnan(t[a]) != isnan(t[b])) return isnan(t[a]) ? 1 : -1;      /* NaN stamps sort last (np.argsort) */
     return (a < b) ? -1 : (a > b);       /* stable, like the merge the reference relies on for np.unique(return_index) */
 }
 
@@ -989,8 +990,7 @@ ORC_API void orc_dynamic_time_alignment(const double *slam_t, int64_t ns, const 
     int64_t nu = 0;
     for (int64_t i = 0; i < ng; ++i) {
         double t = tt[ord[i]];
-        if (nu > 0 && t == ut[nu - 1]) continue;
-        if (isnan(t)) continue;
+        if (nu > 0 && t == ut[nu - 1]) continue;                                  /* (a NaN stamp stays, as in np.unique: its segment fails :364) */
         ut[nu] = t;
         for (int c = 0; c < 3; ++c) up[nu * 3 + c] = gps_p[ord[i] * 3 + c];
         ++nu;
