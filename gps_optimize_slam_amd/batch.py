@@ -973,6 +973,156 @@ def ekf_covariance_batch(batch, config=None, want_filtered=True):
                                  want_filtered=want_filtered)
 
 
+# ---------------------------------------------------------------------------- EKF noise sweep (gsf_ekf_noise_sweep_dev)
+NOISE_P0_MAX, NOISE_R_MIN, NOISE_R_MAX, NOISE_QDT_MAX = 1e8, 1e-8, 1e8, 1e14      # the stated range of the noise values (include/gsf.h, gsf_ekf_config)
+_LN_2PI = 1.8378770664093453
+
+
+def _noise_domain_chk(cand, max_dt):
+    import numpy as np
+    c = np.asarray(cand, dtype=np.float64)
+    p0, q, r = c[:, 0:3], c[:, 3:6], c[:, 6:9]
+    step = max(float(max_dt), 1e-6)
+    ok = np.isfinite(c).all(axis=1) & ((p0 >= 0.0) & (p0 <= NOISE_P0_MAX)).all(axis=1) & ((r >= NOISE_R_MIN) & (r <= NOISE_R_MAX)).all(axis=1) \
+        & ((q >= 0.0) & (q * step <= NOISE_QDT_MAX)).all(axis=1)
+    if not ok.all():
+        k = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"noise candidate {k} = {c[k].tolist()} is outside the stated range 0 <= P0 <= 1e8, 1e-8 <= R <= 1e8, "
+                         f"0 <= Q dt <= 1e14 (dt up to {step} in the stamps' unit)")
+
+
+def noise_candidates(config, q_scales, r_scales, p0_scales=(1.0,), max_dt=1.0):
+    """Candidates for ekf_noise_sweep_ragged on a grid around config['ekf']: the position entries of initial_cov_diag / process_noise_diag /
+    meas_noise_diag times every combination of p0_scales x q_scales x r_scales.  Returns (cand (K,9) float64 numpy rows
+    [P0x P0y P0z Qx Qy Qz Rx Ry Rz], shape = (len(p0_scales), len(q_scales), len(r_scales))); candidate k is the grid point
+    np.unravel_index(k, shape) (C order).  ValueError for a candidate outside the stated range of the noise values (include/gsf.h);
+    max_dt = the longest step between two stamps the candidates will meet, in the stamps' unit (the range bounds Q dt)."""
+    import numpy as np
+    e = (config or CONFIG)["ekf"]
+    p0, q, r = (np.asarray([float(x) for x in e[n]][:3]) for n in ("initial_cov_diag", "process_noise_diag", "meas_noise_diag"))
+    ps, qs, rs = (np.asarray(list(v), dtype=np.float64).reshape(-1) for v in (p0_scales, q_scales, r_scales))
+    shape = (ps.size, qs.size, rs.size)
+    K = ps.size * qs.size * rs.size
+    if not 1 <= K <= 4096:
+        raise ValueError(f"noise_candidates: {K} candidates, 1..4096 per call")
+    cand = np.empty(shape + (9,))
+    cand[..., 0:3] = ps[:, None, None, None] * p0
+    cand[..., 3:6] = qs[None, :, None, None] * q
+    cand[..., 6:9] = rs[None, None, :, None] * r
+    cand = np.ascontiguousarray(cand.reshape(K, 9))
+    _noise_domain_chk(cand, max_dt)
+    return cand, shape
+
+
+class NoiseSweep:
+    """Result of ekf_noise_sweep_ragged for B tracks x K candidates (definitions: include/gsf.h, gsf_ekf_noise_sweep_dev).  Device tensors:
+    stats (B,K,12); nll / mean_nis / rho1 (B,K) derived from it (nll = (3 n ln 2pi + sum log S + sum NIS) / 2, mean_nis = sum NIS / n,
+    rho1 = lag-one term / (3 pairs); NaN where n is 0); best_k (B,2) int32 = the picks by nll and by |mean_nis - 3| (-1: none);
+    pooled (K,12), pooled_nll / pooled_mean_nis (K,), pooled_best (2,) int32: the same over all usable tracks together -- the pick to use,
+    noise being a property of the receiver; status (B,) int32 = _lib.NS_NONE | NS_TIE; innov / innov_var (P,3) = y and S of the traced
+    candidate (None without trace); candidates (K,9)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def config(self, k, base=None):
+        """A CONFIG dict (deep copy of base, default the module's CONFIG) with candidate k written into the position entries of ['ekf']:
+        ready for run_fusion_ragged."""
+        import copy
+        k = int(k)
+        if not 0 <= k < int(self.candidates.shape[0]):
+            raise ValueError(f"NoiseSweep.config: no candidate {k} (a pick of -1 means that nothing was picked)")
+        g = copy.deepcopy(base or CONFIG)
+        row = [float(x) for x in self.candidates[k].cpu().tolist()]
+        for name, lo in (("initial_cov_diag", 0), ("process_noise_diag", 3), ("meas_noise_diag", 6)):
+            v = [float(x) for x in g["ekf"][name]]
+            v[0:3] = row[lo:lo + 3]
+            g["ekf"][name] = v
+        return g
+
+    def at_edge(self, shape, criterion=0):
+        """For a grid made by noise_candidates(shape): does a pick lie on the grid's edge along an axis with more than one value -- the
+        minimum may then lie outside the grid, widen it (the counterpart of CLK_AT_EDGE).  Returns (per track (B,) bool numpy, pooled bool);
+        a pick of -1 is not on an edge."""
+        import numpy as np
+        shape = tuple(int(n) for n in shape)
+        if int(np.prod(shape)) != int(self.candidates.shape[0]):
+            raise ValueError("NoiseSweep.at_edge: the shape does not describe the swept candidates")
+
+        def edge(k):
+            if k < 0:
+                return False
+            return any(n > 1 and (i == 0 or i == n - 1) for i, n in zip(np.unravel_index(int(k), shape), shape))
+        per = np.array([edge(int(k)) for k in self.best_k[:, criterion].cpu().tolist()], dtype=bool)
+        return per, edge(int(self.pooled_best[criterion].item()))
+
+
+def _noise_derived(rows):
+    n = rows[..., 0]
+    nis = (rows[..., 1] + rows[..., 2]) + rows[..., 3]
+    ls = (rows[..., 4] + rows[..., 5]) + rows[..., 6]
+    nll = 0.5 * (((3.0 * n) * _LN_2PI + ls) + nis)
+    return nll, nis / n, rows[..., 10] / (3.0 * rows[..., 11])
+
+
+def ekf_noise_sweep_ragged(ts, pos, quat, gps, valid, offsets, init_pos, init_quat, candidates, config=None, run_status=None, skip_seconds=0.0,
+                           min_updates=1, trace=None):
+    """Innovation statistics of the EKF for K noise candidates per track, one launch chain on torch's current stream
+    (gsf_ekf_noise_sweep_dev).  Inputs as ekf_fuse_ragged: flat device tensors ts (P,), pos (P,3), quat (P,4) = the original SLAM track,
+    gps (P,3) / valid (P,) uint8 = the time-aligned fixes, offsets (B+1,) int64, init_pos (B,3) / init_quat (B,4) = row 0 of the
+    Sim3-aligned track.  candidates (K,9) rows [P0 Q R] x 3 axes (numpy or tensor; noise_candidates builds a grid), inside the stated
+    range of the noise values.  The sharp-turn settings come from config.  skip_seconds: updates up to ts[0] + skip_seconds are not
+    counted (<= 0: all are); min_updates: fewer counted updates give no pick; trace = k: y and S of candidate k per pose.  Returns a NoiseSweep."""
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid")
+    _chk(init_pos, torch.float64, (B, 3), "init_pos"); _chk(init_quat, torch.float64, (B, 4), "init_quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    dev = ts.device
+    cand = torch.as_tensor(candidates, dtype=torch.float64).to(dev).contiguous()
+    if cand.dim() != 2 or cand.shape[1] != 9 or not 1 <= int(cand.shape[0]) <= 4096:
+        raise ValueError(f"ekf_noise_sweep_ragged: candidates must be (K, 9) with 1 <= K <= 4096, got {tuple(cand.shape)}")
+    K = int(cand.shape[0])
+    trace_k = -1 if trace is None else int(trace)
+    if trace is not None and not 0 <= trace_k < K:
+        raise ValueError(f"ekf_noise_sweep_ragged: trace = {trace_k} names no candidate (K = {K})")
+    cfg = EkfConfig.from_config(config or CONFIG)
+    f = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    r = NoiseSweep(stats=torch.empty((B, K, 12), **f), best_k=torch.empty((B, 2), **i32), pooled=torch.empty((K, 12), **f),
+                   pooled_best=torch.empty((2,), **i32), status=torch.empty((B,), **i32),
+                   innov=torch.empty((P, 3), **f) if trace is not None else None, innov_var=torch.empty((P, 3), **f) if trace is not None else None,
+                   candidates=cand)
+    check(_lib.load().gsf_ekf_noise_sweep_dev(context().handle, _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(offsets), _p(run_status), _p(init_pos),
+                                              _p(init_quat), C.byref(cfg), B, _p(cand), K, float(skip_seconds), int(min_updates), trace_k, _p(r.stats),
+                                              _p(r.best_k), _p(r.pooled), _p(r.pooled_best), _p(r.status), _p(r.innov), _p(r.innov_var)))
+    r.nll, r.mean_nis, r.rho1 = _noise_derived(r.stats)
+    r.pooled_nll, r.pooled_mean_nis, _ = _noise_derived(r.pooled)
+    return r
+
+
+def sweep_noise_fused(rb, r, candidates, config=None, skip_seconds=0.0, min_updates=1, trace=None):
+    """ekf_noise_sweep_ragged on the result r of run_fusion_ragged / run_fusion_batch for the batch rb: the aligned fixes, their mask and
+    run_status are r's; the initial pose of every track is row 0 of transform_trajectory's output (EKFGPSSLAM.py:1006) -- r.sim3_pos and
+    the Sim3 rotation applied to the first SLAM quaternion -- and NOT row 0 of r.fused, which RTS may have rewritten (an outage from pose 0)."""
+    ts, pos, quat = rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4)
+    offsets = rb.slam_offsets
+    B, P = _offsets_chk(offsets), int(ts.numel())
+    dev = ts.device
+    if P == 0:
+        first = torch.zeros((B,), dtype=torch.int64, device=dev)
+        ip, iq = torch.zeros((B, 3), dtype=torch.float64, device=dev), torch.zeros((B, 4), dtype=torch.float64, device=dev)
+    else:
+        first = torch.clamp(offsets[:-1], max=P - 1)                      # (an empty track's row is never read)
+        one = torch.arange(B + 1, dtype=torch.int64, device=dev)
+        ip = r.sim3_pos.reshape(-1, 3)[first].contiguous()
+        _, iq, _ = apply_sim3_batch(pos[first].contiguous(), quat[first].contiguous(), one, r.R, r.t, r.s)
+    return ekf_noise_sweep_ragged(ts, pos, quat, r.aligned.reshape(-1, 3), r.valid.reshape(-1), offsets, ip, iq, candidates, config=config,
+                                  run_status=r.run_status, skip_seconds=skip_seconds, min_updates=min_updates, trace=trace)
+
+
 class PoseQuery:
     """The fused track at query stamps (query_poses_ragged), flat over the M queries: pos (M,3), quat (M,4), flags (M,) uint8 of _lib.Q_* bits,
     index (M,) int32 = the bracket's first pose relative to its track (-1: none), pose_flags (M,) uint8 or None = the _lib.POSE_* bits of

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "gsf_internal.hpp"
+#include "gsf_sweep_core.hpp"
 
 namespace gsf {
 
@@ -247,6 +248,8 @@ static const struct { const char* key; int gsf_ctx::*field; int64_t lo, hi; cons
     { "tail_scan_stages", &gsf_ctx::tail_scan_stages, 0, 1,
       "tail_scan_stages must be 1 (the scans of a short last chunk run only the stages that reach its lanes, default) or 0 (always six stages); the results are the "
       "same bits" },
+    { "noise_sweep_group", &gsf_ctx::noise_sweep_group, 0, 64,
+      "noise_sweep_group must be 0 (automatic) or the number of candidates one wave of the EKF noise sweep takes, 1..64; the results are the same bits" },
 };
 
 int gsf_set_option(gsf_ctx* ctx, const char* key, int64_t value)
@@ -664,6 +667,24 @@ int gsf_georef_points(gsf_ctx* ctx, const double* ts, const double* pos, const d
     auto dqi = st.out_opt(q_index, Mq); auto dqp = st.out_opt(q_pose_flags, Mq);
     auto dst_ = st.out(track_state, (size_t)B);
     ST_RUN(gsf_georef_points_dev(ctx, dts, dpos, dquat, doff, drs, dpf, B, dqt, dqo, M, max_gap, dx, deq, det, dsc, dxyz, dfl, dqi, dqp, dst_));
+}
+
+// EKF noise sweep: device form only (include/gsf.h; the Python binding uploads host arrays itself)
+int gsf_ekf_noise_sweep_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                            const int64_t* offsets, const int32_t* run_status, const double* init_pos, const double* init_quat,
+                            const gsf_ekf_config* cfg, int64_t B, const double* cand, int32_t K, double skip_seconds, int32_t min_updates,
+                            int32_t trace_k, double* stats, int32_t* best_k, double* pooled, int32_t* pooled_best, int32_t* ns_status,
+                            double* innov, double* innov_var)
+{
+    GSF_REQUIRE(ctx && cfg && offsets, "ctx/cfg/offsets is NULL");
+    GSF_REQUIRE(B >= 0, "negative B");
+    GSF_REQUIRE(K >= 1 && K <= SWEEP_MAX_K, "K must be in [1, 4096]");
+    GSF_REQUIRE(trace_k < K, "trace_k must be below K (negative: no trace)");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(ts && pos && quat && gps && valid && init_pos && init_quat && cand, "NULL array");
+    GSF_REQUIRE(skip_seconds == skip_seconds, "skip_seconds is NaN");
+    return launch_noise_sweep(ctx, ts, pos, quat, gps, valid, offsets, run_status, init_pos, init_quat, cfg, B, cand, K, skip_seconds, min_updates,
+                              trace_k, stats, best_k, pooled, pooled_best, ns_status, innov, innov_var);
 }
 
 }  // extern "C"

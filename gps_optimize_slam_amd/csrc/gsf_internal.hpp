@@ -45,6 +45,7 @@ struct gsf_ctx {
     int duo_kernel = -1;       // two-wave pipeline kernel for small batches (gsf_set_option "duo_kernel"): -1 automatic, 0 never, 1 always
     int early_variances = -1;  // one-wave pipeline build for short tracks with the first chunk's variances computed under the input burst (gsf_set_option "early_variances"): -1 automatic, 0 never, 1 always where it applies (same bits)
     int tail_scan_stages = 1;  // wave kernels: scans of a short last chunk sized by its last active lane (gsf_set_option "tail_scan_stages"): 1 default, 0 always six stages (same bits)
+    int noise_sweep_group = 0; // candidates per wave of the EKF noise sweep (gsf_set_option "noise_sweep_group"): 0 automatic (sweep_group(), gsf_wave_route.hpp), 1..64 forced (same bits)
     // rows of the fused chains' Sim3 fit (gsf_set_sim3_rows); mode 0 = all valid rows.  Default: the rows main_process_gui hands to its fit
     // (ref :973-998) under the reference's CONFIG defaults (:34, :53, :37), so a raw C caller of gsf_fuse_pipeline_* gets steps 3-5 as the reference runs them
     gsf::FitRows fit_rows{ 1, 4, 5.0, 180.0 };
@@ -116,6 +117,13 @@ int launch_ekf_wave(gsf_ctx* ctx, bool pipeline, const double* ts, const double*
                     const uint8_t* valid, const double* init_pos, const double* init_quat, const gsf_ekf_config* cfg, int64_t B,
                     int64_t N, double* R, double* t, double* s, double* pos_out, double* quat_out, int32_t* status,
                     const int64_t* offsets = nullptr);
+
+// EKF noise sweep (gsf_noise_sweep.hip): the body of gsf_ekf_noise_sweep_dev, arguments checked by the caller
+int launch_noise_sweep(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                       const int64_t* offsets, const int32_t* run_status, const double* init_pos, const double* init_quat,
+                       const gsf_ekf_config* cfg, int64_t B, const double* cand, int32_t K, double skip_seconds, int32_t min_updates,
+                       int32_t trace_k, double* stats, int32_t* best_k, double* pooled, int32_t* pooled_best, int32_t* ns_status,
+                       double* innov, double* innov_var);
 
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
 int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);

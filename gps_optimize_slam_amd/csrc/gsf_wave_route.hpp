@@ -86,6 +86,29 @@ inline WaveRoute wave_route(const WaveRouteIn& in)
     return r;
 }
 
+// EKF noise sweep (gsf_noise_sweep.hip): how many of a call's K candidates one wave takes.  A wave reads its track's chunk once (89 B per
+// pose) and runs its candidates one after the other on it, so a larger group means fewer reads of the same rows and a smaller one more
+// waves.  The chip has 256 CUs x 4 SIMDs; the kernel's registers leave room for two waves on a SIMD, so 2 048 waves fill it.  Automatic
+// (forced == 0): the candidates are split into just enough groups to reach 2 048 waves -- groups = ceil(2048 / B), at most K -- of equal
+// size, at most 64 (one lane holds the carry of one candidate).  One track with K = 64: 64 waves of one candidate each; 1 000 tracks with
+// K = 64: 3 groups of 22, 22 and 20; 2 048 tracks or more: one group of up to 64.  gsf_set_option "noise_sweep_group" 1..64 forces the
+// size.  A candidate's arithmetic does not depend on its group (one code path, a run-time loop), so every choice gives the same bits.
+constexpr int64_t SWEEP_FILL_WAVES = 2048;
+inline int sweep_group(const int64_t B, const int K, const int forced)
+{
+    if (K <= 0) return 1;
+    int kc;
+    if (forced > 0) kc = forced;
+    else {
+        const int64_t want = B > 0 ? (SWEEP_FILL_WAVES + B - 1) / B : SWEEP_FILL_WAVES;   // groups per track that fill the chip
+        const int groups = (int)(want < K ? want : K);
+        kc = (K + groups - 1) / groups;
+    }
+    if (kc > 64) kc = 64;
+    if (kc > K) kc = K;
+    return kc < 1 ? 1 : kc;
+}
+
 // A run-time value as a compile-time one: f(std::integral_constant<int, V>) for the first V of the list that equals v, the LAST one when
 // none does.  How the launchers turn a route into template arguments (nested: one lift per argument).
 template <int V, int... Vs, class F> inline auto wave_lift(const int v, F&& f)

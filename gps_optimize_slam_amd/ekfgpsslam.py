@@ -496,6 +496,32 @@ def ekf_fuse_aligned(timestamps, positions, quaternions, aligned_gps, valid_mask
     return po, qo, int(st[0])
 
 
+def sweep_ekf_noise(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial, global_config, candidates, skip_seconds=0.0, min_updates=1, trace=None):
+    """Innovation statistics of apply_ekf_correction's filter for K candidates of CONFIG['ekf'] on one track (gsf_ekf_noise_sweep_dev;
+    definitions in include/gsf.h): the same alignment call as apply_ekf_correction (ref :847), the initial pose = row 0 of the
+    Sim3-transformed track.  candidates (K,9) rows [P0 Q R] x 3 axes (batch.noise_candidates builds a grid around a CONFIG).  Returns a dict
+    of host arrays: 'stats' (K,12), 'nll' / 'mean_nis' / 'rho1' (K,), 'best_k' (2,) = the picks by nll and by |mean_nis - 3| (-1: none),
+    'status' (NS_* bits of _lib), 'innov' / 'innov_var' (n,3) of candidate `trace` (None without), 'candidates' (K,9)."""
+    import torch
+    from . import batch as gb
+    n = len(slam_data["timestamps"])
+    sim3_pos_initial, sim3_quat_initial = np.asarray(sim3_pos_initial), np.asarray(sim3_quat_initial)
+    if n and not (sim3_pos_initial.shape[0] == n and sim3_quat_initial.shape[0] == n):
+        raise ValueError(f"Sim3-transformed trajectory length ({sim3_pos_initial.shape[0]}) != SLAM timestamp count ({n})")
+    aligned, valid = dynamic_time_alignment(slam_data, gps_data, global_config["time_alignment"])     # ref :847
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(shape)).to(dev)
+    ip = sim3_pos_initial[0] if n else np.zeros(3)
+    iq = sim3_quat_initial[0] if n else np.array([0.0, 0.0, 0.0, 1.0])
+    r = gb.ekf_noise_sweep_ragged(up(slam_data["timestamps"], (n,)), up(slam_data["positions"], (n, 3)), up(slam_data["quaternions"], (n, 4)),
+                                  up(aligned, (n, 3)), up(valid, (n,), np.uint8), torch.tensor([0, n], dtype=torch.int64, device=dev),
+                                  up(ip, (1, 3)), up(iq, (1, 4)), candidates, config=global_config, skip_seconds=skip_seconds,
+                                  min_updates=min_updates, trace=trace)
+    h = lambda t: None if t is None else t.cpu().numpy()
+    return {"stats": h(r.stats[0]), "nll": h(r.nll[0]), "mean_nis": h(r.mean_nis[0]), "rho1": h(r.rho1[0]), "best_k": h(r.best_k[0]),
+            "status": int(r.status[0].item()), "innov": h(r.innov), "innov_var": h(r.innov_var), "candidates": h(r.candidates)}
+
+
 def ekf_covariances(slam_data_in, gps_data_in, global_config):
     """The covariances apply_ekf_correction computes and drops, for one trajectory (host arrays): {"filtered": (n,7,7) = ekf_covs_filt_hist
     (ref :852, :902), "smoothed": (n,7,7) = the covariance of the pose apply_ekf_correction returns -- rts_smoother_segment's (ref :777-803)

@@ -216,6 +216,9 @@ GSF_API int gsf_trim(gsf_ctx *ctx);
                       after its allocation.  No call keeps state in a workspace from one call to the next, so results must not depend on
                       it (tests/test_buffer_hygiene.py).  The word reads as a small number through every type, so a kernel that
                       does read a count or an offset nobody wrote gives a wrong value, not a wild address
+     "noise_sweep_group"  0 automatic (default): gsf_ekf_noise_sweep_dev splits its K candidates into just enough equal groups to put 2 048
+                      waves on the chip, at most 64 candidates per wave (sweep_group() in csrc/gsf_wave_route.hpp) / 1..64: that many
+                      candidates per wave.  Bit-identical results
      "ekf_variant"    reserved (0) */
 GSF_API int gsf_set_option(gsf_ctx *ctx, const char *key, int64_t value);
 /* Which rows feed the Sim3 fit of the fused chains (gsf_fuse_pipeline_*, gsf_fuse_pipeline_robust_*, gsf_run_fusion_batch_*) on this context
@@ -577,6 +580,55 @@ GSF_API int gsf_ekf_cov_ragged_dev(gsf_ctx *ctx, const double *ts, const double 
 GSF_API int gsf_ekf_cov_ragged(gsf_ctx *ctx, const double *ts, const double *quat, const double *gps, const uint8_t *valid,
                                const int64_t *offsets, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
                                double *cov_filt, double *cov_out, uint8_t *pose_flags, int32_t *status);
+
+/* ---- EKF noise sweep: innovation statistics of the filter for K noise candidates per track ------------------------------------------------
+   CONFIG['ekf'] (initial_cov_diag, process_noise_diag, meas_noise_diag, EKFGPSSLAM.py:25-27) is tuned by hand; the standard way to choose
+   and check such values is the filter's own innovation sequence: its normalised innovation squared (NIS; mean 3 for a consistent 3-axis
+   filter), its Gaussian negative log-likelihood and its whiteness.  This entry runs the position filter of apply_ekf_correction for K
+   candidates at once and returns the sums those figures are made of.  GNSS never touches the state quaternion, so the world-frame odometry
+   increments are the same for every candidate; RTS rewrites outputs only (:918-922), so the innovations do not depend on it.
+   In: ts, pos, quat, gps, valid, offsets, init_pos, init_quat, cfg as in gsf_ekf_fuse_ragged_dev; run_status as in gsf_ekf_cov_ragged_dev
+   (may be NULL); cand[K][9] = { P0x, P0y, P0z, Qx, Qy, Qz, Rx, Ry, Rz } per candidate, a DEVICE array, values inside the range stated at
+   gsf_ekf_config (outside it: undocumented, as for cfg).  From cfg, shared by all candidates: the sharp-turn threshold and
+   default_ekf_transition_steps_on_sharp_turn (its position noise is not read; its quaternion axes influence no innovation).
+   For track b, candidate k, axis c in {0, 1, 2}, with dt[i] = max(1e-6, ts[i] - ts[i-1]) (:865) and avail[i] as in gsf_ekf_cov_ragged_dev
+   (:867-869), p[0] = init_pos[b], Pf[0] = P0:
+   - prediction (_predict, :702-715): p-[i] = p[i-1] + d[i], Pp[i] = Pf[i-1] + Q dt[i]; d[i] = R(q_state[i-1]) dp_local[i] from
+     calculate_relative_pose (:77-92) and the state quaternion chain, formed as the fuse kernels form it.
+   - update, on avail[i]: y[i] = z[i] - p-[i] (:722), S[i] = Pp[i] + R (:723), g = Pp / S, Pf = (1-g)^2 Pp + g^2 R (:731),
+     p[i] = p-[i] + w[i] g y[i].  w[i] = 1 except at the recovery pose of an outage judged a sharp turn when steps =
+     default_ekf_transition_steps_on_sharp_turn > 1: there w = 1 / steps, the one-step blend of :752-768 with the override of :889, :899; the
+     covariance is the updated one (:767).  The sharp-turn decision is gsf_ekf_cov_ragged_dev's; outages of fewer than 2 poses are hard
+     updates (:893-894).
+   - without a usable fix: p[i] = p-[i], Pf = Pp.
+   - counted updates U = { i >= 1 : avail[i] and ts[i] > ts[0] + skip_seconds } (the burn-in of step 6, :1018); skip_seconds <= 0 counts
+     every update.  Normalised innovation nu = y / sqrt(S).
+   Out (each may be NULL):
+   stats[B][K][12] = { n_upd = |U|;  sum_U y_c^2 / S_c, c = 0..2 (NIS per axis);  sum_U log S_c;  sum_U y_c^2 (in the stamps' length unit
+     squared);  sum_c sum nu_c[i] nu_c[i-1] over the pairs with i and i-1 both in U;  the number of such pairs }.  Entries 0 and 11 are the
+     same for every candidate.  Derived (the Python binding computes them): nll = (3 n_upd ln 2pi + sum stats[4..6] + sum stats[1..3]) / 2,
+     mean_nis = sum stats[1..3] / n_upd, rho1 = stats[10] / (3 stats[11]).
+   best_k[B][2] = the first k with the smallest nll (criterion 0) and the first k with the smallest |mean_nis - 3| (criterion 1); -1 when
+     n_upd < min_updates.  A candidate whose row is not finite is never picked.
+   pooled[K][12] = the sum of the rows of all tracks with run_status[b] == 0, at least one pose and n_upd >= min_updates, added in ascending
+     b by one fixed-order pass (no atomics: the bytes are reproducible); pooled_best[2] = the picks over the pooled rows.  Noise is a
+     property of the receiver, not of one run, so the pooled pick is the one to use.
+   ns_status[B] = GSF_NS_* bits.
+   innov[P][3] / innov_var[P][3] = y and S of candidate trace_k (0 <= trace_k < K; negative: no trace) on every pose with an update,
+     whatever skip_seconds says, NaN elsewhere.
+   An empty track gets rows of zeros, best_k = -1 and GSF_NS_NONE.  A track with run_status[b] != 0 gets NaN rows (stats and trace),
+   best_k = -1 and GSF_NS_NONE, and its inputs are not read.  1 <= K <= 4096, any track length.  One wave per (track, group of candidates),
+   64 poses per chunk, 89 B read per pose and group, nothing written per pose; gsf_set_option "noise_sweep_group" sets the group size, and a
+   candidate's row is the same bytes for every group size.  Where stats (or pooled, with pooled_best given) is NULL and a pick is asked
+   for, the rows live in the context's kernel workspace.  Device pointers, asynchronous on the context's stream.  There is no host-pointer
+   form: the Python binding uploads host arrays itself. */
+#define GSF_NS_NONE 1      /* no pick: fewer than min_updates counted updates, or no candidate with a finite row */
+#define GSF_NS_TIE 2       /* the two criteria pick different candidates */
+GSF_API int gsf_ekf_noise_sweep_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
+                                    const uint8_t *valid, const int64_t *offsets, const int32_t *run_status, const double *init_pos,
+                                    const double *init_quat, const gsf_ekf_config *cfg, int64_t B, const double *cand, int32_t K,
+                                    double skip_seconds, int32_t min_updates, int32_t trace_k, double *stats, int32_t *best_k,
+                                    double *pooled, int32_t *pooled_best, int32_t *ns_status, double *innov, double *innov_var);
 
 /* ---- pose queries: the fused track at any stamp, sensor points into the track's frame ----------------------------------------------------
    The fused track exists at the SLAM stamps; LiDAR returns, other exposures, map points and a second receiver have stamps of their own.
