@@ -4,29 +4,45 @@
 // The one-wave kernel (gsf_ekf_wave.hip) asks for the track's rows and then issues nothing until they are back; its chunk loop then runs
 // the two Moebius scans of the variance recursion in every chunk.  That recursion depends on the stamps and on which fixes are used --
 // nine of the ~70 bytes per pose the burst moves.  This build
-//   1. requests the stamps and mask bytes of EVERY chunk first, then the fix columns, the SLAM positions and chunk 0's quaternions
-//      (vmcnt retires loads in issue order: the first columns asked for are the first ones back -- measured ~3 000 cycles ahead of the last);
+//   1. requests the stamps and mask bytes of EVERY chunk first, then chunk after chunk the fix and the SLAM position, then chunk 0's
+//      quaternions (vmcnt retires loads in issue order and nothing is stored before the chunk loop: a use of chunk k's registers waits for
+//      chunk k alone; the stamps are back ~3 000 cycles ahead of the last column);
 //   2. waits for stamps and mask bytes ALONE and takes a set mask byte to mean a usable fix (true of every row the generator, the loaders
 //      and time_align_kernel produce; a NaN fix under a set mask byte is the reference's demotion quirk, see 4);
 //   3. runs the local scans of the first GSF_EARLY_CHUNKS chunks side by side in one basic block, applies the carried variance chunk after
 //      chunk and writes P_f, P_p and the gain of their poses into LDS, in the layout of the two-wave kernel's helper.  Only what fits the
 //      shadow of the burst is done here: a chunk's scans are ~1 400-1 700 cycles of issue, and every cycle past the arrival of the rows
 //      delays the fit by as much as the chunk loop gains (all chunks early: +1.3 us; HISTORY.md, "Early variances");
-//   4. runs the fit on the rows it requested in 1 (the fit passes take them as RoundRows, nothing is loaded twice, pose 0 comes from lane 0)
-//      and learns from the fit pass's exact validity masks whether a row of those chunks has its mask byte set and a NaN in its fix.  If
-//      so those chunks' part of the table is formed again from memory, with the NaN test, wave-uniformly;
+//  2b. chooses the rows of the fit (the reference's rule, ref :973-998) from the same stamps and mask bytes, still in the shadow: the
+//      per-lane compares here, the wave-uniform decisions in gsf_rows_rule.hpp (first gap, V[:k], duration limit, both fall-backs as
+//      decisions on popcounts -- no second pass).  One lane mask per chunk comes out, the count, the row flag, and dep_end: the rows whose
+//      validity the choice depends on;
+//   4. sums the fit's moments chunk by chunk AS THE CHUNKS ARRIVE, under those masks, and forms each chunk's exact validity mask from its
+//      fix.  Under the reference's rule a chunk in front of dep_end whose exact mask is not the assumed one (a NaN under a set byte;
+//      wave-uniform, rare) drops the sums: the one-wave kernel's pass, fit_moments_reference_rows, runs unchanged on the held rows.  Chunks
+//      behind dep_end (behind the gap's row of a track that fits its first segment) are not waited for.  Under "every valid row" nothing is
+//      assumed or chosen: the exact masks, then one block of sums, as in the one-wave kernel's pass.  The closed form (fit_from_partials) is the one-wave kernel's.  A miss in
+//      an early chunk forms that part of the table again from memory, with the NaN test, wave-uniformly;
 //   5. runs wave_serial_chunks<PIPELINE, PREVAR = true, ..., PVCHUNKS>: the first chunks read the table as the two-wave kernel's main wave
 //      does, the chunks behind them run their scans as the one-wave kernel does.  There is one chunk loop per build, chosen by nothing.
+// No load may stay pending on a rare path of 2b or 4: where paths meet the wave would wait for it with vmcnt(0), i.e. for the whole burst.
+// Single stamps and the shift of a track whose first valid row is not row 0 therefore come out of the registers (v_readlane), not from memory.
 // One wave per block: no barrier, no wait on another wave; a wave's LDS operations complete in order.
 // Same functions on the same operands in the same order as the one-wave kernel -- the guarantee the two-wave build gives -- so every
 // output byte is the same.  The builds are OVERLOADS of ekf_wave_kernel<PIPELINE, SMALLBATCH, AXMODE> (the build travels in the
 // argument's type, as WaveArgsTail does), keyed by the number of chunks and by the sizing of the last chunk's scans.
 // The table holds the early chunks only: 9 x 64 x GSF_EARLY_CHUNKS x 8 bytes of dynamic LDS, 4.5 KB for one chunk.
 #include "gsf_wave_common.hpp"
+#include "gsf_rows_rule.hpp"
 
 using namespace gsf;
 
 namespace {
+
+// The row choice in the shadow of the burst (1) or behind the arrival of every row (0, the A/B form; HISTORY.md, "Early rows")
+#ifndef GSF_EARLY_RULE
+#define GSF_EARLY_RULE 1
+#endif
 
 static_assert(GSF_ROWS_ROUND == 6, "the early-variance build hands the fit passes ONE round of six chunks");
 
@@ -52,6 +68,8 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     // ---- 1. the whole track is ONE round of the fit's row pass: requested here, in the order in which it is needed
     int stride = pv_stride; double cPx = cfg.P0[0], cPz = cfg.P0[2];      // (fetched here, with the other kernel arguments: see 3)
     asm volatile("" : "+s"(stride), "+s"(cPx), "+s"(cPz));
+    int rows_mode = a.rows.mode, rows_ms = a.rows.min_samples; double rows_gap = a.rows.max_gap, rows_dur = a.rows.max_dur;   // (the row rule's, for 2b)
+    asm volatile("" : "+s"(rows_mode), "+s"(rows_ms), "+s"(rows_gap), "+s"(rows_dur));
     RoundRows<6> rr;
     int il[NCH];
 #pragma unroll
@@ -61,10 +79,11 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     for (int k = 0; k < NCH; ++k) { rr.pt[k] = tsb[il[k]]; vb[k] = valb[il[k]]; }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int k = 0; k < NCH; ++k) { rr.pz[k][0] = gpsb[il[k] * 3]; rr.pz[k][1] = gpsb[il[k] * 3 + 1]; rr.pz[k][2] = gpsb[il[k] * 3 + 2]; }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) { rr.pa[k][0] = posb[il[k] * 3]; rr.pa[k][1] = posb[il[k] * 3 + 1]; rr.pa[k][2] = posb[il[k] * 3 + 2]; }
+    for (int k = 0; k < NCH; ++k) {                                       // chunk after chunk: the fix, then the SLAM position (a use of chunk k waits for chunk k alone)
+        rr.pz[k][0] = gpsb[il[k] * 3]; rr.pz[k][1] = gpsb[il[k] * 3 + 1]; rr.pz[k][2] = gpsb[il[k] * 3 + 2];
+        rr.pa[k][0] = posb[il[k] * 3]; rr.pa[k][1] = posb[il[k] * 3 + 1]; rr.pa[k][2] = posb[il[k] * 3 + 2];
+        __builtin_amdgcn_sched_barrier(0);
+    }
     // chunk 0 of the chunk loop: its stamp, position, fix and mask byte ARE the round's first chunk; only the quaternion is its own
     ChunkIn nxt;
     nxt.q = Quat{ __builtin_nontemporal_load(&quatb[il[0] * 4]), __builtin_nontemporal_load(&quatb[il[0] * 4 + 1]),
@@ -118,15 +137,145 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     __builtin_amdgcn_sched_barrier(0);
     GSF_STAMP(13);                                                       // variance table written (the timing tools run five-chunk tracks: 13 is free there)
 
-    // ---- 4. the fit, on the rows requested above
+    // ---- 2b. the row choice (ref :973-998) from stamps and mask bytes, under the assumption of 2: which rows the fit sums, as one lane mask
+    // per chunk, before a row has been summed -- the fall-backs of the rule are decisions on popcounts (gsf_rows_rule.hpp), not second passes
+#if !GSF_EARLY_RULE                                                       // A/B form (a): the rule behind the arrival of every row
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) asm volatile("" :: "v"(rr.pz[k][0]), "v"(rr.pz[k][1]), "v"(rr.pz[k][2]), "v"(rr.pa[k][0]), "v"(rr.pa[k][1]), "v"(rr.pa[k][2]) : "memory");
+#endif
+    u64 av[6];                                                            // rows of the track whose mask byte is set
+#pragma unroll
+    for (int k = 0; k < 6; ++k) av[k] = k < NCH ? (mask_first(Ni - 64 * k) & mask_nonzero(rr.pv[k])) : 0ull;
+    int k0, l0;
+    const bool anyv = rows_first_valid<6>(av, k0, l0), first0 = (av[0] & 1ull) != 0ull;   // (the usual track: its very first row is valid)
+    const int i0 = anyv ? 64 * k0 + l0 : 0;
+    RowsChoice<6> ch;
+    if (rows_mode != 0) {                                                 // wave-uniform
+        // single stamps come out of the registers that hold them (the row is wave-uniform: a v_readlane), never from memory: a load on this
+        // path would make the wave wait for the whole burst (vmcnt retires in order), and for a round trip of its own on top
+        const auto stamp_at = [&](const int i) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) if ((i >> 6) == k) t = lane_bcast(rr.pt[k], i & 63);
+            return t;
+        };
+        double tfirst = lane_bcast(rr.pt[0], 0);
+        if (!first0) { asm volatile("" ::: "memory"); tfirst = stamp_at(i0); }   // (a real branch, not if-conversion)
+        const double max_gap = rows_gap, tlim = tfirst + rows_dur;   // segment_start_time + max_dur (:989-990)
+        u64 graw[6], le[6]; double tb = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            if (k < NCH) {
+                const double tp = prev_lane(tb, rr.pt[k]);                // stamp of row i - 1
+                tb = lane_bcast(rr.pt[k], 63);
+                graw[k] = mask_gt(rr.pt[k] - tp, max_gap); le[k] = mask_le(rr.pt[k], tlim);
+            } else { graw[k] = 0ull; le[k] = 0ull; }
+        }
+        rows_rule_choose<6>(av, graw, le, Ni, rows_ms, max_gap, stamp_at, ch);
+    } else {                                                              // every valid row: nothing to choose
+        ch.nT = 0; ch.rows_flag = 0; ch.row_end = Ni; ch.nF = 0; ch.dep_end = Ni;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { ch.mo[k] = av[k]; ch.nT += __popcll(av[k]); }
+    }
+    GSF_STAMP(15);                                                       // the rows of the fit are chosen
+
+    // ---- 4. the fit: chunk k is summed when chunk k is back (vmcnt retires loads in the order of 1).  Its fix gives its exact validity mask.
+    // Every valid row (rows mode 0): those masks ARE the rows summed, nothing was assumed (one block, see there).  The reference's rule: the chunk is summed
+    // under the mask of 2b; where the exact mask differs from the assumed one in a chunk the choice depends on, the sums are dropped and the
+    // one-wave kernel's pass runs on the held rows, unchanged.  Rows behind dep_end -- behind the gap's row, when the fit takes the first
+    // segment -- cannot change the choice (gsf_rows_rule.hpp) and are not waited for: a NaN there is the chunk loop's business alone.
+    // Same expressions, same order of additions over the chunks, same shifts, the count from the same popcounts as those passes: same bits.
     nxt.t = rr.pt[0]; nxt.v = rr.pv[0];
-    nxt.p = Vec3{ rr.pa[0][0], rr.pa[0][1], rr.pa[0][2] };
-    nxt.z = Vec3{ rr.pz[0][0], rr.pz[0][1], rr.pz[0][2] };
     Vec3 p0; Quat q0; int32_t fit = 0;
     rr.nearly = NE;
-    { const Quat q0l = lane_bcast(nxt.q, 0); rr.q0[0] = q0l.x; rr.q0[1] = q0l.y; rr.q0[2] = q0l.z; rr.q0[3] = q0l.w; }
-    u64 miss = 0ull;                                                     // rows on which the assumption of 2 does not hold, from the fit pass's own masks
-    if (!wave_prelude<PIPELINE, true>(a, b, base, N, lane, p0, q0, fit, &rr, &miss)) return;   // (fit None, bad pose-0 quaternion: the table is never read)
+    u64 miss = 0ull;                                                     // rows of the early chunks on which the assumption of 2 does not hold
+    double sums[17], bs_[3]; int32_t rows_flag = ch.rows_flag;
+    const double as0 = lane_bcast(rr.pa[0][0], 0), as1 = lane_bcast(rr.pa[0][1], 0), as2 = lane_bcast(rr.pa[0][2], 0);   // pose 0 sits in lane 0
+    double Sa0 = 0, Sa1 = 0, Sa2 = 0, Sb0 = 0, Sb1 = 0, Sb2 = 0, Saa = 0;
+    double Sab[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    double bs0 = lane_bcast(rr.pz[0][0], 0), bs1 = lane_bcast(rr.pz[0][1], 0), bs2 = lane_bcast(rr.pz[0][2], 0);
+    int nsum = 0; u64 bad = 0ull;
+#define GSF_EARLY_SUM(k_, o_)                                                                                                                      \
+    {                                                                                                                                              \
+        const double a0 = o_ ? rr.pa[k_][0] - as0 : 0.0, a1 = o_ ? rr.pa[k_][1] - as1 : 0.0, a2 = o_ ? rr.pa[k_][2] - as2 : 0.0;                  \
+        const double b0 = o_ ? rr.pz[k_][0] - bs0 : 0.0, b1 = o_ ? rr.pz[k_][1] - bs1 : 0.0, b2 = o_ ? rr.pz[k_][2] - bs2 : 0.0;                  \
+        Sa0 += a0; Sa1 += a1; Sa2 += a2; Sb0 += b0; Sb1 += b1; Sb2 += b2;                                                                        \
+        Saa += a0 * a0 + a1 * a1 + a2 * a2;                                                                                                       \
+        Sab[0] += a0 * b0; Sab[1] += a0 * b1; Sab[2] += a0 * b2;                                                                                  \
+        Sab[3] += a1 * b0; Sab[4] += a1 * b1; Sab[5] += a1 * b2;                                                                                  \
+        Sab[6] += a2 * b0; Sab[7] += a2 * b1; Sab[8] += a2 * b2;                                                                                  \
+    }
+    if (rows_mode != 0) {
+        if (!first0) {                                                    // the first valid row is not row 0: the GNSS-side shift (:988)
+            asm volatile("" ::: "memory");                               // (a real branch, not if-conversion)
+            bs0 = bs1 = bs2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < NCH; ++k)                                 // (from the registers that hold the row: its chunk alone is waited for)
+                if (anyv && (i0 >> 6) == k) { bs0 = lane_bcast(rr.pz[k][0], i0 & 63); bs1 = lane_bcast(rr.pz[k][1], i0 & 63); bs2 = lane_bcast(rr.pz[k][2], i0 & 63); }
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (k < NE || 64 * k < ch.dep_end) {                          // wave-uniform
+                const u64 exk = av[k] & mask_not_nan(rr.pz[k][0]) & mask_not_nan(rr.pz[k][1]) & mask_not_nan(rr.pz[k][2]);
+                bad |= av[k] & ~exk;
+                if (k < NE) miss |= av[k] & ~exk & ~(k == 0 ? 1ull : 0ull);
+                if (k == NCH - 1) GSF_STAMP(1);                           // the last chunk's fix has arrived
+            }
+            nsum += __popcll(ch.mo[k]);
+            if (ch.mo[k] != 0ull) {                                       // wave-uniform (a track with a gap sums its first segment only)
+                const bool o = __builtin_amdgcn_inverse_ballot_w64(ch.mo[k]);
+                GSF_EARLY_SUM(k, o)
+            }
+        }
+    } else {
+        // every valid row: nothing was assumed and nothing is chosen -- the exact masks of all chunks, then one straight block of sums, as the
+        // one-wave kernel's pass has it.  (Summed chunk by chunk as the rule's path does, this mode measured 0.16-0.3 us SLOWER than the
+        // parent: HISTORY.md, "Early rows".)
+        u64 mok[NCH];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            mok[k] = av[k] & mask_not_nan(rr.pz[k][0]) & mask_not_nan(rr.pz[k][1]) & mask_not_nan(rr.pz[k][2]);
+            if (k < NE) miss |= av[k] & ~mok[k] & ~(k == 0 ? 1ull : 0ull);
+        }
+        GSF_STAMP(1);                                                     // the rows have arrived
+        if ((mok[0] & 1ull) == 0ull) {                                    // the first valid row is not row 0
+            asm volatile("" ::: "memory");                               // (a real branch, not if-conversion)
+            u64 ex[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) ex[k] = k < NCH ? mok[k] : 0ull;
+            int ke, le_;
+            const bool have = rows_first_valid<6>(ex, ke, le_);
+            bs0 = bs1 = bs2 = 0.0;
+#pragma unroll
+            for (int k = 0; k < NCH; ++k)
+                if (have && ke == k) { bs0 = lane_bcast(rr.pz[k][0], le_); bs1 = lane_bcast(rr.pz[k][1], le_); bs2 = lane_bcast(rr.pz[k][2], le_); }
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            const bool o = __builtin_amdgcn_inverse_ballot_w64(mok[k]);
+            nsum += __popcll(mok[k]);
+            GSF_EARLY_SUM(k, o)
+        }
+    }
+#undef GSF_EARLY_SUM
+    sums[0] = (double)nsum;                                               // (wave-uniform: the count of the rows summed, from the masks)
+    sums[1] = Sa0; sums[2] = Sa1; sums[3] = Sa2; sums[4] = Sb0; sums[5] = Sb1; sums[6] = Sb2; sums[7] = Saa;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) sums[8 + k] = Sab[k];
+    bs_[0] = bs0; bs_[1] = bs1; bs_[2] = bs2;
+    if (bad != 0ull) {
+        // a NaN fix under a set mask byte where the choice looks (wave-uniform, rare): the one-wave kernel's pass, unchanged, on the held rows
+        asm volatile("" ::: "memory");                                   // (a real branch, not if-conversion)
+        fit_moments_reference_rows<6, true>(a, b, base, N, lane, as0, as1, as2, sums, bs_, rows_flag, &rr, &miss);
+    }
+    GSF_STAMP(2);
+    nxt.p = Vec3{ rr.pa[0][0], rr.pa[0][1], rr.pa[0][2] };
+    nxt.z = Vec3{ rr.pz[0][0], rr.pz[0][1], rr.pz[0][2] };
+    {
+        const double as_[3] = { as0, as1, as2 };
+        const Quat qraw0 = lane_bcast(nxt.q, 0);                          // pose 0's quaternion as stored: requested last, used after the closed form
+        if (!fit_from_partials(a, b, base, N, lane, sums, as_, bs_, qraw0, p0, q0, fit, rows_flag, true)) return;   // (fit None, bad pose-0 quaternion: the table is never read)
+    }
     if (miss != 0ull) {
         // a NaN fix under a set mask byte in the first NE chunks (wave-uniform, rare): their part of the table again, from memory, with the
         // NaN test -- the flags, the dt and the variance_chunk() of the chunk loop, as the two-wave kernel's helper forms them
