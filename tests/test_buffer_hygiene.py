@@ -218,9 +218,13 @@ def ragged_inputs(lengths, seed):
     return ts, pos, quat, gps, valid, offs, ip, iq
 
 
-@pytest.mark.parametrize("order", ["as-listed", "reversed"])
+RAGGED_BIG = 2049                                                        # the smallest ragged batch that takes the big-batch build (gsf_wave_route.hpp)
+
+
+@pytest.mark.parametrize("order", ["as-listed", "reversed", "tiled-to-2049"])
 def test_ekf_and_pipeline_ragged(B, monkeypatch, dirt, order):
-    lengths = RAGGED_LENGTHS if order == "as-listed" else RAGGED_LENGTHS[::-1]
+    lengths = {"as-listed": RAGGED_LENGTHS, "reversed": RAGGED_LENGTHS[::-1],
+               "tiled-to-2049": (RAGGED_LENGTHS * (RAGGED_BIG // len(RAGGED_LENGTHS) + 1))[:RAGGED_BIG]}[order]
     ts, pos, quat, gps, valid, offs, ip, iq = ragged_inputs(lengths, 40)
     assert ts.size == sum(lengths) and pos.shape == (ts.size, 3) and ip.shape == (len(lengths), 3)
     d = [dev(a) for a in (ts, pos, quat, gps)] + [dev(valid.astype(np.uint8)), dev(offs)]

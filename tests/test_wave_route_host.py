@@ -134,6 +134,19 @@ def test_headline_shapes_and_corners(hr):
     assert one(B=1000, N=0, ragged=1, block_kernel=1, duo_kernel=1, early_variances=1)[:2] == ("ONE", 6)
 
 
+def test_ragged_calls_change_build_between_2048_and_2049_tracks(hr):
+    """a ragged call takes the one-wave build up to 2 048 tracks and the big-batch build from 2 049 on (the batches of
+    tests/test_ragged_routes.py stand on either side), K4 and pipeline alike, always the six-stage instance, whatever the options say"""
+    for bk, dk, ev, ts, p, x in itertools.product(OPTS, OPTS, OPTS, (0, 1), (0, 1), (0, 1)):
+        c = dict(block_kernel=bk, duo_kernel=dk, early_variances=ev, tail_scan_stages=ts, pipeline=p, xy=x, ragged=1, N=0)
+        got = route(hr, [{**c, "B": 2048}, {**c, "B": 2049}, {**c, "B": 253}])
+        assert [g[:2] for g in got] == [("ONE", 6), ("BIG", 6), ("ONE", 6)], (c, got)
+    # block_kernel = 1 takes a dense call of the same shape, never a ragged one
+    dense = dict(DEFAULTS, block_kernel=1, pipeline=1, xy=1, ragged=0, B=2049, N=271)
+    assert route(hr, [dense])[0][0] == "BLOCK" and route(hr, [dict(dense, ragged=1, N=0)])[0][0] == "BIG"
+    assert route(hr, [dict(dense, B=2048)])[0][0] == "BLOCK" and route(hr, [dict(dense, B=2048, ragged=1, N=0)])[0][0] == "ONE"
+
+
 def test_noise_layout_predicate(hr):
     d = lambda *v: np.array(v, np.float64)
     assert hr.hr_xy(d(1, 1, 2), d(3, 3, 3), d(4, 4, 4)) == 1                         # x and y alike, z differs in one of the three
