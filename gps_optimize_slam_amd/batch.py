@@ -1123,6 +1123,134 @@ def sweep_noise_fused(rb, r, candidates, config=None, skip_seconds=0.0, min_upda
                                   run_status=r.run_status, skip_seconds=skip_seconds, min_updates=min_updates, trace=trace)
 
 
+# ---------------------------------------------------------------------------- GNSS outage study (gsf_outage_study_dev)
+def outage_scenarios(starts, lengths):
+    """Scenarios for outage_study_ragged: every combination of starts x lengths (both in the stamps' unit, starts relative to a track's first
+    stamp) as a (K, 2) float64 numpy array of rows [start, length], length-major: scenario k = il * len(starts) + is_."""
+    import numpy as np
+    st, ln = (np.asarray(list(v) if not np.isscalar(v) else [v], dtype=np.float64).reshape(-1) for v in (starts, lengths))
+    K = st.size * ln.size
+    if not 1 <= K <= 4096:
+        raise ValueError(f"outage_scenarios: {K} scenarios, 1..4096 per call")
+    out = np.empty((ln.size, st.size, 2))
+    out[..., 0] = st[None, :]
+    out[..., 1] = ln[:, None]
+    return np.ascontiguousarray(out.reshape(K, 2))
+
+
+_OS_UNUSABLE = _lib.OS_EMPTY | _lib.OS_UNSORTED | _lib.OS_SKIPPED
+
+
+class OutageStudy:
+    """Result of outage_study_ragged for B tracks x K scenarios (definitions: include/gsf.h, gsf_outage_study_dev).  Device tensors: stats
+    (B,K,13); seg (B,K,2) int32 = the outage [a, b) of every scenario, relative to its track; flags (B,K) int32 of _lib.OS_* bits; rms_dr /
+    rms_fused (B,K) = sqrt(sum e^2 / |E|) dead-reckoned and fused (NaN where E is empty); drift_pct (B,K) = 100 |y| at the recovery / distance
+    travelled; err_dr / err_fused (P,) and trace_pos (P,3) of the traced scenario (None without trace); scenarios (K,2)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def usable(self):
+        """(B,K) bool: rows with none of EMPTY | UNSORTED | SKIPPED and at least one evaluated pose"""
+        return ((self.flags & _OS_UNUSABLE) == 0) & (self.stats[..., 0] > 0)
+
+    def curve(self):
+        """Per distinct scenario length, pooled over the usable rows of all tracks and starts (torch reductions on the device): a dict of
+        (n_lengths,) float64 tensors 'length', 'rows', 'rms_dr', 'rms_fused', 'max_dr', 'max_fused', 'mean_gap', 'mean_dist',
+        'mean_recovery_nis' (over the rows with a recovery), 'share_smoothed', 'share_sharp'.  NaN where a length has no usable row."""
+        st, fl = self.stats, self.flags
+        lengths = torch.unique(self.scenarios[:, 1][~torch.isnan(self.scenarios[:, 1])])
+        ok = self.usable()
+        out = {k: [] for k in ("rows", "rms_dr", "rms_fused", "max_dr", "max_fused", "mean_gap", "mean_dist", "mean_recovery_nis",
+                               "share_smoothed", "share_sharp")}
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=st.device)
+        for L in lengths:
+            m = ok & (self.scenarios[:, 1] == L)[None, :]
+            w = m.to(torch.float64)
+            n, nE = w.sum(), torch.where(m, st[..., 0], torch.zeros_like(w)).sum()       # (where, not a product: skipped rows hold NaN)
+            mean = lambda v, ww=w: torch.where(ww.sum() > 0, (torch.where(ww > 0, v, torch.zeros_like(v))).sum() / ww.sum(), nan)
+            rec = w * ((fl & _lib.OS_NO_RECOVERY) == 0).to(torch.float64)
+            out["rows"].append(n)
+            out["rms_dr"].append(torch.where(nE > 0, torch.sqrt((torch.where(m, st[..., 5], torch.zeros_like(w))).sum() / nE), nan))
+            out["rms_fused"].append(torch.where(nE > 0, torch.sqrt((torch.where(m, st[..., 7], torch.zeros_like(w))).sum() / nE), nan))
+            out["max_dr"].append(torch.where(n > 0, torch.where(m, st[..., 6], torch.zeros_like(w)).max(), nan))
+            out["max_fused"].append(torch.where(n > 0, torch.where(m, st[..., 8], torch.zeros_like(w)).max(), nan))
+            out["mean_gap"].append(mean(st[..., 3])); out["mean_dist"].append(mean(st[..., 4]))
+            out["mean_recovery_nis"].append(mean(st[..., 12], rec))
+            out["share_smoothed"].append(mean(((fl & _lib.OS_SMOOTHED) != 0).to(torch.float64)))
+            out["share_sharp"].append(mean(((fl & _lib.OS_SHARP_TURN) != 0).to(torch.float64)))
+        res = {k: (torch.stack(v) if v else torch.empty((0,), dtype=torch.float64, device=st.device)) for k, v in out.items()}
+        res["length"] = lengths
+        return res
+
+
+def outage_study_ragged(ts, pos, quat, gps, valid, offsets, init_pos, init_quat, scenarios, config=None, run_status=None, truth=None,
+                        truth_valid=None, trace=None):
+    """Drift and RTS gain of the fused track for K withheld GNSS windows per track, one launch chain on torch's current stream
+    (gsf_outage_study_dev).  Inputs as ekf_noise_sweep_ragged; the filter runs under config's own noise.  scenarios (K,2) rows
+    [start, length] in the stamps' unit, start relative to a track's first stamp (numpy or tensor; outage_scenarios builds a grid), shared by
+    all tracks.  truth (P,3) / truth_valid (P,) uint8: what the errors are measured against; both None: the fixes themselves.  trace = k:
+    per-pose errors and fused positions of scenario k.  Returns an OutageStudy."""
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid")
+    _chk(init_pos, torch.float64, (B, 3), "init_pos"); _chk(init_quat, torch.float64, (B, 4), "init_quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    if (truth is None) != (truth_valid is None):
+        raise ValueError("outage_study_ragged: truth and truth_valid go together (both None: the fixes themselves)")
+    if truth is not None:
+        _chk(truth, torch.float64, (P, 3), "truth"); _chk(truth_valid, torch.uint8, (P,), "truth_valid")
+    dev = ts.device
+    scen = torch.as_tensor(scenarios, dtype=torch.float64).to(dev).contiguous()
+    if scen.dim() != 2 or scen.shape[1] != 2 or not 1 <= int(scen.shape[0]) <= 4096:
+        raise ValueError(f"outage_study_ragged: scenarios must be (K, 2) with 1 <= K <= 4096, got {tuple(scen.shape)}")
+    K = int(scen.shape[0])
+    trace_k = -1 if trace is None else int(trace)
+    if trace is not None and not 0 <= trace_k < K:
+        raise ValueError(f"outage_study_ragged: trace = {trace_k} names no scenario (K = {K})")
+    cfg = EkfConfig.from_config(config or CONFIG)
+    f = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    tr = trace is not None
+    r = OutageStudy(stats=torch.empty((B, K, 13), **f), seg=torch.empty((B, K, 2), **i32), flags=torch.empty((B, K), **i32),
+                    err_dr=torch.empty((P,), **f) if tr else None, err_fused=torch.empty((P,), **f) if tr else None,
+                    trace_pos=torch.empty((P, 3), **f) if tr else None, scenarios=scen)
+    check(_lib.load().gsf_outage_study_dev(context().handle, _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(offsets), _p(run_status), _p(init_pos),
+                                           _p(init_quat), C.byref(cfg), B, _p(truth), _p(truth_valid), _p(scen), K, trace_k, _p(r.stats), _p(r.seg),
+                                           _p(r.flags), _p(r.err_dr), _p(r.err_fused), _p(r.trace_pos)))
+    r.rms_dr, r.rms_fused = torch.sqrt(r.stats[..., 5] / r.stats[..., 0]), torch.sqrt(r.stats[..., 7] / r.stats[..., 0])
+    r.drift_pct = 100.0 * r.stats[..., 11] / r.stats[..., 4]
+    return r
+
+
+def outage_study_fused(rb, r, scenarios, truth="primary", config=None, trace=None):
+    """outage_study_ragged on the result r of run_fusion_ragged / run_fusion_batch for the batch rb: the aligned fixes, their mask and
+    run_status are r's, the initial pose of every track is built as sweep_noise_fused builds it.  truth = "primary": errors against the
+    withheld fixes themselves; "gt": against the time-aligned ground-truth leg (r.gt_aligned / r.gt_valid; ValueError without one)."""
+    if truth not in ("primary", "gt"):
+        raise ValueError(f"outage_study_fused: truth must be 'primary' or 'gt', got {truth!r}")
+    tr = tv = None
+    if truth == "gt":
+        if getattr(r, "gt_aligned", None) is None or getattr(r, "gt_valid", None) is None:
+            raise ValueError("outage_study_fused: truth = 'gt' needs a run with a ground-truth leg (r.gt_aligned / r.gt_valid)")
+        tr, tv = r.gt_aligned.reshape(-1, 3), r.gt_valid.reshape(-1)
+    ts, pos, quat = rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4)
+    offsets = rb.slam_offsets
+    B, P = _offsets_chk(offsets), int(ts.numel())
+    dev = ts.device
+    if P == 0:
+        ip, iq = torch.zeros((B, 3), dtype=torch.float64, device=dev), torch.zeros((B, 4), dtype=torch.float64, device=dev)
+    else:
+        first = torch.clamp(offsets[:-1], max=P - 1)                      # (an empty track's row is never read)
+        one = torch.arange(B + 1, dtype=torch.int64, device=dev)
+        ip = r.sim3_pos.reshape(-1, 3)[first].contiguous()
+        _, iq, _ = apply_sim3_batch(pos[first].contiguous(), quat[first].contiguous(), one, r.R, r.t, r.s)
+    return outage_study_ragged(ts, pos, quat, r.aligned.reshape(-1, 3), r.valid.reshape(-1), offsets, ip, iq, scenarios, config=config,
+                               run_status=r.run_status, truth=tr, truth_valid=tv, trace=trace)
+
+
 class PoseQuery:
     """The fused track at query stamps (query_poses_ragged), flat over the M queries: pos (M,3), quat (M,4), flags (M,) uint8 of _lib.Q_* bits,
     index (M,) int32 = the bracket's first pose relative to its track (-1: none), pose_flags (M,) uint8 or None = the _lib.POSE_* bits of

@@ -9,6 +9,7 @@
 
 #include "gsf_internal.hpp"
 #include "gsf_sweep_core.hpp"
+#include "gsf_outage_core.hpp"
 
 namespace gsf {
 
@@ -685,6 +686,23 @@ int gsf_ekf_noise_sweep_dev(gsf_ctx* ctx, const double* ts, const double* pos, c
     GSF_REQUIRE(skip_seconds == skip_seconds, "skip_seconds is NaN");
     return launch_noise_sweep(ctx, ts, pos, quat, gps, valid, offsets, run_status, init_pos, init_quat, cfg, B, cand, K, skip_seconds, min_updates,
                               trace_k, stats, best_k, pooled, pooled_best, ns_status, innov, innov_var);
+}
+
+// GNSS outage study: device form only (include/gsf.h; the Python binding uploads host arrays itself)
+int gsf_outage_study_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                         const int64_t* offsets, const int32_t* run_status, const double* init_pos, const double* init_quat,
+                         const gsf_ekf_config* cfg, int64_t B, const double* truth, const uint8_t* truth_valid, const double* scen, int32_t K,
+                         int32_t trace_k, double* stats, int32_t* seg, int32_t* os_flags, double* err_dr, double* err_fused, double* trace_pos)
+{
+    GSF_REQUIRE(ctx && cfg && offsets, "ctx/cfg/offsets is NULL");
+    GSF_REQUIRE(B >= 0, "negative B");
+    GSF_REQUIRE(K >= 1 && K <= OUTAGE_MAX_K, "K must be in [1, 4096]");
+    GSF_REQUIRE(trace_k < K, "trace_k must be below K (negative: no trace)");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(ts && pos && quat && gps && valid && init_pos && init_quat && scen, "NULL array");
+    GSF_REQUIRE((truth == nullptr) == (truth_valid == nullptr), "truth and truth_valid go together (both NULL: the fixes themselves)");
+    return launch_outage_study(ctx, ts, pos, quat, gps, valid, offsets, run_status, init_pos, init_quat, cfg, B, truth, truth_valid, scen, K,
+                               trace_k, stats, seg, os_flags, err_dr, err_fused, trace_pos);
 }
 
 }  // extern "C"

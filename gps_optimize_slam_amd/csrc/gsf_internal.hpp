@@ -125,6 +125,12 @@ int launch_noise_sweep(gsf_ctx* ctx, const double* ts, const double* pos, const 
                        int32_t trace_k, double* stats, int32_t* best_k, double* pooled, int32_t* pooled_best, int32_t* ns_status,
                        double* innov, double* innov_var);
 
+// GNSS outage study (gsf_outage_study.hip): the body of gsf_outage_study_dev, arguments checked by the caller
+int launch_outage_study(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                        const int64_t* offsets, const int32_t* run_status, const double* init_pos, const double* init_quat,
+                        const gsf_ekf_config* cfg, int64_t B, const double* truth, const uint8_t* truth_valid, const double* scen, int32_t K,
+                        int32_t trace_k, double* stats, int32_t* seg, int32_t* os_flags, double* err_dr, double* err_fused, double* trace_pos);
+
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
 int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);
 int launch_gps_prefilter_auto(gsf_ctx* ctx, const double* t, const double* pos, const int64_t* offsets, const int32_t* counts, int64_t B,

@@ -522,6 +522,37 @@ def sweep_ekf_noise(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial, gl
             "status": int(r.status[0].item()), "innov": h(r.innov), "innov_var": h(r.innov_var), "candidates": h(r.candidates)}
 
 
+def study_gnss_outages(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial, global_config, scenarios, truth_gps_data=None, trace=None):
+    """Drift and RTS gain of apply_ekf_correction's track for K withheld GNSS windows on one track (gsf_outage_study_dev; definitions in
+    include/gsf.h): the same alignment call as apply_ekf_correction (ref :847), the initial pose = row 0 of the Sim3-transformed track.
+    scenarios (K,2) rows [start, length] in seconds, start relative to the first SLAM stamp (batch.outage_scenarios builds a grid).
+    truth_gps_data: a second GNSS log (e.g. ground truth) the errors are measured against, aligned by the same call; None: the withheld
+    fixes themselves.  Returns a dict of host arrays: 'stats' (K,13), 'seg' (K,2), 'flags' (K,) of _lib.OS_* bits, 'rms_dr' / 'rms_fused' /
+    'drift_pct' (K,), 'err_dr' / 'err_fused' (n,) and 'trace_pos' (n,3) of scenario `trace` (None without), 'scenarios' (K,2)."""
+    import torch
+    from . import batch as gb
+    n = len(slam_data["timestamps"])
+    sim3_pos_initial, sim3_quat_initial = np.asarray(sim3_pos_initial), np.asarray(sim3_quat_initial)
+    if n and not (sim3_pos_initial.shape[0] == n and sim3_quat_initial.shape[0] == n):
+        raise ValueError(f"Sim3-transformed trajectory length ({sim3_pos_initial.shape[0]}) != SLAM timestamp count ({n})")
+    aligned, valid = dynamic_time_alignment(slam_data, gps_data, global_config["time_alignment"])     # ref :847
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(shape)).to(dev)
+    tr = tv = None
+    if truth_gps_data is not None:
+        t_al, t_va = dynamic_time_alignment(slam_data, truth_gps_data, global_config["time_alignment"])
+        tr, tv = up(t_al, (n, 3)), up(t_va, (n,), np.uint8)
+    ip = sim3_pos_initial[0] if n else np.zeros(3)
+    iq = sim3_quat_initial[0] if n else np.array([0.0, 0.0, 0.0, 1.0])
+    r = gb.outage_study_ragged(up(slam_data["timestamps"], (n,)), up(slam_data["positions"], (n, 3)), up(slam_data["quaternions"], (n, 4)),
+                               up(aligned, (n, 3)), up(valid, (n,), np.uint8), torch.tensor([0, n], dtype=torch.int64, device=dev),
+                               up(ip, (1, 3)), up(iq, (1, 4)), scenarios, config=global_config, truth=tr, truth_valid=tv, trace=trace)
+    h = lambda t: None if t is None else t.cpu().numpy()
+    return {"stats": h(r.stats[0]), "seg": h(r.seg[0]), "flags": h(r.flags[0]), "rms_dr": h(r.rms_dr[0]), "rms_fused": h(r.rms_fused[0]),
+            "drift_pct": h(r.drift_pct[0]), "err_dr": h(r.err_dr), "err_fused": h(r.err_fused), "trace_pos": h(r.trace_pos),
+            "scenarios": h(r.scenarios)}
+
+
 def ekf_covariances(slam_data_in, gps_data_in, global_config):
     """The covariances apply_ekf_correction computes and drops, for one trajectory (host arrays): {"filtered": (n,7,7) = ekf_covs_filt_hist
     (ref :852, :902), "smoothed": (n,7,7) = the covariance of the pose apply_ekf_correction returns -- rts_smoother_segment's (ref :777-803)

@@ -630,6 +630,63 @@ GSF_API int gsf_ekf_noise_sweep_dev(gsf_ctx *ctx, const double *ts, const double
                                     double skip_seconds, int32_t min_updates, int32_t trace_k, double *stats, int32_t *best_k,
                                     double *pooled, int32_t *pooled_best, int32_t *ns_status, double *innov, double *innov_var);
 
+/* ---- GNSS outage study: drift and RTS gain of the fused track for K withheld windows per track ----------------------------------------------
+   How far does the fused track drift during a GNSS outage of L seconds, and how much of that does the per-outage RTS smoother take back?
+   The standard method withholds the fixes of a window, runs the fusion and measures against the withheld fixes.  This entry does that for
+   K windows per track at once.  GNSS never touches the state quaternion, so the world-frame odometry increments d[i] are the same in
+   every scenario; all covariances are diagonal; and a withheld window changes nothing before the outage it creates: one base pass per
+   track plus O(outage length) work per scenario gives the whole study.
+   In: ts, pos, quat, gps, valid, offsets, run_status, init_pos, init_quat, cfg as in gsf_ekf_noise_sweep_dev (cfg's own noise is used);
+   truth[P][3] / truth_valid[P] = what errors are measured against (both NULL: gps / valid; both or neither); scen[K][2] = { start, length }
+   in the stamps' unit, start relative to the track's first stamp, a DEVICE array shared by all tracks.
+   For track b (n poses, stamps t) and scenario (s, L), with avail[i] as in gsf_ekf_cov_ragged_dev (pose 0: the raw mask byte; every other
+   pose: the byte set and a fix free of NaN) and dt[i] = max(1e-6, t[i] - t[i-1]) (:865):
+   - stamps that are not non-decreasing, or a NaN stamp: GSF_OS_UNSORTED on every scenario of the track, NaN rows, seg = (-1, -1).
+   - window: lo = t[0] + s, hi = lo + L, W = the index range [#{t < lo}, #{t < hi}); s or L NaN, or L <= 0: W is empty.  An empty W gives
+     GSF_OS_EMPTY, a row of zeros and seg = (-1, -1).
+   - modified run: apply_ekf_correction with the mask bytes of W cleared, avail'[i] = avail[i] && i not in W.
+   - outage [a, b): the maximal run of !avail' that contains W; b = the recovery pose, or n when there is none (GSF_OS_NO_RECOVERY).
+     GSF_OS_MERGED: [a, b) is larger than W.  GSF_OS_FROM_START: a = 0.
+   - anchor c = max(a - 1, 0): the unmodified run's filtered position p_f[c] and variance Pf[c] are the modified run's as well.
+   - dead reckoning, a <= k < b: p_dr[k] = p_f[c] + sum_{c<i<=k} d[i], Pdr[k] = Pf[c] + Q sum_{c<i<=k} dt[i] per position axis (k = c = 0:
+     init_pos, P0).
+   - recovery, when b < n: p-[b], Pp[b] formed likewise; y = gps[b] - p-[b] (:722), S = Pp[b] + R (:723), g = Pp[b] / S.
+     sharp = (b - a >= 2) && (a pair (j-1, j) with a < j < b and t[j] > t[j-1] exceeds the yaw-rate threshold -- the pair test of
+     gsf_ekf_cov_ragged_dev, an invalid quaternion in the pair counts -- or threshold < 0) (:882-889, :826).
+   - fused position: not sharp: GSF_OS_SMOOTHED, p_fu[k] = p_dr[k] + (Pdr[k] / Pp[b]) g y per axis, the telescoped rts_smoother_segment
+     (:777-803; no pose of [a, b) takes an update, so the smoother gains multiply to Pdr[k] / Pp[b]).  Sharp (GSF_OS_SHARP_TURN) or no
+     recovery: p_fu = p_dr.  The one-step blend at a sharp recovery (:752-768) alters pose b only, which lies outside [a, b).
+   - evaluated set E = { k in [a, b) : truth_valid[k] and truth[k] free of NaN }; withheld updates H = { i in W : i >= 1, avail[i] };
+     e_dr[k] = |p_dr[k] - truth[k]|, e_fu[k] = |p_fu[k] - truth[k]| (Euclidean, 3-D).
+   Out (each may be NULL):
+   stats[B][K][13] = { |E|;  |H|;  b - a;  gap = t[min(b, n-1)] - t[c] (one subtraction of stamps);  dist = sum_{c<i<=min(b, n-1)} |d[i]|;
+     sum_E e_dr^2;  max_E e_dr;  sum_E e_fu^2;  max_E e_fu;  sum_E of the horizontal (x, y) part of e_dr^2;  the same of e_fu^2;  |y| at the
+     recovery;  NIS at the recovery sum_c y_c^2 / S_c }.  Entries 11 and 12 are NaN without a recovery; entries 6 and 8 are 0 where E is empty.
+     Derived (the Python binding computes them): rms_dr = sqrt(stats[5] / stats[0]), rms_fused = sqrt(stats[7] / stats[0]),
+     drift_pct = 100 stats[11] / stats[4].
+   seg[B][K][2] = (a, b) relative to the track.  os_flags[B][K] = GSF_OS_* bits.
+   err_dr[P], err_fused[P], trace_pos[P][3] = e_dr, e_fu and p_fu of scenario trace_k (0 <= trace_k < K; negative: no trace): errors are NaN
+     outside E, trace_pos is NaN outside [a, b).
+   An empty track gets GSF_OS_EMPTY rows.  A track with run_status[b] != 0 gets GSF_OS_SKIPPED: NaN rows (stats and trace), seg = (-1, -1),
+   and its inputs are not read.  A scenario's row does not depend on K, on the other scenarios, on their order or on the other tracks: it is
+   the same bytes in every call that holds it.  1 <= K <= 4096, any track length.  Base pass: one wave per track, 89 B read and 89 B written
+   per pose into the context's kernel workspace; scenario pass: one wave per (track, scenario), about 58 B read per pose of [a, b).
+   Device pointers; the launches are asynchronous on the context's stream, after one 8-byte read of offsets[B] (it sizes the workspace)
+   for which the call waits on that stream.  There is no host-pointer form: the Python binding uploads host arrays itself. */
+#define GSF_OS_EMPTY 1         /* the window holds no pose (or the track is empty): a row of zeros */
+#define GSF_OS_NO_RECOVERY 2   /* the outage runs to the end of the track */
+#define GSF_OS_SMOOTHED 4      /* the recovery hands [a..b] to the RTS smoother */
+#define GSF_OS_SHARP_TURN 8    /* the recovery is judged a sharp turn: [a, b) stays dead-reckoned */
+#define GSF_OS_MERGED 16       /* the outage is larger than the window: it merged with an outage of the data */
+#define GSF_OS_FROM_START 32   /* the outage begins at pose 0 */
+#define GSF_OS_UNSORTED 64     /* the track's stamps are not non-decreasing, or one is NaN: NaN rows */
+#define GSF_OS_SKIPPED 128     /* run_status[b] != 0: NaN rows, inputs not read */
+GSF_API int gsf_outage_study_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
+                                 const uint8_t *valid, const int64_t *offsets, const int32_t *run_status, const double *init_pos,
+                                 const double *init_quat, const gsf_ekf_config *cfg, int64_t B, const double *truth,
+                                 const uint8_t *truth_valid, const double *scen, int32_t K, int32_t trace_k, double *stats, int32_t *seg,
+                                 int32_t *os_flags, double *err_dr, double *err_fused, double *trace_pos);
+
 /* ---- pose queries: the fused track at any stamp, sensor points into the track's frame ----------------------------------------------------
    The fused track exists at the SLAM stamps; LiDAR returns, other exposures, map points and a second receiver have stamps of their own.
    These entries evaluate the track between its poses with the rule the filter itself uses for orientations (quaternion_nlerp,
