@@ -256,15 +256,18 @@ GSF_HD void svd3(const double* H, Svd3& out)
 //   Q by Newton's iteration X <- (g X + (1/g) X^-T)/2 from X0 = H/|H|_F with X^-T = cof(X)/det(X) (3x3 cofactors), three steps
 //   with Frobenius scaling g and four plain ones.  X and cof(X) share their singular vectors, so the accuracy of the two
 //   coefficients only steers convergence (hardware seeds suffice); the last step takes a full-precision 1/det.  Measured against
-//   a 40-digit SVD on 400 track-shaped H with sigma1/sigma3 from 3e3 to 2e14: |Q - Q_true| <= 2.9e-15 (NumPy's own SVD: 1e-13).
+//   the 50-digit polar factor of the same H (tests/test_sim3_yardstick_host.py::test_header_claims_of_gsf_math keeps these figures):
+//   400 track-shaped H with sigma1/sigma3 from 12 to 9e13: |Q - Q_true| <= 7.1e-15 (the Jacobi SVD below: 8.4e-15, NumPy's SVD:
+//   6.9e-13); with the reflection, sigma3/sigma2 up to 0.70: |R - R_true| (1 - sigma3/sigma2) <= 3.3e-15.
 //   det(H) < 0 (ref :441-442: the last row of Vt is negated) is R = (I - 2 v3 v3^T) Q^T with v3 the right singular vector of
 //   sigma3: cof(X0) = +-sum (sigma_j sigma_k) u_i v_i^T is dominated by u3 v3^T up to e = sigma3/sigma2.  For e < 3e-3 (the
 //   usual case) three steps of x <- cof^T (cof x) from its largest row (e^7); up to e = 0.33, B = cof^T cof squared five times
-//   (e^64).  A track whose vertical direction is noise has det(H) < 0 half of the time and e up to a few 0.1, so this case is not
+//   (e^64), up to e = 0.70 eight times (e^512).  A track whose vertical direction is noise has det(H) < 0 half of the time and e up to a few 0.1, so this case is not
 //   rare and has to be as cheap as the other.  (Rayleigh-quotient steps on P = Q^T H were tried: with sigma2/sigma1 ~ 1e-6 --
 //   straight tracks -- the adjugate of P - rho I loses the direction again: 4e-14 after the power steps, 7e-12 after two steps.)
 // Returns false -- the caller then takes the SVD -- for H that is zero / non-finite, singular to working precision, whose
-// reflection direction is not separated (sigma3/sigma2 > 0.33), or if the iteration did not land on an orthogonal matrix.
+// reflection direction is not separated (e0/nc20 >= 0.47, i.e. sigma3/sigma2 beyond about 0.70), or if the iteration did not land on
+// an orthogonal matrix.
 // ---------------------------------------------------------------------------------------
 GSF_HD void cof3(const double* X, double* C)                               // C = det(X) X^-T
 {

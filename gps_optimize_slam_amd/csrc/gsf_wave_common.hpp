@@ -646,7 +646,8 @@ __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b,
     int32_t fit = 0;
     if (PIPELINE) {
         // K2 on the rows with valid, finite GNSS, ONE pass: moments of the data shifted by pose 0 / the first finite fix
-        // (|shifted| <= track length, so the raw-moment form H = Sab - n ma mb^T loses nothing at UTM magnitudes), then K3
+        // (|shifted| <= track length, so the raw-moment form H = Sab - n ma mb^T pays nothing for the UTM magnitude; its rounding is that of
+        // the shifted products, see finalize_raw in gsf_sim3.hip -- larger than the two-pass form's only if pose 0 / that fix is an outlier), then K3
         // of pose 0.  Sums are per-lane partials + a DPP wave reduction.
         // The rows are read in rounds of MOM_ROUND chunks with every load of a round issued before the first use, so a 271-pose
         // track (the small-batch, latency-bound case) pays ONE memory round trip for the whole pass instead of one per chunk.

@@ -80,6 +80,50 @@ int hh_umeyama(const double* src, const double* dst, int64_t n, double* R, doubl
 int hh_umeyama_polar(const double* src, const double* dst, int64_t n, double* R, double* t, double* s) { return umeyama_impl(src, dst, n, R, t, s, true); }
 // 1 if umeyama_rotation_polar accepts H (else the SVD route is taken)
 int hh_polar_applies(const double* H) { double R[9], tr; return umeyama_rotation_polar(H, R, tr) ? 1 : 0; }
+// the rotation and singular-value sum of umeyama_rotation_polar itself (R, tr untouched where it declines)
+int hh_polar_rotation(const double* H, double* R, double* tr) { return umeyama_rotation_polar(H, R, *tr) ? 1 : 0; }
+// the rotation of the Jacobi-SVD route from H
+void hh_svd_rotation(const double* H, double* R, double* tr) { umeyama_rotation_svd(H, R, *tr); }
+
+// Host restatement of the ONE-PASS reductions (the short-set path of umeyama_batch_kernel and the window kernels of gsf_sim3.hip, the
+// moments pass of the fused pipeline): raw moments of the rows shifted by the first usable (unmasked, finite) row -- shift_last != 0: by
+// the last one, the edit tests/test_sim3_yardstick_host.py uses to show what the outlier twins catch -- in 16 strided partial sums, then
+// H = Sab - n ma mb^T and umeyama_finalize.  mask may be NULL.
+int hh_umeyama_shifted(const double* src, const double* dst, const uint8_t* mask, int64_t n, int polar, int shift_last, double* R, double* t, double* s)
+{
+    auto usable = [&](int64_t i) {
+        if (mask && !mask[i]) return false;
+        for (int k = 0; k < 3; ++k) if (!(fabs(src[i * 3 + k]) < INFINITY) || !(fabs(dst[i * 3 + k]) < INFINITY)) return false;
+        return true;
+    };
+    int64_t is = -1;
+    if (shift_last) { for (int64_t i = n - 1; i >= 0; --i) if (usable(i)) { is = i; break; } }
+    else { for (int64_t i = 0; i < n; ++i) if (usable(i)) { is = i; break; } }
+    if (is < 0) return SIM3_NONE;
+    double as[3], bs[3];
+    for (int k = 0; k < 3; ++k) { as[k] = src[is * 3 + k]; bs[k] = dst[is * 3 + k]; }
+    double part[16][17] = { { 0 } };                                      // per lane: n, Sa3, Sb3, Saa, Sab9
+    for (int64_t i = 0; i < n; ++i) {
+        if (mask && !mask[i]) continue;
+        double* p = part[i & 15];
+        double a[3], b[3];
+        for (int k = 0; k < 3; ++k) { a[k] = src[i * 3 + k] - as[k]; b[k] = dst[i * 3 + k] - bs[k]; }
+        p[0] += 1.0;
+        for (int k = 0; k < 3; ++k) { p[1 + k] += a[k]; p[4 + k] += b[k]; }
+        p[7] += a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) p[8 + r * 3 + c] += a[r] * b[c];
+    }
+    double tot[17] = { 0 };
+    for (int l = 0; l < 16; ++l) for (int k = 0; k < 17; ++k) tot[k] += part[l][k];
+    const double cnt = tot[0];
+    if (!(cnt >= 3.0)) return SIM3_NONE;
+    const double rn = 1.0 / cnt;
+    double ma[3], mb[3], H[9], sc[3], dc[3];
+    for (int k = 0; k < 3; ++k) { ma[k] = tot[1 + k] * rn; mb[k] = tot[4 + k] * rn; sc[k] = as[k] + ma[k]; dc[k] = bs[k] + mb[k]; }
+    for (int k = 0; k < 9; ++k) H[k] = tot[8 + k] - cnt * ma[k / 3] * mb[k % 3];
+    const double ssq = fmax(0.0, tot[7] - cnt * (ma[0] * ma[0] + ma[1] * ma[1] + ma[2] * ma[2]));
+    return polar ? umeyama_finalize<true>(H, ssq, sc, dc, cnt, R, t, *s) : umeyama_finalize(H, ssq, sc, dc, cnt, R, t, *s);
+}
 
 void hh_sincos(const double* x, int64_t n, double* s, double* c) { for (int64_t i = 0; i < n; ++i) gsf_sincos(x[i], s[i], c[i]); }
 
