@@ -1251,6 +1251,200 @@ def outage_study_fused(rb, r, scenarios, truth="primary", config=None, trace=Non
                                run_status=r.run_status, truth=tr, truth_valid=tv, trace=trace)
 
 
+# ---------------------------------------------------------------------------- innovation gate (gsf_innovation_gate_dev)
+GATE_MAX_K = 64
+
+
+def _chi2_cdf(x, dof):
+    import math
+    if dof == 1:
+        return math.erf(math.sqrt(x / 2.0))
+    if dof == 2:
+        return 1.0 - math.exp(-x / 2.0)
+    return math.erf(math.sqrt(x / 2.0)) - math.sqrt(2.0 * x / math.pi) * math.exp(-x / 2.0)
+
+
+def chi2_gate(p, dof=3):
+    """The p-quantile of the chi-square distribution with dof degrees of freedom: the gate below which a consistent filter's NIS falls
+    with probability p (3 dof: 0.95 -> 7.8147, 0.99 -> 11.3449, 0.999 -> 16.2662).  dof 2 has a closed form; dof 1 and 3 invert the CDF
+    (3 dof: erf(sqrt(x/2)) - sqrt(2x/pi) exp(-x/2)) by bisection with math.erf.  Other dof raise ValueError."""
+    import math
+    p = float(p)
+    if dof not in (1, 2, 3):
+        raise ValueError(f"chi2_gate: dof must be 1, 2 or 3, got {dof!r}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"chi2_gate: p must be in [0, 1), got {p!r}")
+    if dof == 2:
+        return -2.0 * math.log1p(-p)
+    lo, hi = 0.0, 1.0
+    while _chi2_cdf(hi, dof) < p:
+        hi *= 2.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            break
+        if _chi2_cdf(mid, dof) < p:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def _gates_arg(gates):
+    """gates of innovation_gate_ragged -> a float64 (K,) tensor, 1 <= K <= 64.  A sequence or a numpy array is a host array that the
+    binding uploads; a tensor is taken as the device array itself, so a host tensor is an error."""
+    if isinstance(gates, torch.Tensor):
+        if not gates.is_cuda:
+            raise ValueError("gates: a tensor must live on the device (pass a sequence or a numpy array to have it uploaded)")
+        if gates.dtype != torch.float64:
+            raise ValueError(f"gates: expected float64, got {gates.dtype}")
+        gt = gates
+    else:
+        import numpy as np
+        a = np.asarray(gates)
+        if a.dtype.kind not in "fiu":
+            raise ValueError(f"gates: expected numbers, got dtype {a.dtype}")
+        gt = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+    if gt.dim() != 1 or not 1 <= int(gt.shape[0]) <= GATE_MAX_K:
+        raise ValueError(f"gates: expected (K,) with 1 <= K <= {GATE_MAX_K}, got {tuple(gt.shape)}")
+    return gt
+
+
+class InnovationGate:
+    """Result of innovation_gate_ragged for B tracks x K gates (definitions: include/gsf.h, gsf_innovation_gate_dev).  Device tensors:
+    valid_out (K,P) uint8; stats (B,K,8) = n_avail, n_tested, n_rejected, n_forced, longest rejected run, first rejected pose (-1: none),
+    largest and summed NIS of the tested fixes that were applied; status (B,) int32 of _lib.GATE_* bits; nis_out (K,P) or None; gates
+    (K,); valid_in (P,) = the mask the gate started from; offsets (B+1,); init_pos / init_quat as passed in."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def _k(self, k):
+        k = int(k)
+        if not 0 <= k < int(self.gates.shape[0]):
+            raise ValueError(f"InnovationGate: no gate {k} (K = {int(self.gates.shape[0])})")
+        return k
+
+    def valid(self, k=0):
+        """(P,) uint8: the mask with gate k's rejected bytes cleared -- feed it to ekf_fuse_ragged / ekf_covariance_ragged"""
+        return self.valid_out[self._k(k)]
+
+    def rejected(self, k=0):
+        """(P,) bool: the poses whose fix gate k rejected (none on a track the gate skipped, whose bytes are all zero)"""
+        rej = (self.valid_in != 0) & (self.valid_out[self._k(k)] == 0)
+        if getattr(self, "status", None) is None or getattr(self, "offsets", None) is None:
+            return rej
+        skipped = (self.status & _lib.GATE_SKIPPED) != 0
+        n = self.offsets[1:] - self.offsets[:-1]
+        return rej & ~torch.repeat_interleave(skipped, n, output_size=int(rej.shape[0]))
+
+    def nis(self, k=0):
+        if self.nis_out is None:
+            raise ValueError("InnovationGate.nis: the call was made without want_nis")
+        return self.nis_out[self._k(k)]
+
+    @property
+    def reject_rate(self):
+        """(B,K): rejected / tested per track and gate (NaN where nothing was tested)"""
+        return self.stats[..., 2] / self.stats[..., 1]
+
+    def table(self):
+        """Per gate, pooled over the tracks that ran (no SKIPPED / EMPTY / UNSORTED bit): a dict of (K,) float64 tensors 'gate', 'tested',
+        'rejected', 'forced', 'reject_rate', 'longest_run' -- what a threshold is chosen from."""
+        bad = _lib.GATE_SKIPPED | _lib.GATE_EMPTY | _lib.GATE_UNSORTED
+        ok = ((self.status & bad) == 0)[:, None, None].expand_as(self.stats)
+        st = torch.where(ok, self.stats, torch.zeros_like(self.stats))    # (where, not a product: skipped rows hold NaN)
+        tested, rej = st[..., 1].sum(dim=0), st[..., 2].sum(dim=0)
+        longest = st[..., 4].max(dim=0).values if st.shape[0] else torch.zeros_like(tested)
+        return dict(gate=self.gates, tested=tested, rejected=rej, forced=st[..., 3].sum(dim=0), reject_rate=rej / tested, longest_run=longest)
+
+
+def innovation_gate_ragged(ts, pos, quat, gps, valid, offsets, init_pos, init_quat, gates, config=None, run_status=None, arm_seconds=0.0,
+                           max_run=0, want_nis=False):
+    """Chi-square gate on the filter's own innovations for K thresholds per track, one launch on torch's current stream
+    (gsf_innovation_gate_dev).  Inputs as ekf_noise_sweep_ragged; the filter runs under config's own noise.  gates: K thresholds on the
+    NIS, 1 <= K <= 64 (a sequence, a numpy array or a tensor on ts's device; chi2_gate gives quantiles; inf rejects nothing).  A fix is
+    tested once its stamp exceeds ts[0] + arm_seconds and rejected when its NIS is above the gate, unless the max_run fixes before it were
+    all rejected (max_run <= 0: no limit).  A rejected fix is a pose without a fix in every respect, so the returned masks go straight
+    into ekf_fuse_ragged / ekf_covariance_ragged.  want_nis: also the NIS of every usable fix, (K,P).  Returns an InnovationGate."""
+    gt = _gates_arg(gates)                                                # (first: these errors need no device)
+    arm_seconds = float(arm_seconds)
+    if arm_seconds != arm_seconds:
+        raise ValueError("innovation_gate_ragged: arm_seconds is NaN")
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid")
+    _chk(init_pos, torch.float64, (B, 3), "init_pos"); _chk(init_quat, torch.float64, (B, 4), "init_quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    dev = ts.device
+    gt = gt.to(dev).contiguous()
+    K = int(gt.shape[0])
+    cfg = EkfConfig.from_config(config or CONFIG)
+    g = InnovationGate(valid_out=torch.empty((K, P), dtype=torch.uint8, device=dev), stats=torch.empty((B, K, 8), dtype=torch.float64, device=dev),
+                       status=torch.empty((B,), dtype=torch.int32, device=dev),
+                       nis_out=torch.empty((K, P), dtype=torch.float64, device=dev) if want_nis else None, gates=gt, valid_in=valid, offsets=offsets,
+                       init_pos=init_pos, init_quat=init_quat, arm_seconds=arm_seconds, max_run=int(max_run))
+    check(_lib.load().gsf_innovation_gate_dev(context().handle, _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(offsets), _p(run_status), _p(init_pos),
+                                              _p(init_quat), C.byref(cfg), B, _p(gt), K, arm_seconds, int(max_run), _p(g.valid_out), _p(g.nis_out),
+                                              _p(g.stats), _p(g.status)))
+    return g
+
+
+def _fused_init_pose(rb, r):
+    """init_pos (B,3) / init_quat (B,4) of every track of a run_fusion_ragged result, as sweep_noise_fused builds them"""
+    ts, pos, quat = rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4)
+    offsets = rb.slam_offsets
+    B, P = _offsets_chk(offsets), int(ts.numel())
+    dev = ts.device
+    if P == 0:
+        return torch.zeros((B, 3), dtype=torch.float64, device=dev), torch.zeros((B, 4), dtype=torch.float64, device=dev)
+    first = torch.clamp(offsets[:-1], max=P - 1)                          # (an empty track's row is never read)
+    one = torch.arange(B + 1, dtype=torch.int64, device=dev)
+    ip = r.sim3_pos.reshape(-1, 3)[first].contiguous()
+    _, iq, _ = apply_sim3_batch(pos[first].contiguous(), quat[first].contiguous(), one, r.R, r.t, r.s)
+    return ip, iq
+
+
+def gate_fused(rb, r, gates, config=None, arm_seconds=0.0, max_run=0, want_nis=False):
+    """innovation_gate_ragged on the result r of run_fusion_ragged / run_fusion_batch for the batch rb: the aligned fixes, their mask and
+    run_status are r's, the initial pose of every track is built as sweep_noise_fused builds it."""
+    ip, iq = _fused_init_pose(rb, r)
+    return innovation_gate_ragged(rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4), r.aligned.reshape(-1, 3), r.valid.reshape(-1),
+                                  rb.slam_offsets, ip, iq, gates, config=config, run_status=r.run_status, arm_seconds=arm_seconds,
+                                  max_run=max_run, want_nis=want_nis)
+
+
+def refuse_gated(rb, r, g, k=0, want_cov=False, skip_seconds=5.0, config=None):
+    """Fuse again with gate k's mask: the existing ekf_fuse_ragged on g.valid(k) (g from gate_fused), optionally ekf_covariance_ragged on
+    the same mask, and step 6's nearest-fix error of the gated track against the fixes the gate kept (eval_errors_batch on the tracks
+    padded to one length; padded rows are not evaluated).  Tracks the run skipped (r.run_status != 0) are fused from whatever their rows
+    hold and should be ignored, as g.status says.  Returns a RunResult with pos (P,3), quat (P,4), status (B,), valid (P,), err_stats
+    (B,4) = count, mean, median, RMSE, errors (P,) (NaN where not evaluated) and cov (FusedCovariance or None)."""
+    ts, pos, quat = rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4)
+    aligned, offsets = r.aligned.reshape(-1, 3), rb.slam_offsets
+    vk = g.valid(k).contiguous()
+    po, qo, st = ekf_fuse_ragged(ts, pos, quat, aligned, vk, offsets, g.init_pos, g.init_quat, config=config)
+    cov = ekf_covariance_ragged(ts, quat, aligned, vk, offsets, config=config, run_status=r.run_status) if want_cov else None
+    B, P = _offsets_chk(offsets), int(ts.numel())
+    dev = ts.device
+    off = offsets.cpu().tolist()
+    N = max([off[b + 1] - off[b] for b in range(B)] + [1])
+    row = torch.arange(N, dtype=torch.int64, device=dev)[None, :]
+    n = (offsets[1:] - offsets[:-1])[:, None]
+    inside = row < n
+    idx = torch.clamp(offsets[:-1, None] + torch.minimum(row, torch.clamp(n - 1, min=0)), max=max(P - 1, 0))
+    if P == 0:
+        return RunResult(pos=po, quat=qo, status=st, valid=vk, err_stats=torch.zeros((B, 4), dtype=torch.float64, device=dev),
+                         errors=torch.empty((0,), dtype=torch.float64, device=dev), cov=cov)
+    dv = torch.where(inside, vk[idx], torch.zeros_like(vk[idx]))
+    stats, err = eval_errors_batch(ts[idx].contiguous(), po[idx].contiguous(), aligned[idx].contiguous(), dv.contiguous(), skip_seconds=skip_seconds)
+    errors = torch.full((P,), float("nan"), dtype=torch.float64, device=dev)
+    errors[idx[inside]] = err[inside]
+    return RunResult(pos=po, quat=qo, status=st, valid=vk, err_stats=stats, errors=errors, cov=cov)
+
+
 class PoseQuery:
     """The fused track at query stamps (query_poses_ragged), flat over the M queries: pos (M,3), quat (M,4), flags (M,) uint8 of _lib.Q_* bits,
     index (M,) int32 = the bracket's first pose relative to its track (-1: none), pose_flags (M,) uint8 or None = the _lib.POSE_* bits of

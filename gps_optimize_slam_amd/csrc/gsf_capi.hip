@@ -10,6 +10,7 @@
 #include "gsf_internal.hpp"
 #include "gsf_sweep_core.hpp"
 #include "gsf_outage_core.hpp"
+#include "gsf_gate_core.hpp"
 
 namespace gsf {
 
@@ -703,6 +704,22 @@ int gsf_outage_study_dev(gsf_ctx* ctx, const double* ts, const double* pos, cons
     GSF_REQUIRE((truth == nullptr) == (truth_valid == nullptr), "truth and truth_valid go together (both NULL: the fixes themselves)");
     return launch_outage_study(ctx, ts, pos, quat, gps, valid, offsets, run_status, init_pos, init_quat, cfg, B, truth, truth_valid, scen, K,
                                trace_k, stats, seg, os_flags, err_dr, err_fused, trace_pos);
+}
+
+// innovation gate: device form only (include/gsf.h; the Python binding uploads host arrays itself)
+int gsf_innovation_gate_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                            const int64_t* offsets, const int32_t* run_status, const double* init_pos, const double* init_quat,
+                            const gsf_ekf_config* cfg, int64_t B, const double* gates, int32_t K, double arm_seconds, int32_t max_run,
+                            uint8_t* valid_out, double* nis_out, double* stats, int32_t* gate_status)
+{
+    GSF_REQUIRE(ctx && cfg && offsets, "ctx/cfg/offsets is NULL");
+    GSF_REQUIRE(B >= 0, "negative B");
+    GSF_REQUIRE(K >= 1 && K <= GATE_MAX_K, "K must be in [1, 64]");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(ts && pos && quat && gps && valid && init_pos && init_quat && gates, "NULL array");
+    GSF_REQUIRE(arm_seconds == arm_seconds, "arm_seconds is NaN");
+    return launch_innovation_gate(ctx, ts, pos, quat, gps, valid, offsets, run_status, init_pos, init_quat, cfg, B, gates, K, arm_seconds, max_run,
+                                  valid_out, nis_out, stats, gate_status);
 }
 
 }  // extern "C"

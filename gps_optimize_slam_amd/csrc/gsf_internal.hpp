@@ -131,6 +131,12 @@ int launch_outage_study(gsf_ctx* ctx, const double* ts, const double* pos, const
                         const gsf_ekf_config* cfg, int64_t B, const double* truth, const uint8_t* truth_valid, const double* scen, int32_t K,
                         int32_t trace_k, double* stats, int32_t* seg, int32_t* os_flags, double* err_dr, double* err_fused, double* trace_pos);
 
+// innovation gate (gsf_gate.hip): the body of gsf_innovation_gate_dev, arguments checked by the caller
+int launch_innovation_gate(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                           const int64_t* offsets, const int32_t* run_status, const double* init_pos, const double* init_quat,
+                           const gsf_ekf_config* cfg, int64_t B, const double* gates, int32_t K, double arm_seconds, int32_t max_run,
+                           uint8_t* valid_out, double* nis_out, double* stats, int32_t* gate_status);
+
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
 int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);
 int launch_gps_prefilter_auto(gsf_ctx* ctx, const double* t, const double* pos, const int64_t* offsets, const int32_t* counts, int64_t B,

@@ -553,6 +553,34 @@ def study_gnss_outages(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial,
             "scenarios": h(r.scenarios)}
 
 
+def gate_gnss_fixes(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial, global_config, gates, arm_seconds=0.0, max_run=0, want_nis=False):
+    """Chi-square gate on the innovations of apply_ekf_correction's filter for K thresholds on one track (gsf_innovation_gate_dev;
+    definitions in include/gsf.h): the same alignment call as apply_ekf_correction (ref :847), the initial pose = row 0 of the
+    Sim3-transformed track.  gates: K thresholds on the NIS (batch.chi2_gate gives quantiles).  Returns a dict of host arrays: 'valid' (K,n)
+    uint8 = the aligned mask with each gate's rejected bytes cleared, 'rejected' (K,n) bool, 'stats' (K,8), 'status' (GATE_* bits of
+    _lib), 'nis' (K,n) or None, 'gates' (K,), 'aligned' (n,3) = the fixes the masks belong to."""
+    import torch
+    from . import batch as gb
+    n = len(slam_data["timestamps"])
+    sim3_pos_initial, sim3_quat_initial = np.asarray(sim3_pos_initial), np.asarray(sim3_quat_initial)
+    if n and not (sim3_pos_initial.shape[0] == n and sim3_quat_initial.shape[0] == n):
+        raise ValueError(f"Sim3-transformed trajectory length ({sim3_pos_initial.shape[0]}) != SLAM timestamp count ({n})")
+    gates = gb._gates_arg(gates)
+    aligned, valid = dynamic_time_alignment(slam_data, gps_data, global_config["time_alignment"])     # ref :847
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(shape)).to(dev)
+    ip = sim3_pos_initial[0] if n else np.zeros(3)
+    iq = sim3_quat_initial[0] if n else np.array([0.0, 0.0, 0.0, 1.0])
+    g = gb.innovation_gate_ragged(up(slam_data["timestamps"], (n,)), up(slam_data["positions"], (n, 3)), up(slam_data["quaternions"], (n, 4)),
+                                  up(aligned, (n, 3)), up(valid, (n,), np.uint8), torch.tensor([0, n], dtype=torch.int64, device=dev),
+                                  up(ip, (1, 3)), up(iq, (1, 4)), gates if gates.is_cuda else gates.numpy(), config=global_config,
+                                  arm_seconds=arm_seconds, max_run=max_run, want_nis=want_nis)
+    h = lambda t: None if t is None else t.cpu().numpy()
+    vo = h(g.valid_out)
+    return {"valid": vo, "rejected": (np.asarray(valid, dtype=np.uint8)[None, :] != 0) & (vo == 0), "stats": h(g.stats[0]),
+            "status": int(g.status[0].item()), "nis": h(g.nis_out), "gates": h(g.gates), "aligned": np.asarray(aligned)}
+
+
 def ekf_covariances(slam_data_in, gps_data_in, global_config):
     """The covariances apply_ekf_correction computes and drops, for one trajectory (host arrays): {"filtered": (n,7,7) = ekf_covs_filt_hist
     (ref :852, :902), "smoothed": (n,7,7) = the covariance of the pose apply_ekf_correction returns -- rts_smoother_segment's (ref :777-803)

@@ -687,6 +687,56 @@ GSF_API int gsf_outage_study_dev(gsf_ctx *ctx, const double *ts, const double *p
                                  const uint8_t *truth_valid, const double *scen, int32_t K, int32_t trace_k, double *stats, int32_t *seg,
                                  int32_t *os_flags, double *err_dr, double *err_fused, double *trace_pos);
 
+/* ---- innovation gate: reject the GNSS fixes the filter disbelieves, K gates per track -----------------------------------------------------
+   The reference's only outlier defence is the polynomial RANSAC pre-filter (filter_gps_outliers_ransac, EKFGPSSLAM.py:136-247) with a
+   threshold of 10 m; every surviving fix is applied with meas_noise_diag = 0.2, so a multipath jump of 3-9 m drags the fused track almost
+   all the way to it.  The standard remedy is a chi-square gate on the normalised innovation squared (NIS): a fix whose NIS exceeds a
+   quantile is not applied.  A rejection changes the state and the variance of every later pose, so the decisions are sequential and the
+   ungated trace of gsf_ekf_noise_sweep_dev is right only up to the first rejection: this entry runs the gated filter itself, for K gates
+   at once.  The reference has no such step; nothing of its flow changes.
+   In: ts, pos, quat, gps, valid, offsets, run_status, init_pos, init_quat, cfg as in gsf_ekf_noise_sweep_dev (cfg's own noise is used);
+   gates[K] = the thresholds, a DEVICE array shared by all tracks, 1 <= K <= 64; arm_seconds; max_run.
+   For track b and gate k the position filter runs exactly as defined at gsf_ekf_noise_sweep_dev (dt, avail, d[i], Pp, S, g and the
+   sharp-turn blend w) with one change.  At a pose i with avail[i]:
+   - nis[i] = (y0^2 / S0 + y1^2 / S1) + y2^2 / S2, from the predicted state of the GATED run.
+   - the pose is tested iff ts[i] > ts[0] + arm_seconds; arm_seconds <= 0 tests every update.
+   - a tested pose is REJECTED iff nis[i] > gates[k] and the forced-accept rule does not apply.  So a NaN NIS is never rejected, and
+     gate = +inf (or NaN) rejects nothing.
+   - forced accept: iff max_run > 0 and the max_run available fixes immediately before i were all rejected (poses without a usable fix
+     neither count towards the run nor reset it), the pose is applied whatever its NIS and counted in n_forced.  max_run <= 0: no limit.
+   - a rejected pose is treated IN EVERY RESPECT as a pose with valid[i] = 0: no update, Pf = Pp; it opens or extends an outage; the
+     sharp-turn ballot and the blend weight at the next recovery see it as part of the outage; it may merge with an outage of the data on
+     either side.
+   That is what makes the entry compose: valid_out is valid with the rejected bytes cleared and every other byte copied (pose 0
+   included), and gsf_ekf_fuse_ragged_dev, gsf_ekf_cov_ragged_dev or gsf_eval_errors_batch_dev on valid_out give the gated fusion, its
+   covariance and its error.  No fuse kernel knows of the gate.
+   Out (each may be NULL), P = offsets[B]:
+   valid_out[K][P] uint8.
+   nis_out[K][P] = the NIS at every pose with avail -- tested or not, rejected or not -- NaN elsewhere.
+   stats[B][K][8] = { n_avail;  n_tested;  n_rejected;  n_forced;  the longest run of consecutive rejected available fixes;  the index of
+     the first rejected pose relative to the track, -1: none;  the largest NIS among the tested poses that were applied (0: none);  their
+     NIS sum }.  The first six are exact counts.  A forced accept is a tested pose that was applied: its NIS is in the last two.  A NaN NIS
+     of such a pose makes the sum NaN and leaves the maximum alone.
+   gate_status[B] = GSF_GATE_* bits, or'ed over the track's K gates.
+   A track with run_status[b] != 0 gets GSF_GATE_SKIPPED: NaN rows (stats and nis_out), valid_out bytes 0, and its inputs are not read.
+   An empty track gets GSF_GATE_EMPTY and rows of zeros with first = -1.  Stamps that are not non-decreasing, or a NaN stamp
+   (GSF_GATE_UNSORTED, the test of GSF_OS_UNSORTED): NaN rows, valid_out = valid.
+   A gate's rows do not depend on K, on the other gates, on their order or on the other tracks: they are the same bytes in every call
+   that holds the gate.  One wave per (track, gate), 64 poses per chunk, 89 B read per pose; a chunk is scanned once plus once per
+   rejection in it (speculate and repair: of the lanes over the gate the lowest has seen only settled decisions), so at most 65 times.
+   B x K words of the context's kernel workspace.  Device pointers, asynchronous on the context's stream.  There is no host-pointer
+   form: the Python binding uploads host arrays itself. */
+#define GSF_GATE_SKIPPED 1        /* run_status[b] != 0: NaN rows, valid_out bytes 0, inputs not read */
+#define GSF_GATE_EMPTY 2          /* the track has no pose */
+#define GSF_GATE_UNSORTED 4       /* the track's stamps are not non-decreasing, or one is NaN: NaN rows, valid_out = valid */
+#define GSF_GATE_ANY_REJECTED 8   /* at least one gate rejected a fix of the track */
+#define GSF_GATE_ANY_FORCED 16    /* at least one gate applied a fix by the forced-accept rule */
+GSF_API int gsf_innovation_gate_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
+                                    const uint8_t *valid, const int64_t *offsets, const int32_t *run_status, const double *init_pos,
+                                    const double *init_quat, const gsf_ekf_config *cfg, int64_t B, const double *gates, int32_t K,
+                                    double arm_seconds, int32_t max_run, uint8_t *valid_out, double *nis_out, double *stats,
+                                    int32_t *gate_status);
+
 /* ---- pose queries: the fused track at any stamp, sensor points into the track's frame ----------------------------------------------------
    The fused track exists at the SLAM stamps; LiDAR returns, other exposures, map points and a second receiver have stamps of their own.
    These entries evaluate the track between its poses with the rule the filter itself uses for orientations (quaternion_nlerp,
