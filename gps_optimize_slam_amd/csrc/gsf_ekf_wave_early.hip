@@ -43,6 +43,12 @@ namespace {
 #ifndef GSF_EARLY_RULE
 #define GSF_EARLY_RULE 1
 #endif
+// The rows part of chunk 0's head where the chunk loop forms it (0) or beside the fit's closed form (1, the A/B form: measured 0.2 us
+// SLOWER -- the closed form's block has no issue slots to spare; HISTORY.md, "Early head")
+#ifndef GSF_EARLY_HEAD
+#define GSF_EARLY_HEAD 0
+#endif
+// (GSF_EARLY_SKIP_Y, the table without its y rows: gsf_wave_common.hpp, where the chunk loop reads the table)
 
 static_assert(GSF_ROWS_ROUND == 6, "the early-variance build hands the fit passes ONE round of six chunks");
 
@@ -130,7 +136,9 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
         const AxisVar vx = variance_finish(mx[k], qx, rx, dt[k], cPx);
         const AxisVar vz = variance_finish(mz[k], qz, rz, dt[k], cPz);
         gsf_pv[0 * stride + i] = vx.Pf; gsf_pv[1 * stride + i] = vx.Pm; gsf_pv[2 * stride + i] = vx.kg;
+#if !GSF_EARLY_SKIP_Y
         gsf_pv[3 * stride + i] = vx.Pf; gsf_pv[4 * stride + i] = vx.Pm; gsf_pv[5 * stride + i] = vx.kg;   // y repeats x
+#endif
         gsf_pv[6 * stride + i] = vz.Pf; gsf_pv[7 * stride + i] = vz.Pm; gsf_pv[8 * stride + i] = vz.kg;
         cPx = lane_bcast(vx.Pf, 63); cPz = lane_bcast(vz.Pf, 63);
     }
@@ -274,7 +282,32 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     {
         const double as_[3] = { as0, as1, as2 };
         const Quat qraw0 = lane_bcast(nxt.q, 0);                          // pose 0's quaternion as stored: requested last, used after the closed form
+#if GSF_EARLY_HEAD
+        // ---- 4b (A/B form, not shipped). the rows part of chunk 0's head (GSF_CHUNK_HEAD_ROWS: unit quaternions, previous-lane moves, dt, the
+        // gate and the outage masks) needs no result of the fit, and every row it reads is in registers: formed HERE, in the basic block of the
+        // closed form, on the idea that its dependent chain leaves a lone wave issue slots.  Measured, it does not: chunk 0 gets 130 cycles
+        // shorter and the prelude 240 longer (HISTORY.md, "Early head").
+        // The chunk loop is untouched -- it expands the same statements on the same operands and finds the values formed.
+        // Too few rows (fit None without a closed form; wave-uniform, rare) leaves first, so that no branch stands between the head and the
+        // closed form; fit_from_partials' own test of the same condition then folds away.  The head has no side effect: the other exits
+        // (a degenerate fit, a bad pose-0 quaternion) leave behind it as they always did.
+        // (one test per operand of fit_from_partials' own condition, so that each is KNOWN where that condition is evaluated again: behind a
+        // joint test the compiler kept a second closed form in the exit)
+        const auto none = [&]() __attribute__((always_inline)) {
+            asm volatile("" ::: "memory");                               // (a real branch, not if-conversion)
+            fit_from_partials(a, b, base, N, lane, sums, as_, bs_, qraw0, p0, q0, fit, rows_flag, true);   // (writes the NaN rows and the status word)
+        };
+        if (!(sums[0] >= 3.0)) { none(); return; }
+        if (rows_flag & SIM3_FLAG_FEW_ROWS) { none(); return; }
+        // chunk 0's carry-in as wave_serial_chunks forms it: pose 0 is its own predecessor (ref :858)
+        Quat h_r; const bool h_ok = quat_unit(qraw0, h_r);
+        const ChunkHeadRows head0 = chunk_head_rows(nxt, ~0ull, 1ull, ~1ull, 0, lane_bcast(nxt.t, 0), lane_bcast(nxt.p, 0), h_ok,
+                                                    __builtin_amdgcn_readlane((int)nxt.v, 0) != 0);
+#endif
         if (!fit_from_partials(a, b, base, N, lane, sums, as_, bs_, qraw0, p0, q0, fit, rows_flag, true)) return;   // (fit None, bad pose-0 quaternion: the table is never read)
+#if GSF_EARLY_HEAD
+        chunk_head_pin(head0);
+#endif
     }
     if (miss != 0ull) {
         // a NaN fix under a set mask byte in the first NE chunks (wave-uniform, rare): their part of the table again, from memory, with the
@@ -290,7 +323,9 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
             AxisVar v0, v1, v2;
             variance_chunk<6>(cfg, 0, -1, dtk, step, avail, cP0, cP1, cP2, v0, v1, v2);   // (AXMODE 1: y repeats x, z has its own scan)
             gsf_pv[0 * stride + i] = v0.Pf; gsf_pv[1 * stride + i] = v0.Pm; gsf_pv[2 * stride + i] = v0.kg;
+#if !GSF_EARLY_SKIP_Y
             gsf_pv[3 * stride + i] = v1.Pf; gsf_pv[4 * stride + i] = v1.Pm; gsf_pv[5 * stride + i] = v1.kg;
+#endif
             gsf_pv[6 * stride + i] = v2.Pf; gsf_pv[7 * stride + i] = v2.Pm; gsf_pv[8 * stride + i] = v2.kg;
             cP0 = lane_bcast(v0.Pf, 63); cP1 = lane_bcast(v1.Pf, 63); cP2 = lane_bcast(v2.Pf, 63); c_t = lane_bcast(t, 63);
         }

@@ -209,7 +209,8 @@ __device__ __forceinline__ void traj_span(const WaveArgs& a, int64_t b, int64_t&
 // showed up as a phantom gap after the prelude.
 __device__ __forceinline__ int32_t* gsf_stamp_buf() { __shared__ int32_t buf[64]; return buf; }
 #define GSF_STAMP(k) do { if (b == GSF_TIMING_B && lane == 0) { int32_t* sb_ = gsf_stamp_buf(); sb_[2 * (k)] = (int32_t)(clock64() & 0x7fffffff); sb_[2 * (k) + 1] = (int32_t)(wall_clock64() & 0x7fffffff); } } while (0)
-#define GSF_STAMP_FLUSH() do { if (b == GSF_TIMING_B && lane == 0 && a.status) { const int32_t* sb_ = gsf_stamp_buf(); for (int k_ = 0; k_ < 32; ++k_) a.status[k_] = sb_[k_]; } } while (0)
+#define GSF_STAMP_FLUSH() do { if (b == GSF_TIMING_B && lane == 0 && a.status) { const int32_t* sb_ = gsf_stamp_buf(); for (int k_ = 0; k_ < 34; ++k_) a.status[k_] = sb_[k_]; } } while (0)
+#define GSF_STAMP_HEAD(c0_) do { if ((c0_) == 0) GSF_STAMP(16); } while (0);   // chunk 0: the rows part of its head formed (stamp 7 = the chunk has arrived)
 #define GSF_STATUS_PTR(a) ((int32_t*)nullptr)
 #elif defined(GSF_WAVE_START_TIMING)
 // diagnostic build only (tools/wave_start_timing.py): EVERY wave writes the 100 MHz clock at its entry (stamp 0) and at its last
@@ -225,6 +226,15 @@ __device__ __forceinline__ int32_t* gsf_stamp_buf() { __shared__ int32_t buf[64]
 #define GSF_STAMP(k) do { } while (0)
 #define GSF_STAMP_FLUSH() do { } while (0)
 #define GSF_STATUS_PTR(a) ((a).status)
+#endif
+#ifndef GSF_STAMP_HEAD
+#define GSF_STAMP_HEAD(c0_)                                              // (no tokens at all: the other builds compile to what they always did)
+#endif
+
+// The early-variance build's table (gsf_ekf_wave_early.hip) under AXMODE 1: the y rows repeat x -- neither written nor read, x copied in
+// registers (1), or written and read as the two-wave kernel's helper has them (0, the A/B form; HISTORY.md, "Early head")
+#ifndef GSF_EARLY_SKIP_Y
+#define GSF_EARLY_SKIP_Y 1
 #endif
 
 #ifndef GSF_WIDE_STORES
@@ -890,6 +900,69 @@ template <> struct RingStore<0> {
     static __device__ __forceinline__ double (*get(int, double* ext))[6][64] { return (double (*)[6][64])ext; }
 };
 
+// The ROWS part of a chunk's head in wave_serial_chunks: what its 64 poses need from the chunk's rows (in: t, p, q, z, the mask byte) and
+// from the carried ROWS (c_t, c_po, c_ok, c_prev_avail) alone -- neither the state (cp, cq, Cq) nor a variance:
+//   - calculate_relative_pose (ref :77-92) against the previous lane / the carry: the unit quaternion, the previous stamp and position.
+//     (The previous pose's unit quaternion is only needed on the cold paths -- generic orientation, sharp-turn pairs -- and the cross-lane
+//     move cannot be sunk there by the compiler: it is fetched inside those wave-uniform branches.)
+//   - both_m: pose i-1 and pose i both have a valid quaternion; dt (ref :865).
+//   - telescope, the fast path (every quaternion of the chunk and the carried one valid -- the normal case): the increments telescope,
+//       dq_first * ... * dq_i = conj(r_carry) * r_i   and   R(q_{i-1}) R(r_{i-1})^-1 = R(Cq),  Cq = q_carry * conj(r_carry),
+//     so the orientation needs no scan and the predicted displacement is ONE rotation by the wave-uniform Cq (identical up to rounding:
+//     r conj(r) = 1 to 1 ulp for unit r).  Any invalid quaternion -> the generic path -- calculate_relative_pose per pose + a quaternion
+//     prefix product -- which sits in ONE block further down, so that the usual chunk runs from the loads to the scans without a branch.
+//   - the GNSS gate (ref :867-869) and the outage structure of the chunk, as masks: avail_m, the fix of pose i is used; av_m, the "gnss
+//     available" flag of pose i (pose 0: raw mask, :848); ap_m, the flag of pose i-1 (lane 0: the carry; pose 0: true); start_mask, an
+//     outage begins at this pose (ref :875-877; pose 0: :861); rec_mask (ref :879); pair_mask, poses i-1 and i both inside the outage.
+// The statements are held ONCE, as text, for two users that must form the same values with the same operations in the same order:
+// chunk_body() expands them where they always stood, and chunk_head_rows() below forms them for a caller that has a chunk's rows in
+// registers ahead of the chunk loop (gsf_ekf_wave_early.hip: chunk 0, beside the fit's closed form).  A function called from chunk_body()
+// was tried first and changed what the other builds compile to (HISTORY.md, "Early head"); the text expanded in place cannot.
+#define GSF_CHUNK_HEAD_ROWS                                                                      \
+    const u64 vraw_m = __ballot(in.v != 0);                                                      \
+    Quat r; const bool ok = quat_unit(q, r);                                                     \
+    const double t_pr = prev_lane(c_t, t);                                                       \
+    const Vec3 p_pr{ prev_lane(c_po.x, p.x), prev_lane(c_po.y, p.y), prev_lane(c_po.z, p.z) };   \
+    const u64 ok_mask = __ballot(ok);                                                            \
+    const u64 both_m = ((ok_mask << 1) | (c_ok ? 1ull : 0ull)) & ok_mask;                        \
+    const bool both_ok = __builtin_amdgcn_inverse_ballot_w64(both_m);                            \
+    const double dt = fmax(1e-6, t - t_pr);                                                      \
+    const bool telescope = c_ok && ((ok_mask & act_mask) == act_mask);                           \
+    const u64 zfin_m = __ballot(!(isnan(z.x) || isnan(z.y) || isnan(z.z)));                      \
+    const u64 avail_m = step_m & vraw_m & zfin_m;                                                \
+    const bool avail = __builtin_amdgcn_inverse_ballot_w64(avail_m);                             \
+    const u64 av_m = (init_m & vraw_m) | avail_m;                                                \
+    const bool av = __builtin_amdgcn_inverse_ballot_w64(av_m);                                   \
+    const u64 a_mask = act_mask & av_m;                                                          \
+    const u64 ap_m = (a_mask << 1) | ((c0 == 0 || c_prev_avail) ? 1ull : 0ull);                  \
+    const u64 start_mask = act_mask & ~av_m & ap_m;                                              \
+    const u64 rec_mask = step_m & av_m & ~ap_m;                                                  \
+    const u64 pair_mask = step_m & ~av_m & ~ap_m;                                                \
+    const bool recovers = __builtin_amdgcn_inverse_ballot_w64(rec_mask);                         \
+    const bool outpair = __builtin_amdgcn_inverse_ballot_w64(pair_mask);                         \
+    status |= (start_mask != 0ull) ? ST_HAD_OUTAGE : 0;
+
+// The values of GSF_CHUNK_HEAD_ROWS for the chunk `in` whose first pose is c0, formed AHEAD of the chunk loop.  Nothing is handed over:
+// chunk_body() expands the same statements on the same operands, and the compiler's value numbering finds them formed already -- the
+// loop is the one every build runs, so the early values cannot change a result.  chunk_head_pin() after the code they are to be
+// interleaved with keeps them formed in front of it (not sunk back to their first use in the loop).
+struct ChunkHeadRows { Quat r; double t_pr; Vec3 p_pr; double dt; u64 ok_mask, both_m, avail_m, av_m, start_mask, rec_mask, pair_mask; bool telescope; };
+__device__ __forceinline__ ChunkHeadRows chunk_head_rows(const ChunkIn& in, const u64 act_mask, const u64 init_m, const u64 step_m, const int64_t c0,
+                                                         const double c_t, const Vec3& c_po, const bool c_ok, const bool c_prev_avail)
+{
+    const double t = in.t;
+    const Vec3 p = in.p; const Quat q = in.q; const Vec3 z = in.z;
+    int32_t status = 0;                                                  // (the loop's own expansion sets the flag)
+    GSF_CHUNK_HEAD_ROWS
+    (void)status; (void)both_ok; (void)avail; (void)av; (void)recovers; (void)outpair;   // (lane predicates: register copies of the masks, formed again at their use)
+    return ChunkHeadRows{ r, t_pr, p_pr, dt, ok_mask, both_m, avail_m, av_m, start_mask, rec_mask, pair_mask, telescope };
+}
+__device__ __forceinline__ void chunk_head_pin(const ChunkHeadRows& h)
+{
+    asm volatile("" :: "v"(h.r.x), "v"(h.r.y), "v"(h.r.z), "v"(h.r.w), "v"(h.p_pr.x), "v"(h.p_pr.y), "v"(h.p_pr.z), "v"(h.dt),
+                       "s"(h.ok_mask), "s"(h.both_m), "s"(h.avail_m), "s"(h.av_m), "s"(h.start_mask), "s"(h.rec_mask), "s"(h.pair_mask));
+}
+
 // The chunk loop of the wave-per-trajectory filter, entered with the initial pose (p0, q0) and the first 64 poses already requested
 // (nxt).  Split from the prelude so that a kernel with its own fit / initial-pose logic can fall back to it (gsf_ekf_lat.hip).
 // AXMODE 1: the caller has checked on the host that axes x and y share (P0, Q, R) and z does not -- the default CONFIG -- so the
@@ -981,38 +1054,8 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         }
         const double t = in.t;
         const Vec3 p = in.p; const Quat q = in.q; const Vec3 z = in.z;
-        const u64 vraw_m = __ballot(in.v != 0);
-        // ---- calculate_relative_pose (ref :77-92) against the previous lane / the carry
-        Quat r; const bool ok = quat_unit(q, r);
-        const double t_pr = prev_lane(c_t, t);
-        const Vec3 p_pr{ prev_lane(c_po.x, p.x), prev_lane(c_po.y, p.y), prev_lane(c_po.z, p.z) };
-        // (the previous pose's unit quaternion is only needed on the cold paths -- generic orientation, sharp-turn pairs -- and the
-        // cross-lane move cannot be sunk there by the compiler: it is fetched inside those wave-uniform branches)
-        const u64 ok_mask = __ballot(ok);
-        const u64 both_m = ((ok_mask << 1) | (c_ok ? 1ull : 0ull)) & ok_mask;   // pose i-1 and pose i both have a valid quaternion
-        const bool both_ok = __builtin_amdgcn_inverse_ballot_w64(both_m);
-        const double dt = fmax(1e-6, t - t_pr);                          // ref :865
-        // Fast path (every quaternion of the chunk and the carried one valid -- the normal case): the increments telescope,
-        //   dq_first * ... * dq_i = conj(r_carry) * r_i   and   R(q_{i-1}) R(r_{i-1})^-1 = R(Cq),  Cq = q_carry * conj(r_carry),
-        // so the orientation needs no scan and the predicted displacement is ONE rotation by the wave-uniform Cq
-        // (identical up to rounding: r conj(r) = 1 to 1 ulp for unit r).  Any invalid quaternion -> generic path below.
-        const bool telescope = c_ok && ((ok_mask & act_mask) == act_mask);
-        // (the generic path -- calculate_relative_pose per pose + a quaternion prefix product -- sits in ONE block further down, so
-        // that the usual chunk runs from the loads to the scans without a branch)
-        // ---- GNSS gate (ref :867-869) and the outage structure of the chunk, as masks
-        const u64 zfin_m = __ballot(!(isnan(z.x) || isnan(z.y) || isnan(z.z)));
-        const u64 avail_m = step_m & vraw_m & zfin_m;                    // the fix of pose i is used
-        const bool avail = __builtin_amdgcn_inverse_ballot_w64(avail_m);
-        const u64 av_m = (init_m & vraw_m) | avail_m;                    // "gnss available" flag of pose i (pose 0: raw mask, :848)
-        const bool av = __builtin_amdgcn_inverse_ballot_w64(av_m);
-        const u64 a_mask = act_mask & av_m;
-        const u64 ap_m = (a_mask << 1) | ((c0 == 0 || c_prev_avail) ? 1ull : 0ull);   // the flag of pose i-1 (lane 0: the carry; pose 0: true)
-        const u64 start_mask = act_mask & ~av_m & ap_m;                  // outage begins at this pose (ref :875-877; pose 0: :861)
-        const u64 rec_mask = step_m & av_m & ~ap_m;                      // ref :879
-        const u64 pair_mask = step_m & ~av_m & ~ap_m;                    // poses i-1 and i both inside the outage
-        const bool recovers = __builtin_amdgcn_inverse_ballot_w64(rec_mask);
-        const bool outpair = __builtin_amdgcn_inverse_ballot_w64(pair_mask);
-        status |= (start_mask != 0ull) ? ST_HAD_OUTAGE : 0;
+        GSF_CHUNK_HEAD_ROWS                                              // (the rows part of the head: the text above wave_serial_chunks)
+        GSF_STAMP_HEAD(c0)
         // is_sharp_turn_in_segment (ref :808-826): pair (i-1, i) exceeds the yaw-rate threshold (or has a bad quaternion)
         u64 f_mask = 0ull;
         if (pair_mask != 0ull) {
@@ -1063,7 +1106,11 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
 #endif
             const int64_t il = active ? i : N - 1;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { Pf[c] = pv[(c * 3 + 0) * pv_stride + il]; Pm[c] = pv[(c * 3 + 1) * pv_stride + il]; kg[c] = pv[(c * 3 + 2) * pv_stride + il]; }
+            for (int c = 0; c < 3; ++c) {
+                // (the early-variance build's table has no y rows where y repeats x: GSF_EARLY_SKIP_Y)
+                if constexpr (GSF_EARLY_SKIP_Y && PVCHUNKS > 0 && AXMODE == 1) { if (c == 1) { Pf[1] = Pf[0]; Pm[1] = Pm[0]; kg[1] = kg[0]; continue; } }
+                Pf[c] = pv[(c * 3 + 0) * pv_stride + il]; Pm[c] = pv[(c * 3 + 1) * pv_stride + il]; kg[c] = pv[(c * 3 + 2) * pv_stride + il];
+            }
         } else {
             AxisVar v0, v1, v2;
             variance_chunk<NS>(cfg, same_axis[1], same_axis[2], dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);

@@ -1,5 +1,7 @@
 """Diagnostic: time stamps of wave 0 of the trajectory-major K4 / pipeline (needs libgsf.so built with -DGSF_CHUNK_TIMING).
-usage: chunk_timing.py B N [pipeline]"""
+usage: [OUTAGE=lo:hi] chunk_timing.py B N [pipeline]
+OUTAGE=20:50 withholds the fixes of poses 20..50 of the stamped track (track 0 unless the build says -DGSF_TIMING_B=b and TRACK=b is set), so
+that the chunk holding them runs outage pairs and a recovery."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -8,6 +10,13 @@ from gps_optimize_slam_amd import batch as B
 nb, n = int(sys.argv[1]), int(sys.argv[2])
 pipe = len(sys.argv) > 3
 bj = B.TrajectoryBatch.synthetic(nb, n, layout=B.LAYOUT_TRAJ_MAJOR, seed=1)
+if os.environ.get("OUTAGE"):
+    lo, hi = (int(x) for x in os.environ["OUTAGE"].split(":"))
+    trk = int(os.environ.get("TRACK", "0"))
+    bj.valid.view(nb, n)[trk, lo:hi + 1] = 0
+    bj.gps.view(nb, n, 3)[trk, lo:hi + 1] = float("nan")
+    print(f"track {trk}: fixes of poses {lo}..{hi} withheld")
+print("stamped track's fixes withheld at poses:", (bj.valid.view(nb, n)[int(os.environ.get("TRACK", "0"))] == 0).nonzero().flatten().tolist())
 oj = B.FusedPoses(bj.layout, nb, n, "cuda")
 oj.status.zero_()
 fn = (lambda: B.fuse_pipeline_batch(bj, out=oj, fit_rows=os.environ.get('FIT_ROWS', 'reference'))) if pipe else (lambda: B.ekf_fuse_batch(bj, out=oj))
@@ -19,6 +28,9 @@ raw = oj.status.cpu().numpy()
 st = raw[:2 * (8 + nch)].reshape(-1, 2).astype("int64")
 if raw[30] or raw[31]:
     print(f"(stamp 15, gap check of the last round done: cycles {int(raw[30]) - int(raw[0])}, {(int(raw[31]) - int(raw[1])) / 100.0:.2f} us after entry)")
+if len(raw) > 33 and (raw[32] or raw[33]):
+    print(f"(stamp 16, chunk 0: rows part of its head formed: cycles {int(raw[32]) - int(raw[0])}, {(int(raw[33]) - int(raw[1])) / 100.0:.2f} us after entry; "
+          f"{int(raw[32]) - int(raw[14])} cycles after 'chunk 0 arrived')")
 names = ["entry", "rows of the (last) round arrived", "moments loop done", "reductions done", "umeyama_finalize done", "pose 0 aligned", "prelude done",
          "chunk 0 arrived"] + [f"chunk {k} done" for k in range(nch)]
 c0, w0 = st[0]
