@@ -84,6 +84,8 @@ TEXT_DEVICE, TEXT_SKIPPED, TEXT_HOST = 0, 1, 2                  # its track_stat
 NS_NONE, NS_TIE = 1, 2                                          # ns_status bits of gsf_ekf_noise_sweep_dev
 OS_EMPTY, OS_NO_RECOVERY, OS_SMOOTHED, OS_SHARP_TURN, OS_MERGED, OS_FROM_START, OS_UNSORTED, OS_SKIPPED = 1, 2, 4, 8, 16, 32, 64, 128   # os_flags bits of gsf_outage_study_dev
 GATE_SKIPPED, GATE_EMPTY, GATE_UNSORTED, GATE_ANY_REJECTED, GATE_ANY_FORCED = 1, 2, 4, 8, 16    # gate_status bits of gsf_innovation_gate_dev
+STREAM_F64, STREAM_I64, STREAM_LAYOUT_VERSION = 22, 6, 1      # state sizes per track and layout version of the streaming fusion (gsf_stream_*)
+STREAM_FULL, STREAM_BAD_STATE = 256, 512                        # ... and its status bits, beside the ST_* ones
 CLK_NONE, CLK_AT_EDGE, CLK_FLAT = 1, 2, 4                       # clk_status bits of gsf_clock_offset_search_dev
 QT_EMPTY, QT_UNSORTED, QT_SKIPPED, QT_BAD_EXTRINSIC = 1, 2, 4, 8    # track_state bits of gsf_pose_query_dev / gsf_georef_points_dev
 Q_EXACT, Q_BEFORE, Q_AFTER, Q_GAP, Q_NAN, Q_TRACK, Q_BAD_QUAT = 1, 2, 4, 8, 16, 32, 64      # ... and their q_flags bits
@@ -172,6 +174,9 @@ SIGNATURES = {
     "gsf_ekf_noise_sweep_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _i32, _f64, _i32, _i32] + [_vp] * 7),
     "gsf_outage_study_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _i32, _i32] + [_vp] * 6),
     "gsf_innovation_gate_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _i32, _f64, _i32] + [_vp] * 4),
+    "gsf_stream_open_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 5),
+    "gsf_stream_append_dev": (C.c_int, [_vp, C.POINTER(EkfConfig), _i64, _i64] + [_vp] * 18),
+    "gsf_stream_gather_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 9),
     "gsf_pose_query_dev": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 6),
     "gsf_pose_query": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 6),
     "gsf_georef_points_dev": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 9),

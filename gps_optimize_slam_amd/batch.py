@@ -1559,3 +1559,139 @@ def georef_fused(rb, r, pt_t, pt_xyz, pt_offsets, ext_q=None, ext_t=None, scale=
     return georef_points_ragged(rb.ts, r.fused.pos, r.fused.quat, rb.slam_offsets, pt_t, pt_xyz, pt_offsets, ext_q=ext_q, ext_t=ext_t, scale=scale,
                                 pose_flags=_fused_pose_flags(r), run_status=r.run_status, max_gap=max_gap,
                                 zone=r.zone if wgs84 else None, south=r.south if wgs84 else None)
+
+
+# ---- streaming fusion: append poses to live tracks (gsf_stream_*) ----------------------------------------------------------------------------
+class StreamStep:
+    """What FusionStream.append returns: pos (P,3) / quat (P,4) = the fused rows of this call's segments as they stand when the call ends,
+    cov (P,7) = the filtered covariance diagonal after each pose; n_total (B,) int64 = poses each track holds; n_final (B,): rows
+    [0, n_final) will never be written again; revised_from (B,) = the smallest global index this call wrote; status (B,) int32 = the
+    accumulated _lib.ST_* bits as of now | _lib.STREAM_FULL (this segment was refused: NaN rows, track untouched) | _lib.STREAM_BAD_STATE."""
+    __slots__ = ("pos", "quat", "cov", "n_total", "n_final", "revised_from", "status")
+
+    def __init__(self, pos, quat, cov, n_total, n_final, revised_from, status):
+        self.pos, self.quat, self.cov, self.n_total, self.n_final, self.revised_from, self.status = pos, quat, cov, n_total, n_final, revised_from, status
+
+    def __iter__(self):
+        return iter((self.pos, self.quat, self.cov, self.n_total, self.n_final, self.revised_from, self.status))
+
+
+def _stream_sizes_chk(B, cap):
+    B, cap = int(B), int(cap)
+    if B < 0 or cap < 1:
+        raise ValueError(f"FusionStream: B >= 0 and cap >= 1 expected, got B = {B}, cap = {cap}")
+    return B, cap
+
+
+class FusionStream:
+    """B tracks whose fusion can be continued: the filter state and the last `cap` fused rows of every track live in tensors this object
+    owns, an append costs what its new poses cost, and every append says which rows are final.  init_pos (B,3) / init_quat (B,4) are what
+    they are at ekf_fuse_ragged: the Sim3-transformed pose 0.  How a track is cut into appends does not change one bit of any output.
+    Capacity: a track whose open outage plus new segment exceeds `cap` rows is refused (StreamStep.status & _lib.STREAM_FULL) and left
+    untouched; give the stream a larger cap, append shorter segments, or reopen() that track.  Every call is one launch on torch's current
+    stream."""
+
+    def __init__(self, B, cap, init_pos, init_quat, config=None, device="cuda"):
+        self.B, self.cap = _stream_sizes_chk(B, cap)
+        self.config = config or CONFIG
+        self._cfg = EkfConfig.from_config(self.config)
+        dev = torch.device(device)
+        f = dict(dtype=torch.float64, device=dev)
+        self.state_f64 = torch.empty((_lib.STREAM_F64, self.B), **f)
+        self.state_i64 = torch.empty((_lib.STREAM_I64, self.B), dtype=torch.int64, device=dev)
+        self.ring_t, self.ring_pos, self.ring_quat = torch.empty((self.B, self.cap), **f), torch.empty((self.B, self.cap, 3), **f), torch.empty((self.B, self.cap, 4), **f)
+        if init_pos is not None:
+            self.reopen(None, init_pos, init_quat)
+
+    @property
+    def device(self):
+        return self.state_f64.device
+
+    def reopen(self, mask, init_pos, init_quat):
+        """(re-)start the tracks with a non-zero byte in mask (B,) uint8 (None: all) from init_pos (B,3) / init_quat (B,4); the others are untouched"""
+        dev = self.device
+        ip = torch.as_tensor(init_pos, dtype=torch.float64).to(dev).contiguous()
+        iq = torch.as_tensor(init_quat, dtype=torch.float64).to(dev).contiguous()
+        _chk(ip, torch.float64, (self.B, 3), "init_pos"); _chk(iq, torch.float64, (self.B, 4), "init_quat")
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8).contiguous()
+            _chk(mask, torch.uint8, (self.B,), "mask")
+        check(_lib.load().gsf_stream_open_dev(context(dev).handle, self.B, self.cap, _p(ip), _p(iq), _p(mask), _p(self.state_f64), _p(self.state_i64)))
+
+    def append(self, ts, pos, quat, gps, valid, seg_offsets, want_cov=True):
+        """ts (P,), pos (P,3), quat (P,4) = the new original SLAM poses, gps (P,3) / valid (P,) uint8 = their time-aligned fixes and mask, flat
+        over the tracks; track b contributes rows seg_offsets[b] .. seg_offsets[b+1] (int64 (B+1,)), possibly none.  Returns a StreamStep."""
+        B = _offsets_chk(seg_offsets)
+        if B != self.B:
+            raise ValueError(f"seg_offsets: {self.B + 1} entries expected, got {B + 1}")
+        P = int(ts.shape[0]) if ts.dim() == 1 else -1
+        _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+        _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid")
+        dev = self.device
+        f = dict(dtype=torch.float64, device=dev)
+        i = dict(dtype=torch.int64, device=dev)
+        s = StreamStep(torch.empty((P, 3), **f), torch.empty((P, 4), **f), torch.empty((P, 7), **f) if want_cov else None, torch.empty((B,), **i),
+                       torch.empty((B,), **i), torch.empty((B,), **i), torch.empty((B,), dtype=torch.int32, device=dev))
+        check(_lib.load().gsf_stream_append_dev(context(dev).handle, C.byref(self._cfg), B, self.cap, _p(self.state_f64), _p(self.state_i64), _p(self.ring_t),
+                                                _p(self.ring_pos), _p(self.ring_quat), _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(seg_offsets),
+                                                _p(s.pos), _p(s.quat), _p(s.cov), _p(s.n_total), _p(s.n_final), _p(s.revised_from), _p(s.status)))
+        return s
+
+    def rows(self, lo, counts):
+        """rows [lo[b], lo[b] + counts[b]) of every track from the ring: ts (P,), pos (P,3), quat (P,4), out_offsets (B+1,); a row the ring
+        no longer holds (or does not hold yet) is NaN.  lo / counts: (B,) int64 tensors or sequences (sequences cost no device read)."""
+        dev = self.device
+        host_counts = not torch.is_tensor(counts)
+        lo = torch.as_tensor(lo, dtype=torch.int64).to(dev).contiguous()
+        cnt = torch.as_tensor(counts, dtype=torch.int64)
+        _chk(lo, torch.int64, (self.B,), "lo")
+        if tuple(cnt.shape) != (self.B,):
+            raise ValueError(f"counts: shape ({self.B},) expected")
+        off_h = torch.zeros(self.B + 1, dtype=torch.int64)
+        off_h[1:] = torch.cumsum(cnt.cpu() if not host_counts else cnt, 0)
+        if self.B and int(cnt.min()) < 0:
+            raise ValueError("counts: negative")
+        P = int(off_h[-1])
+        off = off_h.to(dev)
+        f = dict(dtype=torch.float64, device=dev)
+        t, p, q = torch.empty((P,), **f), torch.empty((P, 3), **f), torch.empty((P, 4), **f)
+        check(_lib.load().gsf_stream_gather_dev(context(dev).handle, self.B, self.cap, _p(self.state_i64), _p(self.ring_t), _p(self.ring_pos),
+                                                _p(self.ring_quat), _p(lo), _p(off), _p(t), _p(p), _p(q)))
+        return t, p, q, off
+
+    @property
+    def n_total(self):
+        return self.state_i64[2]
+
+    def state_dict(self):
+        """the checkpoint: plain tensors (safe to .cpu() and save) from which from_state continues with the same bits"""
+        return dict(version=_lib.STREAM_LAYOUT_VERSION, B=self.B, cap=self.cap, config=self.config, state_f64=self.state_f64.clone(),
+                    state_i64=self.state_i64.clone(), ring_t=self.ring_t.clone(), ring_pos=self.ring_pos.clone(), ring_quat=self.ring_quat.clone())
+
+    @classmethod
+    def from_state(cls, d, device="cuda"):
+        """a stream that continues the one state_dict() was taken from.  A checkpoint of another layout version is refused (ValueError) before
+        anything touches a device."""
+        if int(d.get("version", -1)) != _lib.STREAM_LAYOUT_VERSION:
+            raise ValueError(f"FusionStream.from_state: layout version {d.get('version')!r}, this library reads version {_lib.STREAM_LAYOUT_VERSION}")
+        B, cap = _stream_sizes_chk(d["B"], d["cap"])
+        shapes_ = dict(state_f64=(_lib.STREAM_F64, B), state_i64=(_lib.STREAM_I64, B), ring_t=(B, cap), ring_pos=(B, cap, 3), ring_quat=(B, cap, 4))
+        for k, shp in shapes_.items():
+            t = d[k]
+            want = torch.int64 if k == "state_i64" else torch.float64
+            if not torch.is_tensor(t) or t.dtype != want or tuple(t.shape) != shp:
+                raise ValueError(f"FusionStream.from_state: {k}: {want} tensor of shape {shp} expected")
+        si = d["state_i64"]
+        if B and (bool((si[0] != _lib.STREAM_LAYOUT_VERSION).any()) or bool((si[1] != cap).any())):
+            raise ValueError("FusionStream.from_state: state_i64 was not written by this layout version for this cap")
+        s = cls(B, cap, None, None, config=d.get("config"), device=device)
+        for k in shapes_:
+            getattr(s, k).copy_(d[k])
+        return s
+
+    @classmethod
+    def from_run(cls, rb, r, cap=4096, config=None):
+        """a stream opened from the Sim3-transformed pose 0 of every track of a run_fusion_ragged result r for the batch rb (built as
+        gate_fused builds it), on rb's device; feed it rb's poses with r.aligned / r.valid, in pieces"""
+        ip, iq = _fused_init_pose(rb, r)
+        return cls(int(ip.shape[0]), cap, ip, iq, config=config, device=ip.device)

@@ -581,6 +581,64 @@ def gate_gnss_fixes(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial, gl
             "status": int(g.status[0].item()), "nis": h(g.nis_out), "gates": h(g.gates), "aligned": np.asarray(aligned)}
 
 
+class FusionSession:
+    """One track fused as it grows (batch.FusionStream with one track; host arrays in, host arrays out): push() takes the next poses and
+    returns their fused rows and how far the track is final.  init_pos (3,) / init_quat (4,) = the Sim3-transformed pose 0, as at
+    ekf_fuse_aligned.  The filter continues exactly where it stopped: the pushes of a track give the bits of one push of the whole track.
+    `cap` rows of history are kept for the RTS back-pass; a push longer than cap // 2 poses goes to the device in pieces of that length
+    (the split changes no bit).  An outage that does not fit the ring with the next piece raises GsfError, the session staying as it was
+    before that piece: open a session with a larger cap."""
+
+    def __init__(self, init_pos, init_quat, config=None, cap=4096):
+        import torch
+        from . import batch as gb
+        self.cap = int(cap)
+        self.config = config or CONFIG
+        self._dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+        if self._dev is None:
+            raise GsfError("torch sees no GPU: a fusion session needs an MI355X (no CPU fallback)")
+        self._s = gb.FusionStream(1, self.cap, f64(init_pos, (1, 3)), f64(init_quat, (1, 4)), config=self.config, device=self._dev)
+        self.n_total = self.n_final = 0
+        self.status = 0
+
+    def rows(self, lo, count):
+        """rows [lo, lo + count) of the track as they stand: ts, pos, quat (NaN where the ring no longer holds a row)"""
+        t, p, q, _ = self._s.rows([int(lo)], [int(count)])
+        return t.cpu().numpy(), p.cpu().numpy(), q.cpu().numpy()
+
+    def push(self, ts, pos, quat, aligned, valid):
+        """ts (m,), pos (m,3), quat (m,4) = the next original SLAM poses, aligned (m,3) / valid (m,) = their time-aligned fixes and mask.
+        Returns dict(pos (m,3), quat (m,4), cov (m,7) filtered covariance diagonals, n_total, n_final, revised_from, status): rows
+        [0, n_final) of the track are final, rows from revised_from on were written by this push (fetch the ones before this push's
+        own with rows())."""
+        import torch
+        ts, pos, quat, aligned = f64(ts).reshape(-1), f64(pos).reshape(-1, 3), f64(quat).reshape(-1, 4), f64(aligned).reshape(-1, 3)
+        valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
+        m = ts.shape[0]
+        if not (pos.shape[0] == quat.shape[0] == aligned.shape[0] == valid.shape[0] == m):
+            raise ValueError("FusionSession.push: arrays of different lengths")
+        up = lambda a: torch.from_numpy(a).to(self._dev)
+        d = [up(a) for a in (ts, pos, quat, aligned, valid)]
+        po, qo, co = np.empty((m, 3)), np.empty((m, 4)), np.empty((m, 7))
+        first, revised = self.n_total, self.n_total
+        piece = max(1, self.cap // 2)
+        for lo in range(0, max(m, 1), piece):
+            hi = min(m, lo + piece)
+            st = self._s.append(*[a[lo:hi].contiguous() for a in d], torch.tensor([0, hi - lo], dtype=torch.int64, device=self._dev))
+            status, rf = int(st.status[0].item()), int(st.revised_from[0].item())
+            if status & (_lib.STREAM_FULL | _lib.STREAM_BAD_STATE):
+                raise GsfError(f"FusionSession.push: poses {lo}..{hi - 1} of this push refused (status {status}): the open outage and the piece "
+                               f"exceed cap = {self.cap}; the {lo} poses before them were taken")
+            po[lo:hi], qo[lo:hi], co[lo:hi] = st.pos.cpu().numpy(), st.quat.cpu().numpy(), st.cov.cpu().numpy()
+            start = first + lo
+            if rf < start and start > first:                                # a back-pass reached into an earlier piece of this push
+                a = max(rf, first)
+                _, po[a - first:lo], qo[a - first:lo] = self.rows(a, start - a)
+            revised = min(revised, rf)
+            self.n_total, self.n_final, self.status = int(st.n_total[0].item()), int(st.n_final[0].item()), status
+        return dict(pos=po, quat=qo, cov=co, n_total=self.n_total, n_final=self.n_final, revised_from=revised, status=self.status)
+
+
 def ekf_covariances(slam_data_in, gps_data_in, global_config):
     """The covariances apply_ekf_correction computes and drops, for one trajectory (host arrays): {"filtered": (n,7,7) = ekf_covs_filt_hist
     (ref :852, :902), "smoothed": (n,7,7) = the covariance of the pose apply_ekf_correction returns -- rts_smoother_segment's (ref :777-803)

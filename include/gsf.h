@@ -737,6 +737,56 @@ GSF_API int gsf_innovation_gate_dev(gsf_ctx *ctx, const double *ts, const double
                                     double arm_seconds, int32_t max_run, uint8_t *valid_out, double *nis_out, double *stats,
                                     int32_t *gate_status);
 
+/* ---- streaming fusion: append poses to live tracks, finished rows marked ------------------------------------------------------------------
+   Every fuse entry above takes a whole track and returns a whole track.  The filter itself is a recursion with a small state, and only an
+   open outage reaches back (the RTS back-pass, EKFGPSSLAM.py:906-922), as far as the outage's first pose.  A STREAM is a set of B tracks that
+   can be continued: the cost of an append depends on the new poses only, and every call says which rows are final.
+
+   The whole state of a stream lives in caller-owned DEVICE buffers.  No handle, no allocation inside the library.  There is no host-pointer
+   form (a stream that crossed PCIe with its ring on every call would cost what it saves): a binding uploads its segment itself, as the
+   Python one does, and examples/stream_track.c shows it from plain C.
+     state_f64[GSF_STREAM_F64 * B], state_i64[GSF_STREAM_I64 * B]: opaque; field-major (field k of track b at [k * B + b]).  The layout
+       version and cap are stored in the state and checked by every append: a state of another version or ring size is refused with
+       GSF_STREAM_BAD_STATE (NaN rows, counters 0, nothing written).  The state is exact float64 / int64, so it is a checkpoint: copy the
+       buffers and the ring anywhere, continue there, and get the same bits.
+     ring_t[B][cap], ring_pos[B][cap][3], ring_quat[B][cap][4]: the history ring, stamps and fused poses; global pose index i of track b
+       lives in slot i % cap.  It need not be initialised.
+
+   gsf_stream_open_dev: zero poses seen; init_pos[B][3] / init_quat[B][4] mean what they mean at gsf_ekf_fuse_ragged_dev (the Sim3-transformed
+     pose 0).  track_mask[B] (may be NULL = all): only the tracks with a non-zero byte are (re-)opened, the others are left untouched.
+   gsf_stream_append_dev: ts / pos / quat / gps / valid are flat ragged arrays as at gsf_ekf_fuse_ragged_dev (original SLAM poses, time-aligned
+     fixes, mask); track b contributes rows seg_offsets[b] .. seg_offsets[b+1], possibly none (the no-op).  Each track's filter continues
+     exactly where it stopped: how a track is cut into segments does not change one bit of any output.  Outputs, each may be NULL:
+       pos_out / quat_out  the fused rows of this segment as they stand when the call ends (the segment's ragged shape);
+       cov_out[.][7]       the filtered covariance diagonal after each pose of the segment (cov_filt of gsf_ekf_cov_ragged_dev);
+       n_total[B]          poses the track holds;
+       n_final[B]          rows [0, n_final) will never be written again: the open outage's first pose, else n_total;
+       revised_from[B]     the smallest global index this call wrote: n_total before the call, or the start of an outage whose back-pass
+                           reached further back;
+       status[B]           the accumulated GSF_ST_* bits as of now (GSF_ST_ENDED_IN_OUTAGE = an outage is open at this moment) | GSF_STREAM_*.
+     CAPACITY.  A back-pass reads the rows of its outage, so a ring slot must not be reused while it can still be read.  Before any work a
+     track with (outage open ? n_total - outage start : 0) + segment length > cap is refused with GSF_STREAM_FULL: state and ring untouched,
+     its segment rows NaN, counters as before the call, the other tracks proceed.  An RTS segment is never silently truncated; a stream that
+     stays within capacity is the reference's filter.  Remedies: a larger cap (a new stream), shorter segments, or re-opening that track.
+   gsf_stream_gather_dev: rows [lo[b], lo[b] + out_offsets[b+1] - out_offsets[b]) of each track's ring into ragged ts_out / pos_out / quat_out
+     (each may be NULL); rows outside [n_total - cap, n_total) are NaN.  This is how a caller fetches revised or final rows.
+   One launch each, lane per track, asynchronous on the context's stream. */
+#define GSF_STREAM_F64 22
+#define GSF_STREAM_I64 6
+#define GSF_STREAM_LAYOUT_VERSION 1
+#define GSF_STREAM_FULL 256       /* this call's segment was refused by the capacity rule */
+#define GSF_STREAM_BAD_STATE 512  /* the state was not written by this layout version for this cap */
+GSF_API int gsf_stream_open_dev(gsf_ctx *ctx, int64_t B, int64_t cap, const double *init_pos, const double *init_quat,
+                                const uint8_t *track_mask, double *state_f64, int64_t *state_i64);
+GSF_API int gsf_stream_append_dev(gsf_ctx *ctx, const gsf_ekf_config *cfg, int64_t B, int64_t cap, double *state_f64, int64_t *state_i64,
+                                  double *ring_t, double *ring_pos, double *ring_quat, const double *ts, const double *pos,
+                                  const double *quat, const double *gps, const uint8_t *valid, const int64_t *seg_offsets,
+                                  double *pos_out, double *quat_out, double *cov_out, int64_t *n_total, int64_t *n_final,
+                                  int64_t *revised_from, int32_t *status);
+GSF_API int gsf_stream_gather_dev(gsf_ctx *ctx, int64_t B, int64_t cap, const int64_t *state_i64, const double *ring_t,
+                                  const double *ring_pos, const double *ring_quat, const int64_t *lo, const int64_t *out_offsets,
+                                  double *ts_out, double *pos_out, double *quat_out);
+
 /* ---- pose queries: the fused track at any stamp, sensor points into the track's frame ----------------------------------------------------
    The fused track exists at the SLAM stamps; LiDAR returns, other exposures, map points and a second receiver have stamps of their own.
    These entries evaluate the track between its poses with the rule the filter itself uses for orientations (quaternion_nlerp,
