@@ -76,6 +76,12 @@ class RunConfig(C.Structure):
         return c
 
 
+class LocalConfig(C.Structure):
+    """gsf_local_config (include/gsf.h): the knot grid, window and fit rule of gsf_sim3_local_fit_dev."""
+    _fields_ = [("mode", C.c_int32), ("min_rows", C.c_int32), ("spacing", C.c_double), ("half_window", C.c_double), ("rot_open", C.c_double),
+                ("ratio_max", C.c_double)]
+
+
 RUN_GPS_EMPTY, RUN_GPS_FEW, RUN_PREFILTER_UNHANDLED, RUN_SIM3_FAILED, RUN_BAD_QUAT = 1, 2, 4, 8, 16      # run_status bits of gsf_run_fusion_batch_dev
 RUN_GT_EMPTY, RUN_GT_FEW, RUN_GT_UNHANDLED, RUN_SLAM_EMPTY = 32, 64, 128, 256                          # ... and of gsf_run_fusion_ragged_dev only
 SIM3_FLAG_SATURATED = 256
@@ -84,6 +90,10 @@ TEXT_DEVICE, TEXT_SKIPPED, TEXT_HOST = 0, 1, 2                  # its track_stat
 NS_NONE, NS_TIE = 1, 2                                          # ns_status bits of gsf_ekf_noise_sweep_dev
 OS_EMPTY, OS_NO_RECOVERY, OS_SMOOTHED, OS_SHARP_TURN, OS_MERGED, OS_FROM_START, OS_UNSORTED, OS_SKIPPED = 1, 2, 4, 8, 16, 32, 64, 128   # os_flags bits of gsf_outage_study_dev
 GATE_SKIPPED, GATE_EMPTY, GATE_UNSORTED, GATE_ANY_REJECTED, GATE_ANY_FORCED = 1, 2, 4, 8, 16    # gate_status bits of gsf_innovation_gate_dev
+LOC_SCALE, LOC_SIM3, LOC_KMAX = 0, 1, 4096                      # modes of gsf_sim3_local_fit_dev and its largest knot stride
+LOC_EMPTY, LOC_UNSORTED, LOC_TOO_MANY, LOC_SKIPPED = 1, 2, 4, 8   # ... its track_status bits
+KNOT_FEW, KNOT_VAR0, KNOT_SCALE, KNOT_ROT_FALLBACK = 1, 2, 4, 8   # ... its knot_flags bits (the first three make a knot invalid)
+LP_BRIDGED, LP_HELD, LP_GLOBAL, LP_BAD_QUAT, LP_TRACK = 1, 2, 4, 8, 16      # pose_flags bits of gsf_sim3_local_apply_dev
 STREAM_F64, STREAM_I64, STREAM_LAYOUT_VERSION = 22, 6, 1      # state sizes per track and layout version of the streaming fusion (gsf_stream_*)
 STREAM_FULL, STREAM_BAD_STATE = 256, 512                        # ... and its status bits, beside the ST_* ones
 CLK_NONE, CLK_AT_EDGE, CLK_FLAT = 1, 2, 4                       # clk_status bits of gsf_clock_offset_search_dev
@@ -174,6 +184,8 @@ SIGNATURES = {
     "gsf_ekf_noise_sweep_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _i32, _f64, _i32, _i32] + [_vp] * 7),
     "gsf_outage_study_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _i32, _i32] + [_vp] * 6),
     "gsf_innovation_gate_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _i32, _f64, _i32] + [_vp] * 4),
+    "gsf_sim3_local_fit_dev": (C.c_int, [_vp] * 6 + [_i64, _vp, _vp, _vp, C.POINTER(LocalConfig), _i32] + [_vp] * 8),
+    "gsf_sim3_local_apply_dev": (C.c_int, [_vp] * 5 + [_i64, _vp, _vp, _vp, _f64, _i32] + [_vp] * 10),
     "gsf_stream_open_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 5),
     "gsf_stream_append_dev": (C.c_int, [_vp, C.POINTER(EkfConfig), _i64, _i64] + [_vp] * 18),
     "gsf_stream_gather_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 9),

@@ -1416,6 +1416,29 @@ def gate_fused(rb, r, gates, config=None, arm_seconds=0.0, max_run=0, want_nis=F
                                   max_run=max_run, want_nis=want_nis)
 
 
+def _step6_rows(ts, offsets, trajs, aligned, valid, skip_seconds):
+    """step 6's nearest-fix error of several trajectories of the same ragged batch (eval_errors_batch on the tracks padded to one length;
+    padded rows are not evaluated) -> [(stats (B,4), errors (P,))] in the order of trajs"""
+    B, P = _offsets_chk(offsets), int(ts.numel())
+    dev = ts.device
+    if P == 0:
+        return [(torch.zeros((B, 4), dtype=torch.float64, device=dev), torch.empty((0,), dtype=torch.float64, device=dev)) for _ in trajs]
+    off = offsets.cpu().tolist()
+    N = max([off[b + 1] - off[b] for b in range(B)] + [1])
+    row = torch.arange(N, dtype=torch.int64, device=dev)[None, :]
+    n = (offsets[1:] - offsets[:-1])[:, None]
+    inside = row < n
+    idx = torch.clamp(offsets[:-1, None] + torch.minimum(row, torch.clamp(n - 1, min=0)), max=max(P - 1, 0))
+    dv = torch.where(inside, valid[idx], torch.zeros_like(valid[idx])).contiguous()
+    out = []
+    for p in trajs:
+        stats, err = eval_errors_batch(ts[idx].contiguous(), p[idx].contiguous(), aligned[idx].contiguous(), dv, skip_seconds=skip_seconds)
+        errors = torch.full((P,), float("nan"), dtype=torch.float64, device=dev)
+        errors[idx[inside]] = err[inside]
+        out.append((stats, errors))
+    return out
+
+
 def refuse_gated(rb, r, g, k=0, want_cov=False, skip_seconds=5.0, config=None):
     """Fuse again with gate k's mask: the existing ekf_fuse_ragged on g.valid(k) (g from gate_fused), optionally ekf_covariance_ragged on
     the same mask, and step 6's nearest-fix error of the gated track against the fixes the gate kept (eval_errors_batch on the tracks
@@ -1427,22 +1450,168 @@ def refuse_gated(rb, r, g, k=0, want_cov=False, skip_seconds=5.0, config=None):
     vk = g.valid(k).contiguous()
     po, qo, st = ekf_fuse_ragged(ts, pos, quat, aligned, vk, offsets, g.init_pos, g.init_quat, config=config)
     cov = ekf_covariance_ragged(ts, quat, aligned, vk, offsets, config=config, run_status=r.run_status) if want_cov else None
+    (stats, errors), = _step6_rows(ts, offsets, (po,), aligned, vk, skip_seconds)
+    return RunResult(pos=po, quat=qo, status=st, valid=vk, err_stats=stats, errors=errors, cov=cov)
+
+
+# ---------------------------------------------------------------------------- local Sim3 alignment (gsf_sim3_local_fit_dev / _apply_dev)
+_LOCAL_MODES = {"scale": _lib.LOC_SCALE, "sim3": _lib.LOC_SIM3}
+
+
+def _local_config(mode, min_rows, spacing, half_window, rot_open, ratio_max):
+    """the arguments of the local alignment as a gsf_local_config, checked as the entry checks them (these errors need no device)"""
+    if mode not in _LOCAL_MODES:
+        raise ValueError(f"local alignment: mode must be 'scale' or 'sim3', got {mode!r}")
+    c = _lib.LocalConfig()
+    c.mode, c.min_rows = _LOCAL_MODES[mode], int(min_rows)
+    c.spacing, c.half_window, c.rot_open, c.ratio_max = float(spacing), float(half_window), float(rot_open), float(ratio_max)
+    if c.min_rows < (3 if c.mode == _lib.LOC_SIM3 else 2):
+        raise ValueError("local alignment: min_rows must be >= 2 (mode 'scale') / >= 3 (mode 'sim3')")
+    if not (0.0 < c.spacing < float("inf")):
+        raise ValueError("local alignment: spacing must be positive and finite")
+    if not c.half_window >= 0.0:
+        raise ValueError("local alignment: half_window must be >= 0")
+    if not (c.rot_open >= 0.0 and c.ratio_max >= 1.0):
+        raise ValueError("local alignment: rot_open must be >= 0 and ratio_max >= 1")
+    return c
+
+
+class LocalAlignment:
+    """Result of local_align_ragged / local_apply_ragged for B tracks with a knot stride of Kmax (definitions: include/gsf.h,
+    gsf_sim3_local_fit_dev).  Device tensors: knot_R (B,Kmax,9), knot_t (B,Kmax,3), knot_s, knot_rms (B,Kmax), knot_n, knot_flags (B,Kmax)
+    int32 (_lib.KNOT_* bits), n_knots, track_status (B,) int32 (_lib.LOC_* bits), and per pose pos (P,3), quat (P,4), scale_at (P,),
+    pose_flags (P,) int32 (_lib.LP_* bits).  pos / quat are a track like any other: they go straight into ekf_fuse_ragged,
+    outage_study_ragged, ekf_noise_sweep_ragged and innovation_gate_ragged as the motion source."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def scale_curve(self, b):
+        """(stamps, s_k, valid) of track b's knots, on the host: tau_k = t0 + k spacing, s_k (NaN where invalid), valid as bool"""
+        K = int(self.n_knots[b].item())
+        o = int(self.offsets[b].item())
+        t0 = float(self.ts[o].item()) if K else 0.0
+        s = self.knot_s[b, :K].cpu().numpy()
+        ok = (self.knot_flags[b, :K].cpu().numpy() & (_lib.KNOT_FEW | _lib.KNOT_VAR0 | _lib.KNOT_SCALE)) == 0
+        return (t0 + self.spacing * torch.arange(K, dtype=torch.float64)).numpy(), s, ok
+
+    def drift(self, b):
+        """(largest, smallest) valid s_k / s_global of track b; (nan, nan) where no knot is valid"""
+        _, s, ok = self.scale_curve(b)
+        if not ok.any():
+            return float("nan"), float("nan")
+        r = s[ok] / float(self.s[b].item())
+        return float(r.max()), float(r.min())
+
+
+def _local_args(ts, pos, quat, offsets, R, t, s):
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(R, torch.float64, (B, 9), "R"); _chk(t, torch.float64, (B, 3), "t"); _chk(s, torch.float64, (B,), "s")
+    return B, P
+
+
+def _knot_stride(ts, offsets, spacing, B, P):
+    """the largest K_b of the batch (one small reduction and one number read back), at least 1 and at most _lib.LOC_KMAX"""
+    if B == 0 or P == 0:
+        return 1
+    n = offsets[1:] - offsets[:-1]
+    first, last = torch.clamp(offsets[:-1], max=P - 1), torch.clamp(offsets[1:] - 1, min=0, max=P - 1)
+    K = torch.floor((ts[last] - ts[first]) / spacing) + 2.0
+    K = torch.where((n > 0) & torch.isfinite(K), K, torch.ones_like(K))
+    return int(min(max(float(K.max().item()), 1.0), float(_lib.LOC_KMAX)))
+
+
+def local_apply_ragged(ts, pos, quat, offsets, R, t, s, spacing, knot_R, knot_t, knot_s, knot_flags, n_knots, track_status):
+    """The blend of gsf_sim3_local_apply_dev under FED knots (the caller's own, or a LocalAlignment's after editing): knot_R (B,Kmax,9),
+    knot_t (B,Kmax,3), knot_s (B,Kmax), knot_flags (B,Kmax) int32, n_knots, track_status (B,) int32.  One launch pair on torch's current
+    stream.  Returns pos (P,3), quat (P,4), scale_at (P,), pose_flags (P,) int32."""
+    B, P = _local_args(ts, pos, quat, offsets, R, t, s)
+    Kmax = int(knot_s.shape[1]) if knot_s.dim() == 2 else -1
+    if not 1 <= Kmax <= _lib.LOC_KMAX:
+        raise ValueError(f"local_apply_ragged: the knot stride must be in [1, {_lib.LOC_KMAX}]")
+    _chk(knot_R, torch.float64, (B, Kmax, 9), "knot_R"); _chk(knot_t, torch.float64, (B, Kmax, 3), "knot_t"); _chk(knot_s, torch.float64, (B, Kmax), "knot_s")
+    _chk(knot_flags, torch.int32, (B, Kmax), "knot_flags"); _chk(n_knots, torch.int32, (B,), "n_knots"); _chk(track_status, torch.int32, (B,), "track_status")
+    dev = ts.device
+    po, qo = torch.empty_like(pos), torch.empty_like(quat)
+    sc, fl = torch.empty((P,), dtype=torch.float64, device=dev), torch.empty((P,), dtype=torch.int32, device=dev)
+    check(_lib.load().gsf_sim3_local_apply_dev(context().handle, _p(ts), _p(pos), _p(quat), _p(offsets), B, _p(R), _p(t), _p(s), float(spacing), Kmax,
+                                               _p(knot_R), _p(knot_t), _p(knot_s), _p(knot_flags), _p(n_knots), _p(track_status), _p(po), _p(qo),
+                                               _p(sc), _p(fl)))
+    return po, qo, sc, fl
+
+
+def local_align_ragged(ts, pos, quat, gps, valid, offsets, R, t, s, spacing=30.0, half_window=30.0, min_rows=8, mode="scale", rot_open=1e-3,
+                       ratio_max=2.0, run_status=None, max_knots=None):
+    """Local Sim3 alignment of B ragged tracks on torch's current stream: Sim3 knots every `spacing` seconds, each fitted on the usable
+    rows within `half_window` of it, and every pose mapped by the blend of its neighbouring valid knots (gsf_sim3_local_fit_dev then
+    gsf_sim3_local_apply_dev; definitions in include/gsf.h).  ts (P,), pos (P,3), quat (P,4): the original SLAM tracks; gps (P,3) / valid
+    (P,) uint8 as the time alignment returns them; R (B,9), t (B,3), s (B,): each track's global Sim3.  mode "scale" fits scale and
+    translation per knot under the global rotation (well posed on a straight road), "sim3" the full closed form with "scale" as the
+    fall-back of a rotation-open window.  run_status (B,) int32: tracks with a non-zero word pass through as NaN rows
+    (_lib.LOC_SKIPPED).  max_knots: the knot stride, by default the largest K_b of the batch (one number read back).  Returns a
+    LocalAlignment."""
+    cfg = _local_config(mode, min_rows, spacing, half_window, rot_open, ratio_max)
+    if max_knots is not None and not 1 <= int(max_knots) <= _lib.LOC_KMAX:
+        raise ValueError(f"local_align_ragged: max_knots must be in [1, {_lib.LOC_KMAX}]")
+    B, P = _local_args(ts, pos, quat, offsets, R, t, s)
+    _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    Kmax = int(max_knots) if max_knots is not None else _knot_stride(ts, offsets, cfg.spacing, B, P)
+    dev = ts.device
+    f = dict(dtype=torch.float64, device=dev)
+    i = dict(dtype=torch.int32, device=dev)
+    la = LocalAlignment(knot_R=torch.empty((B, Kmax, 9), **f), knot_t=torch.empty((B, Kmax, 3), **f), knot_s=torch.empty((B, Kmax), **f),
+                        knot_n=torch.empty((B, Kmax), **i), knot_rms=torch.empty((B, Kmax), **f), knot_flags=torch.empty((B, Kmax), **i),
+                        n_knots=torch.empty((B,), **i), track_status=torch.empty((B,), **i), ts=ts, offsets=offsets, R=R, t=t, s=s,
+                        spacing=cfg.spacing, half_window=cfg.half_window, mode=mode)
+    check(_lib.load().gsf_sim3_local_fit_dev(context().handle, _p(ts), _p(pos), _p(gps), _p(valid), _p(offsets), B, _p(R), _p(t), _p(s), C.byref(cfg),
+                                             Kmax, _p(la.knot_R), _p(la.knot_t), _p(la.knot_s), _p(la.knot_n), _p(la.knot_rms), _p(la.knot_flags),
+                                             _p(la.n_knots), _p(la.track_status)))
+    if run_status is not None:                                            # failed runs: no knots, NaN rows (the blend sees the status word)
+        skip = run_status != 0
+        la.track_status = torch.where(skip, la.track_status | _lib.LOC_SKIPPED, la.track_status)
+        la.n_knots = torch.where(skip, torch.zeros_like(la.n_knots), la.n_knots)
+        nan = float("nan")
+        la.knot_R, la.knot_t = la.knot_R.masked_fill(skip[:, None, None], nan), la.knot_t.masked_fill(skip[:, None, None], nan)
+        la.knot_s, la.knot_rms = la.knot_s.masked_fill(skip[:, None], nan), la.knot_rms.masked_fill(skip[:, None], nan)
+        la.knot_n, la.knot_flags = la.knot_n.masked_fill(skip[:, None], 0), la.knot_flags.masked_fill(skip[:, None], 0)
+    la.pos, la.quat, la.scale_at, la.pose_flags = local_apply_ragged(ts, pos, quat, offsets, R, t, s, cfg.spacing, la.knot_R, la.knot_t, la.knot_s,
+                                                                     la.knot_flags, la.n_knots, la.track_status)
+    return la
+
+
+def local_align_fused(rb, r, **kw):
+    """local_align_ragged on the result r of run_fusion_ragged / run_fusion_batch for the batch rb: the run's global Sim3, the aligned
+    fixes, their mask and run_status are r's, as at gate_fused.  Failed runs pass through as NaN rows."""
+    return local_align_ragged(rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4), r.aligned.reshape(-1, 3), r.valid.reshape(-1),
+                              rb.slam_offsets, r.R, r.t, r.s, run_status=r.run_status, **kw)
+
+
+def refuse_local(rb, r, la, want_cov=False, skip_seconds=5.0, config=None):
+    """Fuse again with the locally aligned track la (local_align_fused) as the motion source: the existing ekf_fuse_ragged on la.pos /
+    la.quat with their row 0 as every track's initial pose -- calculate_relative_pose is linear in the positions and invariant under a
+    common rotation, so the filter's increments then carry the local scale; no fuse kernel knows of it -- optionally
+    ekf_covariance_ragged, and step 6's nearest-fix error rows for the raw SLAM track, the locally aligned one and the fused one.  Tracks
+    the run skipped are fused from NaN rows and should be ignored, as la.track_status says.  Returns a RunResult in the shape of
+    refuse_gated's: pos (P,3), quat (P,4), status (B,), valid (P,), err_stats (B,4) / errors (P,) of the fused track, cov, and
+    err_stats3 (3,B,4) / errors3 (3,P) for raw / local-aligned / fused."""
+    ts, pos = rb.ts.reshape(-1), rb.pos.reshape(-1, 3)
+    aligned, valid, offsets = r.aligned.reshape(-1, 3), r.valid.reshape(-1).contiguous(), rb.slam_offsets
     B, P = _offsets_chk(offsets), int(ts.numel())
     dev = ts.device
-    off = offsets.cpu().tolist()
-    N = max([off[b + 1] - off[b] for b in range(B)] + [1])
-    row = torch.arange(N, dtype=torch.int64, device=dev)[None, :]
-    n = (offsets[1:] - offsets[:-1])[:, None]
-    inside = row < n
-    idx = torch.clamp(offsets[:-1, None] + torch.minimum(row, torch.clamp(n - 1, min=0)), max=max(P - 1, 0))
-    if P == 0:
-        return RunResult(pos=po, quat=qo, status=st, valid=vk, err_stats=torch.zeros((B, 4), dtype=torch.float64, device=dev),
-                         errors=torch.empty((0,), dtype=torch.float64, device=dev), cov=cov)
-    dv = torch.where(inside, vk[idx], torch.zeros_like(vk[idx]))
-    stats, err = eval_errors_batch(ts[idx].contiguous(), po[idx].contiguous(), aligned[idx].contiguous(), dv.contiguous(), skip_seconds=skip_seconds)
-    errors = torch.full((P,), float("nan"), dtype=torch.float64, device=dev)
-    errors[idx[inside]] = err[inside]
-    return RunResult(pos=po, quat=qo, status=st, valid=vk, err_stats=stats, errors=errors, cov=cov)
+    if P:
+        first = torch.clamp(offsets[:-1], max=P - 1)                      # (an empty track's row is never read)
+        ip, iq = la.pos[first].contiguous(), la.quat[first].contiguous()
+    else:
+        ip, iq = torch.zeros((B, 3), dtype=torch.float64, device=dev), torch.zeros((B, 4), dtype=torch.float64, device=dev)
+    po, qo, st = ekf_fuse_ragged(ts, la.pos, la.quat, aligned, valid, offsets, ip, iq, config=config)
+    cov = ekf_covariance_ragged(ts, la.quat, aligned, valid, offsets, config=config, run_status=r.run_status) if want_cov else None
+    rows = _step6_rows(ts, offsets, (pos, la.pos, po), aligned, valid, skip_seconds)
+    return RunResult(pos=po, quat=qo, status=st, valid=valid, err_stats=rows[2][0], errors=rows[2][1], cov=cov, init_pos=ip, init_quat=iq,
+                     err_stats3=torch.stack([x[0] for x in rows]), errors3=torch.stack([x[1] for x in rows]))
 
 
 class PoseQuery:

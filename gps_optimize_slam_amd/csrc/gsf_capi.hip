@@ -722,4 +722,42 @@ int gsf_innovation_gate_dev(gsf_ctx* ctx, const double* ts, const double* pos, c
                                   valid_out, nis_out, stats, gate_status);
 }
 
+// local Sim3 alignment: device forms only (include/gsf.h; the Python binding uploads host arrays itself)
+int gsf_sim3_local_fit_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* gps, const uint8_t* valid, const int64_t* offsets,
+                           int64_t B, const double* R, const double* t, const double* s, const gsf_local_config* cfg, int32_t Kmax,
+                           double* knot_R, double* knot_t, double* knot_s, int32_t* knot_n, double* knot_rms, int32_t* knot_flags,
+                           int32_t* n_knots, int32_t* track_status)
+{
+    GSF_REQUIRE(ctx && cfg && offsets, "ctx/cfg/offsets is NULL");
+    GSF_REQUIRE(B >= 0 && B <= 0x7fffffff, "bad B");
+    GSF_REQUIRE(Kmax >= 1 && Kmax <= 4096, "Kmax must be in [1, 4096]");
+    GSF_REQUIRE(cfg->mode == GSF_LOC_SCALE || cfg->mode == GSF_LOC_SIM3, "mode must be GSF_LOC_SCALE or GSF_LOC_SIM3");
+    GSF_REQUIRE(cfg->min_rows >= (cfg->mode == GSF_LOC_SIM3 ? 3 : 2), "min_rows must be >= 2 (mode 0) / >= 3 (mode 1)");
+    GSF_REQUIRE(cfg->spacing > 0.0 && cfg->spacing < INFINITY, "spacing must be positive and finite");
+    GSF_REQUIRE(cfg->half_window >= 0.0, "half_window must be >= 0");
+    GSF_REQUIRE(cfg->rot_open >= 0.0 && cfg->ratio_max >= 1.0, "rot_open must be >= 0 and ratio_max >= 1");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(ts && pos && gps && valid && R && t && s, "NULL input array");
+    GSF_REQUIRE(knot_R && knot_t && knot_s && knot_n && knot_rms && knot_flags && n_knots && track_status, "NULL output array");
+    return launch_local_fit(ctx, ts, pos, gps, valid, offsets, B, R, t, s, cfg, Kmax, knot_R, knot_t, knot_s, knot_n, knot_rms, knot_flags,
+                            n_knots, track_status);
+}
+
+int gsf_sim3_local_apply_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const int64_t* offsets, int64_t B,
+                             const double* R, const double* t, const double* s, double spacing, int32_t Kmax, const double* knot_R,
+                             const double* knot_t, const double* knot_s, const int32_t* knot_flags, const int32_t* n_knots,
+                             const int32_t* track_status, double* pos_out, double* quat_out, double* scale_at, int32_t* pose_flags)
+{
+    GSF_REQUIRE(ctx && offsets, "ctx/offsets is NULL");
+    GSF_REQUIRE(B >= 0 && B <= 0x7fffffff, "bad B");
+    GSF_REQUIRE(Kmax >= 1 && Kmax <= 4096, "Kmax must be in [1, 4096]");
+    GSF_REQUIRE(spacing > 0.0 && spacing < INFINITY, "spacing must be positive and finite");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(ts && pos && quat && R && t && s, "NULL input array");
+    GSF_REQUIRE(knot_R && knot_t && knot_s && knot_flags && n_knots && track_status, "NULL knot array");
+    GSF_REQUIRE(pos_out && quat_out && scale_at && pose_flags, "NULL output array");
+    return launch_local_apply(ctx, ts, pos, quat, offsets, B, R, t, s, spacing, Kmax, knot_R, knot_t, knot_s, knot_flags, n_knots, track_status,
+                              pos_out, quat_out, scale_at, pose_flags);
+}
+
 }  // extern "C"

@@ -137,6 +137,16 @@ int launch_innovation_gate(gsf_ctx* ctx, const double* ts, const double* pos, co
                            const gsf_ekf_config* cfg, int64_t B, const double* gates, int32_t K, double arm_seconds, int32_t max_run,
                            uint8_t* valid_out, double* nis_out, double* stats, int32_t* gate_status);
 
+// local Sim3 alignment (gsf_local.hip): the bodies of gsf_sim3_local_fit_dev / gsf_sim3_local_apply_dev, arguments checked by the caller
+int launch_local_fit(gsf_ctx* ctx, const double* ts, const double* pos, const double* gps, const uint8_t* valid, const int64_t* offsets,
+                     int64_t B, const double* R, const double* t, const double* s, const gsf_local_config* cfg, int32_t Kmax, double* knot_R,
+                     double* knot_t, double* knot_s, int32_t* knot_n, double* knot_rms, int32_t* knot_flags, int32_t* n_knots,
+                     int32_t* track_status);
+int launch_local_apply(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const int64_t* offsets, int64_t B, const double* R,
+                       const double* t, const double* s, double spacing, int32_t Kmax, const double* knot_R, const double* knot_t,
+                       const double* knot_s, const int32_t* knot_flags, const int32_t* n_knots, const int32_t* track_status, double* pos_out,
+                       double* quat_out, double* scale_at, int32_t* pose_flags);
+
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
 int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);
 int launch_gps_prefilter_auto(gsf_ctx* ctx, const double* t, const double* pos, const int64_t* offsets, const int32_t* counts, int64_t B,

@@ -581,6 +581,43 @@ def gate_gnss_fixes(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial, gl
             "status": int(g.status[0].item()), "nis": h(g.nis_out), "gates": h(g.gates), "aligned": np.asarray(aligned)}
 
 
+def align_trajectory_local(slam_data, aligned_gps, valid_mask, R, t, s, spacing=30.0, half_window=30.0, min_rows=8, mode="scale", rot_open=1e-3,
+                           ratio_max=2.0):
+    """Local Sim3 alignment of one track on NumPy arrays (batch.local_align_ragged; definitions in include/gsf.h, gsf_sim3_local_fit_dev):
+    Sim3 knots every `spacing` seconds along the track, each fitted on the usable rows of aligned_gps / valid_mask (what
+    dynamic_time_alignment returned) within `half_window` of it, and every pose mapped by the blend of its neighbouring valid knots.  R, t,
+    s: the track's global Sim3 (compute_sim3_transform_robust).  Raises ValueError where the batched form sets a track status (no pose,
+    stamps that decrease, more than 4096 knots).  Returns a dict of host arrays: 'positions' (n,3), 'quaternions' (n,4), 'scale_at' (n,),
+    'pose_flags' (n,) (LP_* bits of _lib), 'knot_stamps', 'knot_R' (K,3,3), 'knot_t' (K,3), 'knot_s', 'knot_n', 'knot_rms', 'knot_flags'
+    (KNOT_* bits), 'knot_valid' (K,) bool.  The positions / quaternions go to ekf_fuse_aligned and its kin as the motion source."""
+    import torch
+    from . import batch as gb
+    from . import _lib
+    gb._local_config(mode, min_rows, spacing, half_window, rot_open, ratio_max)      # (argument errors need no device)
+    n = len(slam_data["timestamps"])
+    if n == 0:
+        raise ValueError("align_trajectory_local: the track has no pose")
+    ts = np.ascontiguousarray(slam_data["timestamps"], dtype=np.float64).reshape(n)
+    if np.isnan(ts).any() or (np.diff(ts) < 0).any():
+        raise ValueError("align_trajectory_local: the stamps are not non-decreasing")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.array(a, dtype=dt, order="C").reshape(shape)).to(dev)     # (a copy: the caller's arrays may be read-only)
+    la = gb.local_align_ragged(up(ts, (n,)), up(slam_data["positions"], (n, 3)), up(slam_data["quaternions"], (n, 4)), up(aligned_gps, (n, 3)),
+                               up(np.asarray(valid_mask) != 0, (n,), np.uint8), torch.tensor([0, n], dtype=torch.int64, device=dev), up(R, (1, 9)),
+                               up(t, (1, 3)), up(s, (1,)), spacing=spacing, half_window=half_window, min_rows=min_rows, mode=mode,
+                               rot_open=rot_open, ratio_max=ratio_max)
+    st = int(la.track_status[0].item())
+    if st:
+        names = [nm for nm, bit in (("empty", _lib.LOC_EMPTY), ("unsorted", _lib.LOC_UNSORTED), ("too many knots", _lib.LOC_TOO_MANY)) if st & bit]
+        raise ValueError(f"align_trajectory_local: track status {st} ({', '.join(names)})")
+    K = int(la.n_knots[0].item())
+    stamps, _, ok = la.scale_curve(0)
+    h = lambda x: x.cpu().numpy()
+    return {"positions": h(la.pos), "quaternions": h(la.quat), "scale_at": h(la.scale_at), "pose_flags": h(la.pose_flags), "knot_stamps": stamps,
+            "knot_R": h(la.knot_R[0, :K]).reshape(K, 3, 3), "knot_t": h(la.knot_t[0, :K]), "knot_s": h(la.knot_s[0, :K]), "knot_n": h(la.knot_n[0, :K]),
+            "knot_rms": h(la.knot_rms[0, :K]), "knot_flags": h(la.knot_flags[0, :K]), "knot_valid": ok}
+
+
 class FusionSession:
     """One track fused as it grows (batch.FusionStream with one track; host arrays in, host arrays out): push() takes the next poses and
     returns their fused rows and how far the track is final.  init_pos (3,) / init_quat (4,) = the Sim3-transformed pose 0, as at

@@ -787,6 +787,79 @@ GSF_API int gsf_stream_gather_dev(gsf_ctx *ctx, int64_t B, int64_t cap, const in
                                   const double *ring_pos, const double *ring_quat, const int64_t *lo, const int64_t *out_offsets,
                                   double *ts_out, double *pos_out, double *quat_out);
 
+/* ---- local Sim3 alignment: windowed knots against SLAM scale drift ------------------------------------------------------------------------
+   The chain fits ONE Sim3 per track (EKFGPSSLAM.py:973-1006) and applies its scale to the whole run, while a monocular front end drifts in
+   scale over minutes.  These two entries fit Sim3 KNOTS on a time grid along each track and map every pose by a blend of the neighbouring
+   knots.  The locally aligned track is a track like any other: handed to gsf_ekf_fuse_ragged_dev (and the sweep, outage and gate entries)
+   as the motion source it scales the filter's increments by the local scale, because calculate_relative_pose is linear in the positions
+   and invariant under a common rotation.  No fuse kernel knows of it; the reference has no such step and nothing of its flow changes.
+   In, per track b = rows offsets[b] .. offsets[b + 1]: ts, pos[.][3], quat[.][4] of the original SLAM track; gps[.][3] / valid as
+   dynamic_time_alignment returns them (NaN allowed); the track's global R[9], t[3], s.  A row is USABLE when valid != 0 and its fix is
+   finite (the rule of gsf_sim3_fit_rows_batch_dev).
+   [grid]  t0 = ts[first];  K_b = floor((ts[last] - t0) / spacing) + 2;  tau_k = fma(k, spacing, t0): every pose has a knot on each side.
+     Kmax = the caller's knot stride, 1 .. 4096: knot k of track b is slot b * Kmax + k of every knot array.
+     K_b > Kmax gives GSF_LOC_TOO_MANY, stamps that decrease inside a track (or a NaN stamp) GSF_LOC_UNSORTED, a track of 0 poses
+     GSF_LOC_EMPTY.  A track with any of these gets NaN rows and n_knots = 0; it is never truncated.
+   [window]  of knot k: the usable rows with -half_window <= (ts - tau_k) <= half_window, in double precision, the difference formed first.
+   [fit]  a_i / b_i the window's SLAM rows / fixes minus their means, H = sum a_i b_i^T:
+     GSF_LOC_SCALE (mode 0): R_k = the track's global R;  s_k = tr(R H) / sum |a_i|^2;  t_k = mean(b) - s_k R mean(a).  min_rows >= 2.
+       Well posed on a straight road, where the rotation of a full fit is not.
+     GSF_LOC_SIM3 (mode 1): the closed form of :436-451 as gsf_sim3_umeyama_batch_dev computes it from shifted raw moments (the scale
+       carries sigma1 + sigma2 + sigma3 as :444 is written).  min_rows >= 3.  A knot whose window is rotation-open,
+       (sigma2 + d sigma3) <= rot_open sigma1 (d = -1 where :441 flips), takes the mode-0 form and is flagged GSF_KNOT_ROT_FALLBACK.
+   [validity]  a knot is valid unless GSF_KNOT_FEW (fewer than min_rows rows), GSF_KNOT_VAR0 (sum |a_i|^2 / n < 1e-12) or GSF_KNOT_SCALE
+     (s_k <= 1e-6, or s_k / s outside [1 / ratio_max, ratio_max]) is set; a NaN fails every one of these tests.
+   Per knot: knot_R[9], knot_t[3], knot_s, knot_n (rows in the window), knot_rms (RMS of T_k(pos_i) - gps_i over them), knot_flags.  An
+   invalid knot keeps knot_n and its flags and gets NaN for the rest.  [slots]  Slots k >= n_knots[b] are NaN-FILLED (knot_n = 0,
+   knot_flags = 0): every call writes every byte of the B x Kmax knot arrays.
+   [neighbours]  of a pose with k = min(floor((ts - t0) / spacing), K_b - 2): L = the nearest valid knot <= k, Rr = the nearest valid
+     knot >= k + 1.  Both: w = (ts - tau_L) / (tau_Rr - tau_L), GSF_LP_BRIDGED when Rr - L > 1.  One: that knot alone, GSF_LP_HELD.  None:
+     the global transform, GSF_LP_GLOBAL.
+   [blend]  T_k(p) = s_k R_k p + t_k in the operation order of gsf_apply_sim3_batch_dev.
+     pos' = T_L(p) + w (T_Rr(p) - T_L(p)) -- this form, so equal knots return T_L(p) to the bit;
+     quat' = quaternion_nlerp(R_L (x) q, R_Rr (x) q, w) (:94-105), R (x) q as gsf_apply_sim3_batch_dev forms it; where the two products
+     are the same numbers the result is that product itself.  A quaternion whose norm is 0 / NaN / inf gives a NaN quaternion and
+     GSF_LP_BAD_QUAT.  scale_at = s_L + w (s_Rr - s_L).
+   A pose of a track whose track_status is not 0 gets NaN rows and GSF_LP_TRACK.
+   gsf_sim3_local_apply_dev takes knots from anywhere -- a caller may edit them or feed its own -- and reads exactly the fields the fit
+   writes: knot_R, knot_t, knot_s, knot_flags (the validity bits), n_knots, track_status.  With every knot of a track equal to its global
+   transform, pos_out / quat_out are the bytes of gsf_apply_sim3_batch_dev and scale_at is s.
+   Nothing outside rows offsets[b] .. offsets[b + 1] of a per-pose array is written.  One wave per (track, knot) for the fit, no LDS, no
+   atomics; one thread per pose for the blend; 2 x B x Kmax words of the context's kernel workspace (the neighbour tables).  Device
+   pointers, asynchronous on the context's stream.  There is no host-pointer form: the Python binding uploads host arrays itself. */
+typedef struct gsf_local_config {
+    int32_t mode;          /* GSF_LOC_SCALE / GSF_LOC_SIM3                                  [fit] */
+    int32_t min_rows;      /* fewest usable rows of a window: >= 2 (mode 0), >= 3 (mode 1)  [fit] */
+    double spacing;        /* seconds between knots, > 0                                    [grid] */
+    double half_window;    /* seconds on either side of a knot, >= 0                        [window] */
+    double rot_open;       /* mode 1: rotation-open threshold, default 1e-3                 [fit] */
+    double ratio_max;      /* largest s_k / s and s / s_k of a valid knot, >= 1, default 2  [validity] */
+} gsf_local_config;
+#define GSF_LOC_SCALE 0           /* gsf_local_config.mode: scale and translation per knot under the global rotation   [fit] */
+#define GSF_LOC_SIM3 1            /* ... the full closed form per knot, mode 0 where the window is rotation-open       [fit] */
+#define GSF_LOC_EMPTY 1           /* track_status: the track has no pose                                               [grid] */
+#define GSF_LOC_UNSORTED 2        /* ... its stamps are not non-decreasing, or one is NaN                              [grid] */
+#define GSF_LOC_TOO_MANY 4        /* ... K_b > Kmax                                                                    [grid] */
+#define GSF_LOC_SKIPPED 8         /* ... set by a caller for a track it wants passed through as NaN rows (the Python binding: run_status != 0) */
+#define GSF_KNOT_FEW 1            /* knot_flags: fewer than min_rows usable rows in the window                         [validity] */
+#define GSF_KNOT_VAR0 2           /* ... sum |a_i|^2 / n < 1e-12                                                       [validity] */
+#define GSF_KNOT_SCALE 4          /* ... s_k <= 1e-6 or s_k / s outside [1 / ratio_max, ratio_max]                     [validity] */
+#define GSF_KNOT_ROT_FALLBACK 8   /* ... mode 1, rotation-open window: fitted in the mode-0 form (the knot is valid)   [fit] */
+#define GSF_LP_BRIDGED 1          /* pose_flags: the two knots are not adjacent (Rr - L > 1)                           [neighbours] */
+#define GSF_LP_HELD 2             /* ... one valid knot on one side only: that knot alone                              [neighbours] */
+#define GSF_LP_GLOBAL 4           /* ... no valid knot on either side: the global transform                            [neighbours] */
+#define GSF_LP_BAD_QUAT 8         /* ... the pose's quaternion could not be normalised: NaN quaternion                 [blend] */
+#define GSF_LP_TRACK 16           /* ... the track's status is not 0: NaN row */
+GSF_API int gsf_sim3_local_fit_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *gps, const uint8_t *valid,
+                                   const int64_t *offsets, int64_t B, const double *R, const double *t, const double *s,
+                                   const gsf_local_config *cfg, int32_t Kmax, double *knot_R, double *knot_t, double *knot_s,
+                                   int32_t *knot_n, double *knot_rms, int32_t *knot_flags, int32_t *n_knots, int32_t *track_status);
+GSF_API int gsf_sim3_local_apply_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *offsets,
+                                     int64_t B, const double *R, const double *t, const double *s, double spacing, int32_t Kmax,
+                                     const double *knot_R, const double *knot_t, const double *knot_s, const int32_t *knot_flags,
+                                     const int32_t *n_knots, const int32_t *track_status, double *pos_out, double *quat_out,
+                                     double *scale_at, int32_t *pose_flags);
+
 /* ---- pose queries: the fused track at any stamp, sensor points into the track's frame ----------------------------------------------------
    The fused track exists at the SLAM stamps; LiDAR returns, other exposures, map points and a second receiver have stamps of their own.
    These entries evaluate the track between its poses with the rule the filter itself uses for orientations (quaternion_nlerp,
