@@ -973,6 +973,57 @@ def ekf_covariance_batch(batch, config=None, want_filtered=True):
                                  want_filtered=want_filtered)
 
 
+# ---------------------------------------------------------------------------- whole-track RTS smoothing (gsf_ekf_smooth_ragged_dev)
+class SmoothedTrack:
+    """The fixed-interval RTS smoother over fused tracks (ekf_smooth_ragged), flat over the P rows of the batch: pos (P,3) / quat (P,4) = the
+    smoothed track (the quaternion is the filter's: GNSS never touches it); cov (P,7) = the smoothed diagonal [x y z qx qy qz qw];
+    pos_filt (P,3) / cov_filt (P,7) or None = the causal filter's own track and diagonal; flags (P,) uint8 of _lib.POSE_* bits, where
+    POSE_SMOOTHED means "a later fix of the same span was applied" (every other row holds the filter's bytes) and POSE_SPAN_START marks row 0
+    and every sharp-turn recovery; status (B,) int32 of _lib.ST_* bits (ST_RTS_APPLIED: some row is POSE_SMOOTHED); offsets (B+1,)."""
+
+    def __init__(self, pos, quat, cov, pos_filt, cov_filt, flags, status, offsets):
+        self.pos, self.quat, self.cov, self.pos_filt, self.cov_filt = pos, quat, cov, pos_filt, cov_filt
+        self.flags, self.status, self.offsets = flags, status, offsets
+
+    def dense(self, which="cov"):
+        """(P,7,7) matrices, the shape the reference's lists hold (which="filtered": the filter's, needs want_filtered=True)"""
+        d = self.cov_filt if which == "filtered" else self.cov
+        if d is None:
+            raise ValueError("SmoothedTrack.dense: the filtered covariance was not asked for (want_filtered=True)")
+        return torch.diag_embed(d)
+
+    def correction(self):
+        """pos - pos_filt (P,3): what the later fixes moved every pose by (needs want_filtered=True)"""
+        if self.pos_filt is None:
+            raise ValueError("SmoothedTrack.correction: the filtered track was not asked for (want_filtered=True)")
+        return self.pos - self.pos_filt
+
+
+def ekf_smooth_ragged(ts, pos, quat, gps, valid, offsets, init_pos, init_quat, config=None, run_status=None, want_filtered=False):
+    """The fixed-interval RTS smoother over whole tracks (gsf_ekf_smooth_ragged_dev; definition: include/gsf.h), one launch on torch's
+    current stream.  Inputs as ekf_fuse_ragged -- ts (P,), pos (P,3) / quat (P,4) = the original SLAM poses, gps (P,3) / valid (P,) uint8 =
+    the time-aligned fixes, offsets (B+1,) int64, init_pos (B,3) / init_quat (B,4) -- plus run_status (B,) int32 or None: tracks with
+    run_status != 0 get NaN rows, zero flags and status 0.  The forward pass is the filter of ekf_fuse_ragged; every sharp-turn recovery
+    starts a new span, and each span is smoothed backwards from its last pose.  want_filtered: also the filter's own track and diagonal.
+    Returns a SmoothedTrack."""
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid")
+    _chk(init_pos, torch.float64, (B, 3), "init_pos"); _chk(init_quat, torch.float64, (B, 4), "init_quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    cfg = EkfConfig.from_config(config or CONFIG)
+    f = dict(dtype=torch.float64, device=ts.device)
+    st = SmoothedTrack(torch.empty((P, 3), **f), torch.empty((P, 4), **f), torch.empty((P, 7), **f),
+                       torch.empty((P, 3), **f) if want_filtered else None, torch.empty((P, 7), **f) if want_filtered else None,
+                       torch.empty((P,), dtype=torch.uint8, device=ts.device), torch.empty((B,), dtype=torch.int32, device=ts.device), offsets)
+    check(_lib.load().gsf_ekf_smooth_ragged_dev(context().handle, _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(offsets), _p(init_pos),
+                                                _p(init_quat), _p(run_status), C.byref(cfg), B, _p(st.pos), _p(st.quat), _p(st.cov), _p(st.pos_filt),
+                                                _p(st.cov_filt), _p(st.flags), _p(st.status)))
+    return st
+
+
 # ---------------------------------------------------------------------------- EKF noise sweep (gsf_ekf_noise_sweep_dev)
 NOISE_P0_MAX, NOISE_R_MIN, NOISE_R_MAX, NOISE_QDT_MAX = 1e8, 1e-8, 1e8, 1e14      # the stated range of the noise values (include/gsf.h, gsf_ekf_config)
 _LN_2PI = 1.8378770664093453
@@ -1437,6 +1488,23 @@ def _step6_rows(ts, offsets, trajs, aligned, valid, skip_seconds):
         errors[idx[inside]] = err[inside]
         out.append((stats, errors))
     return out
+
+
+def smooth_fused(rb, r, valid=None, config=None, skip_seconds=5.0):
+    """ekf_smooth_ragged on the result r of run_fusion_ragged for the batch rb: the aligned fixes, their mask and run_status are r's (valid=:
+    another mask over the same rows, e.g. g.valid(k) of gate_fused), the initial pose of every track is built as sweep_noise_fused builds
+    it.  Returns the SmoothedTrack (with the filter's own track) carrying step 6's nearest-fix error of the fused track r returned and of
+    the smoothed one against the fixes of the mask: err_stats2 (2,B,4) = {fused, smoothed} x {count, mean, median, RMSE}, errors2 (2,P)
+    (NaN where not evaluated)."""
+    ts, aligned, offsets = rb.ts.reshape(-1), r.aligned.reshape(-1, 3), rb.slam_offsets
+    v = (r.valid.reshape(-1) if valid is None else valid).contiguous()
+    ip, iq = _fused_init_pose(rb, r)
+    st = ekf_smooth_ragged(ts, rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4), aligned, v, offsets, ip, iq, config=config, run_status=r.run_status,
+                           want_filtered=True)
+    rows = _step6_rows(ts, offsets, (r.fused.pos.reshape(-1, 3), st.pos), aligned, v, skip_seconds)
+    st.err_stats2, st.errors2 = torch.stack([x[0] for x in rows]), torch.stack([x[1] for x in rows])
+    st.valid, st.init_pos, st.init_quat = v, ip, iq
+    return st
 
 
 def refuse_gated(rb, r, g, k=0, want_cov=False, skip_seconds=5.0, config=None):

@@ -496,6 +496,40 @@ def ekf_fuse_aligned(timestamps, positions, quaternions, aligned_gps, valid_mask
     return po, qo, int(st[0])
 
 
+def ekf_smooth_aligned(timestamps, positions, quaternions, aligned_gps, valid_mask, init_pos, init_quat, global_config=None):
+    """The fixed-interval RTS smoother over one whole track, beside ekf_fuse_aligned (gsf_ekf_smooth_ragged_dev; definition: include/gsf.h):
+    the forward pass is ekf_fuse_aligned's filter, every sharp-turn recovery starts a new span, each span is smoothed backwards from its
+    last pose.  Host arrays -> dict of host arrays: 'pos' (n,3) / 'quat' (n,4) the smoothed track, 'cov' (n,7) the smoothed diagonal,
+    'pos_filt' / 'cov_filt' the causal filter's, 'flags' (n,) uint8 of _lib.POSE_* bits, 'status' (ST_* bits)."""
+    import torch
+    from . import batch as gb
+    ts = f64(timestamps).ravel()
+    n = ts.size
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(shape)).to(dev)
+    r = gb.ekf_smooth_ragged(up(ts, (n,)), up(positions, (n, 3)), up(quaternions, (n, 4)), up(aligned_gps, (n, 3)), up(valid_mask, (n,), np.uint8),
+                             torch.tensor([0, n], dtype=torch.int64, device=dev), up(init_pos, (1, 3)), up(init_quat, (1, 4)),
+                             config=global_config, want_filtered=True)
+    h = lambda t: t.cpu().numpy()
+    return {"pos": h(r.pos), "quat": h(r.quat), "cov": h(r.cov), "pos_filt": h(r.pos_filt), "cov_filt": h(r.cov_filt), "flags": h(r.flags),
+            "status": int(r.status[0].item())}
+
+
+def smooth_trajectory(slam_data_in, gps_data_in, sim3_pos_initial, sim3_quat_initial, global_config):
+    """apply_ekf_correction's arguments, the whole-track smoother's result: the same alignment call (ref :847), the initial pose = row 0 of
+    the Sim3-transformed track, then ekf_smooth_aligned.  Returns its dict; an empty track gives empty arrays (ref :835)."""
+    n = len(slam_data_in["timestamps"])
+    sim3_pos_initial, sim3_quat_initial = np.asarray(sim3_pos_initial), np.asarray(sim3_quat_initial)
+    if n == 0:
+        return {"pos": np.empty((0, 3)), "quat": np.empty((0, 4)), "cov": np.empty((0, 7)), "pos_filt": np.empty((0, 3)), "cov_filt": np.empty((0, 7)),
+                "flags": np.empty((0,), np.uint8), "status": 0}
+    if not (sim3_pos_initial.shape[0] == n and sim3_quat_initial.shape[0] == n):
+        raise ValueError(f"Sim3-transformed trajectory length ({sim3_pos_initial.shape[0]}) != SLAM timestamp count ({n})")
+    aligned, valid = dynamic_time_alignment(slam_data_in, gps_data_in, global_config["time_alignment"])     # ref :847
+    return ekf_smooth_aligned(slam_data_in["timestamps"], slam_data_in["positions"], slam_data_in["quaternions"], aligned, valid,
+                              sim3_pos_initial[0], sim3_quat_initial[0], global_config)
+
+
 def sweep_ekf_noise(slam_data, gps_data, sim3_pos_initial, sim3_quat_initial, global_config, candidates, skip_seconds=0.0, min_updates=1, trace=None):
     """Innovation statistics of apply_ekf_correction's filter for K candidates of CONFIG['ekf'] on one track (gsf_ekf_noise_sweep_dev;
     definitions in include/gsf.h): the same alignment call as apply_ekf_correction (ref :847), the initial pose = row 0 of the

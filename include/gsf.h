@@ -581,6 +581,41 @@ GSF_API int gsf_ekf_cov_ragged(gsf_ctx *ctx, const double *ts, const double *qua
                                const int64_t *offsets, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
                                double *cov_filt, double *cov_out, uint8_t *pose_flags, int32_t *status);
 
+/* ---- whole-track RTS smoothing: the fixed-interval smoother over the fused track -----------------------------------------------------------
+   apply_ekf_correction (EKFGPSSLAM.py:831-935) runs a causal filter and hands rts_smoother_segment (:777-803) only the poses of a GNSS
+   outage (:906-923): wherever GNSS is present the fused pose at stamp t uses the fixes up to t and none after it.  The reference keeps
+   everything the fixed-interval smoother needs (ekf_states_*_hist, ekf_covs_*_hist) and never makes the call; this entry makes it.
+   Forward pass -- the filter of gsf_ekf_fuse_ragged_dev / gsf_ekf_cov_ragged_dev, exactly: dt[i] = max(1e-6, ts[i] - ts[i-1]) (:865),
+   avail[i] as at :867-869, Pp[i] = Pf[i-1] + Q dt[i]; with a fix the gain k = Pp / (Pp + R) and the Joseph Pf; a sharp-turn recovery takes
+   the one-step blend weight 1 / steps (:752-768, :889); outages and the sharp-turn decision are gsf_ekf_cov_ragged_dev's.  xf, xp = the
+   filtered and the predicted position, g[i] = xf[i] - xp[i] = the applied correction (0 without an update).
+   Spans -- every recovery b that the filter judges a sharp turn starts a new span: [0..b1-1], [b1..b2-1], ..., [bm..N-1].  The reference's
+   judgement that RTS is not to be trusted across such an outage is kept; a caller who wants to smooth through turns raises
+   sharp_turn_yaw_rate_threshold_deg_per_sec (a pair never exceeds once thr dt >= pi).
+   Backward pass, per span and axis -- rts_smoother_segment (:777-803) on the span: A[k] = Pf[k] / Pp[k+1] (A[k] = 0 where Pp[k+1] == 0:
+   the reference lands there through pinv); xs[last] = xf[last], Ps[last] = Pf[last]; xs[k] = xf[k] + A[k] (xs[k+1] - xp[k+1]);
+   Ps[k] = Pf[k] + A[k]^2 (Ps[k+1] - Pp[k+1]).  In correction coordinates e = xs - xf, d = Ps - Pf:
+       e[k] = A[k] (e[k+1] + g[k+1]),   d[k] = A[k]^2 (d[k+1] + (Pf[k+1] - Pp[k+1])),   e = d = 0 at a span's last pose
+   -- two affine suffix scans per axis, and A := 0 on a span's last pose makes it one scan per track.  Consequences: the quaternion axes
+   are never updated, so Ps = Pf on axes 3-6 and the smoothed quaternion is the filter's (the reference re-normalises it: <= 2.2e-16);
+   poses of a sharp-turn outage, and poses after the last update of a span, keep their filtered values exactly; a zero-variance axis
+   (P0 = Q = 0) comes back unsmoothed and free of NaN.  A <= 1, so products only underflow to 0: the stated range of the noise values
+   (gsf_ekf_config: 0 <= P0 <= 1e8, 1e-8 <= R <= 1e8, 0 <= Q dt <= 1e14) holds unchanged.
+   In: as gsf_ekf_fuse_ragged_dev, plus run_status as in gsf_ekf_cov_ragged_dev (may be NULL: NaN rows, zero flags, status 0, inputs not
+   read).  Out: pos_out[P][3], quat_out[P][4] = the smoothed track; cov_out[P][7] = the smoothed diagonal; pos_filt[P][3], cov_filt[P][7]
+   (the filter's own track and diagonal), pose_flags[P], status[B]: each may be NULL.  pose_flags = GSF_POSE_GNSS_USED | _IN_OUTAGE |
+   _SHARP_TURN with their meanings above; GSF_POSE_SMOOTHED means HERE "a later fix of the same span was applied" -- exactly the rows
+   where e, d are not structurally zero (every other row returns the filter's bytes); GSF_POSE_SPAN_START marks row 0 and every
+   sharp-turn recovery.  status = GSF_ST_* bits as gsf_ekf_fuse_ragged_dev sets them, with GSF_ST_RTS_APPLIED set when any row is
+   GSF_POSE_SMOOTHED.  An empty track has no rows and status 0.  One wave per track, two passes over it (the backward pass re-reads what
+   the forward pass parked in the track's own cov_out rows), no workspace, any track length.  Device pointers, asynchronous on the
+   context's stream; there is no host-pointer form: the Python binding uploads host arrays itself. */
+#define GSF_POSE_SPAN_START 16 /* gsf_ekf_smooth_ragged_dev: first row of a smoothing span (row 0, every sharp-turn recovery) */
+GSF_API int gsf_ekf_smooth_ragged_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
+                                      const uint8_t *valid, const int64_t *offsets, const double *init_pos, const double *init_quat,
+                                      const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B, double *pos_out, double *quat_out,
+                                      double *cov_out, double *pos_filt, double *cov_filt, uint8_t *pose_flags, int32_t *status);
+
 /* ---- EKF noise sweep: innovation statistics of the filter for K noise candidates per track ------------------------------------------------
    CONFIG['ekf'] (initial_cov_diag, process_noise_diag, meas_noise_diag, EKFGPSSLAM.py:25-27) is tuned by hand; the standard way to choose
    and check such values is the filter's own innovation sequence: its normalised innovation squared (NIS; mean 3 for a consistent 3-axis
