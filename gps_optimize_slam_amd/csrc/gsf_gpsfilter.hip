@@ -15,196 +15,11 @@
 // One 128-thread block per problem; rows of a problem are contiguous ([total] arrays + int64 offsets[P+1]).
 #include "gsf_mt19937.hpp"
 #include "gsf_wave_common.hpp"   // wave_sum on DPP (no LDS round trips)
+#include "gsf_poly_core.hpp"     // the fit itself: PolyModel, fit_subset*, poly_predict, dynamic_max_trials (host/device, window-local time)
 
 using namespace gsf;
 
 namespace {
-
-constexpr int RP_MAX_SAMPLES = 16;
-constexpr int RP_MAX_DEGREE = 3;
-
-template <int MAXD> struct PolyModelT { double coef[MAXD], intercept; };
-typedef PolyModelT<RP_MAX_DEGREE> PolyModel;
-
-template <int MAXD>
-__device__ __forceinline__ double poly_predict(const PolyModelT<MAXD>& m, int degree, double t)
-{
-    // (compile-time bounds: a loop to the run-time degree indexes m.coef dynamically, which put every model of the chain kernel into scratch
-    // memory -- each prediction then started with dependent trips to it.  The terms k < degree are formed exactly as that loop formed them.)
-    double acc = 0.0, tk = t;
-#pragma unroll
-    for (int k = 0; k < MAXD; ++k) { acc = (k < degree) ? (acc + m.coef[k] * tk) : acc; tk *= t; }
-    return acc + m.intercept;
-}
-
-// LinearRegression(fit_intercept=True) on PolynomialFeatures(degree)(t): centre the columns t^k and y by their subset means, solve
-// the least squares by modified Gram-Schmidt (the constant column is identically zero after centring: coefficient 0),
-// intercept = mean(y) - sum coef_k mean(t^k).
-// MAXD / MAXS size the per-thread arrays (3 / 16 for the kernels of the hot path, 8 / 64 for the wide kernel); REORTH: a second
-// Gram-Schmidt sweep per column ("twice is enough"), for the higher degrees whose centred power columns are nearly dependent.
-template <int MAXD, int MAXS, bool REORTH>
-__device__ __forceinline__ PolyModelT<MAXD> fit_subset_t(const double* __restrict__ t, const double* __restrict__ y, const int32_t* __restrict__ idx,
-                                                         int ms, int degree, int ystride = 1)
-{
-    double c[MAXD][MAXS], yy[MAXS], mean[MAXD], ymean = 0.0;
-    for (int k = 0; k < MAXD; ++k) mean[k] = 0.0;
-    for (int i = 0; i < ms; ++i) {
-        const double ti = t[idx[i]];
-        double tk = ti;
-        for (int k = 0; k < degree; ++k) { c[k][i] = tk; mean[k] += tk; tk *= ti; }
-        yy[i] = y[(int64_t)idx[i] * ystride]; ymean += yy[i];
-    }
-    const double rn = 1.0 / (double)ms;
-    ymean *= rn;
-    for (int k = 0; k < degree; ++k) mean[k] *= rn;
-    for (int i = 0; i < ms; ++i) { yy[i] -= ymean; for (int k = 0; k < degree; ++k) c[k][i] -= mean[k]; }
-    // MGS: c_k = sum_{j<=k} R[j][k] q_j, q_j stored in place of c_j;  z_j = q_j . y
-    double Rm[MAXD][MAXD], z[MAXD];
-    for (int k = 0; k < MAXD; ++k) { z[k] = 0.0; for (int j = 0; j < MAXD; ++j) Rm[k][j] = 0.0; }
-    for (int k = 0; k < degree; ++k) {
-        for (int j = 0; j < k; ++j) {
-            double d = 0.0;
-            for (int i = 0; i < ms; ++i) d += c[j][i] * c[k][i];
-            Rm[j][k] = d;
-            for (int i = 0; i < ms; ++i) c[k][i] -= d * c[j][i];
-        }
-        if (REORTH) {
-            for (int j = 0; j < k; ++j) {
-                double d = 0.0;
-                for (int i = 0; i < ms; ++i) d += c[j][i] * c[k][i];
-                Rm[j][k] += d;
-                for (int i = 0; i < ms; ++i) c[k][i] -= d * c[j][i];
-            }
-        }
-        double nn = 0.0;
-        for (int i = 0; i < ms; ++i) nn += c[k][i] * c[k][i];
-        nn = sqrt(nn);
-        Rm[k][k] = nn;
-        const double inv = nn > 0.0 ? 1.0 / nn : 0.0;                     // a dependent column gets coefficient 0 (minimum-norm spirit)
-        double d = 0.0;
-        for (int i = 0; i < ms; ++i) { c[k][i] *= inv; d += c[k][i] * yy[i]; }
-        z[k] = d;
-    }
-    PolyModelT<MAXD> m;
-    for (int k = degree - 1; k >= 0; --k) {                               // back substitution R coef = z
-        double v = z[k];
-        for (int j = k + 1; j < degree; ++j) v -= Rm[k][j] * m.coef[j];
-        m.coef[k] = Rm[k][k] > 0.0 ? v / Rm[k][k] : 0.0;
-    }
-    for (int k = degree; k < MAXD; ++k) m.coef[k] = 0.0;
-    double off = 0.0;
-    for (int k = 0; k < degree; ++k) off += mean[k] * m.coef[k];
-    m.intercept = ymean - off;
-    return m;
-}
-// The same fit with every array in REGISTERS: fit_subset_t's c[MAXD][MAXS] / yy[MAXS] are indexed by run-time loop bounds (ms, degree), which
-// puts them in scratch memory -- 656 bytes per lane in the chain kernel, and the two fits of a window-axis problem (the batch's models, the
-// winner's model again) were 51 % of its time (23 k + 27 k of 98 k cycles, in-kernel clocks, gpurun_out/r5h/pf_timing.log).  Here every loop
-// has a compile-time bound and is unrolled; rows >= ms and columns >= degree hold zeros, which the sums take in as exact no-ops (x + 0 * 0 = x),
-// so the operations that matter happen in fit_subset_t's order: the same bits.
-template <int MAXD, int MAXS>
-__device__ __forceinline__ PolyModelT<MAXD> fit_subset_regs(const double* __restrict__ t, const double* __restrict__ y, const int32_t* __restrict__ idx,
-                                                            const int ms, const int degree, const int ystride)
-{
-    double c[MAXD][MAXS], yy[MAXS], mean[MAXD], ymean = 0.0;
-#pragma unroll
-    for (int k = 0; k < MAXD; ++k) mean[k] = 0.0;
-#pragma unroll
-    for (int i = 0; i < MAXS; ++i) {
-        const bool on = i < ms;
-        const int32_t ix = idx[on ? i : 0];
-        const double ti = t[ix], yv = y[(int64_t)ix * ystride];
-        double tk = ti;
-#pragma unroll
-        for (int k = 0; k < MAXD; ++k) {
-            const bool use = on && k < degree;
-            c[k][i] = use ? tk : 0.0;
-            mean[k] += use ? tk : 0.0;
-            tk *= ti;
-        }
-        yy[i] = on ? yv : 0.0; ymean += on ? yv : 0.0;
-    }
-    const double rn = 1.0 / (double)ms;
-    ymean *= rn;
-#pragma unroll
-    for (int k = 0; k < MAXD; ++k) mean[k] *= rn;
-#pragma unroll
-    for (int i = 0; i < MAXS; ++i) {
-        const bool on = i < ms;
-        yy[i] = on ? yy[i] - ymean : 0.0;
-#pragma unroll
-        for (int k = 0; k < MAXD; ++k) c[k][i] = (on && k < degree) ? c[k][i] - mean[k] : 0.0;
-    }
-    double Rm[MAXD][MAXD], z[MAXD];
-#pragma unroll
-    for (int k = 0; k < MAXD; ++k) {
-        z[k] = 0.0;
-#pragma unroll
-        for (int j = 0; j < MAXD; ++j) Rm[k][j] = 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < MAXD; ++k) {
-        if (k < degree) {                                                 // (uniform over the wave: degree is a launch parameter)
-#pragma unroll
-            for (int j = 0; j < k; ++j) {
-                double d = 0.0;
-#pragma unroll
-                for (int i = 0; i < MAXS; ++i) d += c[j][i] * c[k][i];
-                Rm[j][k] = d;
-#pragma unroll
-                for (int i = 0; i < MAXS; ++i) c[k][i] -= d * c[j][i];
-            }
-            double nn = 0.0;
-#pragma unroll
-            for (int i = 0; i < MAXS; ++i) nn += c[k][i] * c[k][i];
-            nn = sqrt(nn);
-            Rm[k][k] = nn;
-            const double inv = nn > 0.0 ? 1.0 / nn : 0.0;
-            double d = 0.0;
-#pragma unroll
-            for (int i = 0; i < MAXS; ++i) { c[k][i] *= inv; d += c[k][i] * yy[i]; }
-            z[k] = d;
-        }
-    }
-    PolyModelT<MAXD> m;
-#pragma unroll
-    for (int k = MAXD - 1; k >= 0; --k) {
-        double v = z[k];
-#pragma unroll
-        for (int j = k + 1; j < MAXD; ++j) if (j < degree) v -= Rm[k][j] * m.coef[j];
-        m.coef[k] = (k < degree && Rm[k][k] > 0.0) ? v / Rm[k][k] : 0.0;
-    }
-    double off = 0.0;
-#pragma unroll
-    for (int k = 0; k < MAXD; ++k) if (k < degree) off += mean[k] * m.coef[k];
-    m.intercept = ymean - off;
-    return m;
-}
-// REGS: the register form -- for the chain kernel, one wave per SIMD with registers to spare; the thread-per-trial kernels of the fed-sample
-// route run several waves per SIMD and keep the compact scratch form (90 instead of 216 registers) unless GSF_POLY_FIT_REGS says otherwise
-#ifndef GSF_POLY_FIT_REGS
-#define GSF_POLY_FIT_REGS 0
-#endif
-template <bool REGS = (GSF_POLY_FIT_REGS != 0)>
-__device__ __forceinline__ PolyModel fit_subset(const double* __restrict__ t, const double* __restrict__ y, const int32_t* __restrict__ idx,
-                                                int ms, int degree, int ystride = 1)
-{
-    if (!REGS) return fit_subset_t<RP_MAX_DEGREE, RP_MAX_SAMPLES, false>(t, y, idx, ms, degree, ystride);
-    if (ms <= 8) return fit_subset_regs<RP_MAX_DEGREE, 8>(t, y, idx, ms, degree, ystride);
-    return fit_subset_regs<RP_MAX_DEGREE, RP_MAX_SAMPLES>(t, y, idx, ms, degree, ystride);
-}
-
-// sklearn.linear_model._ransac._dynamic_max_trials
-__device__ __forceinline__ double dynamic_max_trials(int n_inliers, int n_samples, int min_samples, double probability)
-{
-    const double EPS = 2.220446049250313e-16;                             // np.spacing(1)
-    const double ratio = (double)n_inliers / (double)n_samples;
-    const double nom = fmax(EPS, 1.0 - probability);
-    const double denom = fmax(EPS, 1.0 - pow(ratio, (double)min_samples));
-    if (nom == 1.0) return 0.0;
-    if (denom == 1.0) return INFINITY;
-    return fabs(ceil(log(nom) / log(denom)));
-}
 
 constexpr int RP_MAX_TRIALS = 1024;
 // THREADS >= max_trials: one thread per trial.  (Trials strided over a fixed block in a loop -- even a template-unrolled one -- made
@@ -224,6 +39,7 @@ __global__ __launch_bounds__(THREADS) void ransac_poly_kernel(const double* __re
     const int64_t i0 = offsets[p], i1 = offsets[p + 1];
     const int n = (int)(i1 - i0);
     const double* tp = t + i0; const double* yp = y + i0;
+    const double t0 = n > 0 ? tp[0] : 0.0;                                // window-local time: every stamp is taken relative to the problem's first row
     const int tau = threadIdx.x;
     PolyModel m;
     m.coef[0] = m.coef[1] = m.coef[2] = 0.0; m.intercept = 0.0;
@@ -234,12 +50,12 @@ __global__ __launch_bounds__(THREADS) void ransac_poly_kernel(const double* __re
         for (int k = 0; k < ms; ++k) in_range = in_range && ix[k] >= 0 && ix[k] < n;
     }
     if (tau < max_trials && n > 0 && in_range) {
-        m = fit_subset(tp, yp, sample_idx + ((int64_t)p * max_trials + tau) * ms, ms, degree);
+        m = fit_subset(tp, yp, sample_idx + ((int64_t)p * max_trials + tau) * ms, ms, degree, 1, t0);
         // |y - y_pred| <= threshold over all rows (ref loss "absolute_error"), then r2_score of the model on its inliers
         int cnt = 0; double sy = 0.0;
 #pragma unroll 8                                                          // rows are wave-uniform scalar loads: keep several in flight
         for (int i = 0; i < n; ++i) {
-            const double res = fabs(yp[i] - poly_predict(m, degree, tp[i]));
+            const double res = fabs(yp[i] - poly_predict(m, degree, tp[i] - t0));
             if (res <= thr) { ++cnt; sy += yp[i]; }
         }
         double score = NAN;                                               // fewer than two samples: sklearn returns nan (and warns)
@@ -248,7 +64,7 @@ __global__ __launch_bounds__(THREADS) void ransac_poly_kernel(const double* __re
             double ss_res = 0.0, ss_tot = 0.0;
 #pragma unroll 8
             for (int i = 0; i < n; ++i) {
-                const double pr = poly_predict(m, degree, tp[i]);
+                const double pr = poly_predict(m, degree, tp[i] - t0);
                 if (fabs(yp[i] - pr) <= thr) { ss_res += (yp[i] - pr) * (yp[i] - pr); ss_tot += (yp[i] - ym) * (yp[i] - ym); }
             }
             score = ss_tot != 0.0 ? 1.0 - ss_res / ss_tot : (ss_res == 0.0 ? 1.0 : 0.0);   // force_finite
@@ -278,14 +94,14 @@ __global__ __launch_bounds__(THREADS) void ransac_poly_kernel(const double* __re
     const int best = sh_best;
     if (best < 0) { for (int i = tau; i < n; i += THREADS) inlier_mask[i0 + i] = 0; return; }
     // every thread re-fits the accepted sample set (6 rows) and marks its share of the rows
-    const PolyModel mb = fit_subset(tp, yp, sample_idx + ((int64_t)p * max_trials + best) * ms, ms, degree);
-    for (int i = tau; i < n; i += THREADS) inlier_mask[i0 + i] = fabs(yp[i] - poly_predict(mb, degree, tp[i])) <= thr ? 1 : 0;
+    const PolyModel mb = fit_subset(tp, yp, sample_idx + ((int64_t)p * max_trials + best) * ms, ms, degree, 1, t0);
+    for (int i = tau; i < n; i += THREADS) inlier_mask[i0 + i] = fabs(yp[i] - poly_predict(mb, degree, tp[i] - t0)) <= thr ? 1 : 0;
 }
 
 // The same problem for configurations beyond the fast kernel's per-thread arrays and one-pass block (polynomial_degree up to 8,
 // min_samples up to 64, any max_trials): trials strided over a 256-thread block, per-trial (inlier count, score) parked in a global
 // slab, the same acceptance walk.  Any CONFIG scikit-learn accepts in practice runs; speed is secondary here.
-constexpr int RPW_MAX_DEGREE = 8, RPW_MAX_SAMPLES = 64, RPW_THREADS = 256;
+constexpr int RPW_THREADS = 256;                                      // (RPW_MAX_DEGREE = 8, RPW_MAX_SAMPLES = 64: gsf_poly_core.hpp)
 __global__ __launch_bounds__(RPW_THREADS) void ransac_poly_wide_kernel(const double* __restrict__ t, const double* __restrict__ y,
                                                                         const int64_t* __restrict__ offsets, const int32_t* __restrict__ sample_idx,
                                                                         int max_trials, int ms, int degree, double thr, double stop_prob,
@@ -298,6 +114,7 @@ __global__ __launch_bounds__(RPW_THREADS) void ransac_poly_wide_kernel(const dou
     const int64_t i0 = offsets[p], i1 = offsets[p + 1];
     const int n = (int)(i1 - i0);
     const double* tp = t + i0; const double* yp = y + i0;
+    const double t0 = n > 0 ? tp[0] : 0.0;                                // window-local time, as in ransac_poly_kernel
     int32_t* cntp = tr_cnt + p * (int64_t)max_trials; double* scp = tr_score + p * (int64_t)max_trials;
     bool bad = false;
     for (int tau = threadIdx.x; tau < max_trials && n > 0; tau += RPW_THREADS) {
@@ -305,10 +122,10 @@ __global__ __launch_bounds__(RPW_THREADS) void ransac_poly_wide_kernel(const dou
         bool in_range = true;
         for (int k = 0; k < ms; ++k) in_range = in_range && ix[k] >= 0 && ix[k] < n;
         if (!in_range) { bad = true; cntp[tau] = -1; scp[tau] = NAN; continue; }
-        const PolyModelT<RPW_MAX_DEGREE> m = fit_subset_t<RPW_MAX_DEGREE, RPW_MAX_SAMPLES, true>(tp, yp, ix, ms, degree);
+        const PolyModelT<RPW_MAX_DEGREE> m = fit_subset_t<RPW_MAX_DEGREE, RPW_MAX_SAMPLES, true>(tp, yp, ix, ms, degree, 1, t0);
         int cnt = 0; double sy = 0.0;
         for (int i = 0; i < n; ++i) {
-            const double res = fabs(yp[i] - poly_predict(m, degree, tp[i]));
+            const double res = fabs(yp[i] - poly_predict(m, degree, tp[i] - t0));
             if (res <= thr) { ++cnt; sy += yp[i]; }
         }
         double score = NAN;
@@ -316,7 +133,7 @@ __global__ __launch_bounds__(RPW_THREADS) void ransac_poly_wide_kernel(const dou
             const double ym = sy / (double)cnt;
             double ss_res = 0.0, ss_tot = 0.0;
             for (int i = 0; i < n; ++i) {
-                const double pr = poly_predict(m, degree, tp[i]);
+                const double pr = poly_predict(m, degree, tp[i] - t0);
                 if (fabs(yp[i] - pr) <= thr) { ss_res += (yp[i] - pr) * (yp[i] - pr); ss_tot += (yp[i] - ym) * (yp[i] - ym); }
             }
             score = ss_tot != 0.0 ? 1.0 - ss_res / ss_tot : (ss_res == 0.0 ? 1.0 : 0.0);
@@ -344,20 +161,21 @@ __global__ __launch_bounds__(RPW_THREADS) void ransac_poly_wide_kernel(const dou
     __syncthreads();
     const int best = sh_best;
     if (best < 0) { for (int i = threadIdx.x; i < n; i += RPW_THREADS) inlier_mask[i0 + i] = 0; return; }
-    const PolyModelT<RPW_MAX_DEGREE> mb = fit_subset_t<RPW_MAX_DEGREE, RPW_MAX_SAMPLES, true>(tp, yp, sample_idx + ((int64_t)p * max_trials + best) * ms, ms, degree);
-    for (int i = threadIdx.x; i < n; i += RPW_THREADS) inlier_mask[i0 + i] = fabs(yp[i] - poly_predict(mb, degree, tp[i])) <= thr ? 1 : 0;
+    const PolyModelT<RPW_MAX_DEGREE> mb = fit_subset_t<RPW_MAX_DEGREE, RPW_MAX_SAMPLES, true>(tp, yp, sample_idx + ((int64_t)p * max_trials + best) * ms, ms, degree, 1, t0);
+    for (int i = threadIdx.x; i < n; i += RPW_THREADS) inlier_mask[i0 + i] = fabs(yp[i] - poly_predict(mb, degree, tp[i] - t0)) <= thr ? 1 : 0;
 }
 
 // score of one fed trial (steps 1 of the header comment) for rows with a stride (AoS position rows)
 __device__ __forceinline__ void score_trial(const double* __restrict__ tp, const double* __restrict__ yp, int ystride, int n, const int32_t* idx, int ms,
                                             int degree, double thr, int& cnt_out, double& score_out)
 {
-    const PolyModel m = fit_subset(tp, yp, idx, ms, degree, ystride);
+    const double t0 = n > 0 ? tp[0] : 0.0;                                // window-local time
+    const PolyModel m = fit_subset(tp, yp, idx, ms, degree, ystride, t0);
     int cnt = 0; double sy = 0.0;
 #pragma unroll 4
     for (int i = 0; i < n; ++i) {
         const double yi = yp[(int64_t)i * ystride];
-        const double res = fabs(yi - poly_predict(m, degree, tp[i]));
+        const double res = fabs(yi - poly_predict(m, degree, tp[i] - t0));
         if (res <= thr) { ++cnt; sy += yi; }
     }
     double score = NAN;
@@ -367,7 +185,7 @@ __device__ __forceinline__ void score_trial(const double* __restrict__ tp, const
 #pragma unroll 4
         for (int i = 0; i < n; ++i) {
             const double yi = yp[(int64_t)i * ystride];
-            const double pr = poly_predict(m, degree, tp[i]);
+            const double pr = poly_predict(m, degree, tp[i] - t0);
             if (fabs(yi - pr) <= thr) { ss_res += (yi - pr) * (yi - pr); ss_tot += (yi - ym) * (yi - ym); }
         }
         score = ss_tot != 0.0 ? 1.0 - ss_res / ss_tot : (ss_res == 0.0 ? 1.0 : 0.0);
@@ -465,6 +283,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
         const long long pf_w0 = clock64();
 #endif
         const double* tp = t + r_base + r0;
+        const double t0 = tp[0];                                          // window-local time: the window's first stamp comes off every stamp where it is loaded (n >= ms >= 1 here)
         // window mask lives in keep[] itself as bit 1 (AND over axes), folded into bit 0 (OR over windows) when the window succeeds
         for (int i = lane; i < n; i += 64) kp[r0 + i] |= 2;
         // the window's rows in registers when they fit (up to 64 x PF_TILE = 512 rows; lane l holds rows l, l + 64, ...): the stamps once per
@@ -477,7 +296,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
 #pragma unroll
             for (int k = 0; k < PF_TILE; ++k) {
                 const int i = k * 64 + lane, ic = in_regs ? (i < n ? i : n - 1) : 0;
-                tv[k] = tp[ic]; y3[0][k] = p3[(int64_t)ic * 3]; y3[1][k] = p3[(int64_t)ic * 3 + 1]; y3[2][k] = p3[(int64_t)ic * 3 + 2]; yv[k] = 0.0;
+                tv[k] = tp[ic] - t0; y3[0][k] = p3[(int64_t)ic * 3]; y3[1][k] = p3[(int64_t)ic * 3 + 1]; y3[2][k] = p3[(int64_t)ic * 3 + 2]; yv[k] = 0.0;
             }
         }
         // ---- speculative pass (round 5).  On a clean window every axis's RANSACRegressor stops after its FIRST trial (the sample's model
@@ -500,7 +319,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
             draw(na, sh_idx, sh_end);
             PF_ADD(12);
             const double* y0 = pos + (r_base + r0) * 3 + ax;
-            if (lane < na) sh_model[lane] = fit_subset<true>(tp, y0 + lane, sh_idx + (size_t)lane * ms, ms, degree, 3);
+            if (lane < na) sh_model[lane] = fit_subset<true>(tp, y0 + lane, sh_idx + (size_t)lane * ms, ms, degree, 3, t0);
             __syncthreads();
             PF_ADD(13);
             int cnt3[3] = { 0, 0, 0 };                                    // by ABSOLUTE axis (constant register indices)
@@ -586,7 +405,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
                 // models: a lane per trial (at most 32 of them work); scores: the whole wave over the ROWS of one trial at a time -- a batch
                 // is 4-64 trials of ~150 rows, and a lane walking all rows of its trial alone was 44 of a window-axis's 85 us
                 for (int tau = lane; tau < nb; tau += 64) {
-                    sh_model[tau] = fit_subset<true>(tp, yp, sh_idx + (size_t)(drawn + tau) * ms, ms, degree, 3);
+                    sh_model[tau] = fit_subset<true>(tp, yp, sh_idx + (size_t)(drawn + tau) * ms, ms, degree, 3, t0);
                     sh_end[drawn + tau] += raw_base;                          // outputs consumed since the window-axis start
                 }
                 __syncthreads();
@@ -611,7 +430,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
                         for (int i0 = 0; i0 < n; i0 += 64) {
                             const int i = i0 + lane;
                             const double yi = i < n ? yp[(int64_t)i * 3] : 0.0;
-                            const bool in = i < n && fabs(yi - poly_predict(m, degree, tp[i < n ? i : 0])) <= thr;
+                            const bool in = i < n && fabs(yi - poly_predict(m, degree, tp[i < n ? i : 0] - t0)) <= thr;
                             cnt += __popcll(__ballot(in));
                             sy += in ? yi : 0.0;
                         }
@@ -634,7 +453,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
                             for (int i0 = 0; i0 < n; i0 += 64) {
                                 const int i = i0 + lane;
                                 const double yi = i < n ? yp[(int64_t)i * 3] : 0.0;
-                                const double pr = poly_predict(m, degree, tp[i < n ? i : 0]);
+                                const double pr = poly_predict(m, degree, tp[i < n ? i : 0] - t0);
                                 const bool in = i < n && fabs(yi - pr) <= thr;
                                 ss_res += in ? (yi - pr) * (yi - pr) : 0.0;
                                 ss_tot += in ? (yi - ym) * (yi - ym) : 0.0;
@@ -675,7 +494,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
             // the winner's model: still in LDS when the winner belongs to the batch scored last (the usual case: the first batch decides), else fitted
             // again -- same function, same rows, same bits either way
             const int batch0 = drawn - last_nb;
-            const PolyModel mb = best >= batch0 ? sh_model[best - batch0] : fit_subset<true>(tp, yp, sh_idx + (size_t)best * ms, ms, degree, 3);
+            const PolyModel mb = best >= batch0 ? sh_model[best - batch0] : fit_subset<true>(tp, yp, sh_idx + (size_t)best * ms, ms, degree, 3, t0);
             if (in_regs) {
 #pragma unroll
                 for (int k = 0; k < PF_TILE; ++k) {
@@ -684,7 +503,7 @@ __global__ __launch_bounds__(64) void gps_prefilter_chain_kernel(const double* _
                 }
             } else {
                 for (int i = lane; i < n; i += 64) {
-                    const bool in = fabs(yp[(int64_t)i * 3] - poly_predict(mb, degree, tp[i])) <= thr;
+                    const bool in = fabs(yp[(int64_t)i * 3] - poly_predict(mb, degree, tp[i] - t0)) <= thr;
                     if (!in) kp[r0 + i] &= (uint8_t)~2u;
                 }
             }

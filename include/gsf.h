@@ -292,7 +292,21 @@ GSF_API int gsf_geodetic_to_enu_batch(gsf_ctx *ctx, const double *lat_deg, const
    n_inliers, status (bit 0: no consensus set -- the reference's ValueError; bit 1: a fed sample set named a row outside the problem
    and was skipped).  degree 1..8, min_samples <= 64, max_trials <= 2^20; inside degree <= 3, min_samples <= 16, max_trials <= 1024
    one thread scores one trial in one pass, beyond that a slower kernel strides the trials (per-trial results in the context's
-   workspace). */
+   workspace).
+   DOMAIN OF THE FIT (every pre-filter entry: this one, gsf_gps_prefilter_chain*, gsf_gps_prefilter_auto_dev, the whole-run entries).
+   Fit and prediction run in WINDOW-LOCAL TIME: the stamp of the first row of the problem (here) or of the window (the chain) is
+   subtracted from every stamp where it is loaded, so the outputs do not depend on where the clock's zero lies -- stamps in seconds,
+   milliseconds or microseconds, track-relative or Unix.  That first stamp must be FINITE: a NaN or infinite one makes every local stamp,
+   every prediction and so every row of the problem / window an outlier (status bit 0 here, win_status 1 in the chain), where a non-finite
+   stamp on any other row spoils only the samples that hold it and that row's own residual; the entries do not check stamps, and the
+   reference's loader hands on the stamps of the file as they are.  A prediction at stamp t is within C x b(t) of the least-squares polynomial of the
+   stored rows, b(t) = u kappa Lambda(t) max|y_i - ybar| + 4 u max|y| (u = 2^-53; kappa: condition of the sample's centred, unit-norm power
+   columns in local time; Lambda(t): sum of the prediction's |weights| on the sample's targets; C = 5.44, measured).
+   The reference's float64 solve on RAW stamps is not: at Unix magnitude and degree 2 it is tens of metres from that polynomial, so on
+   such logs the entries follow the exact fit and the reference does not.  RANK RULE: a power column whose norm after the Gram-Schmidt
+   sweep is at most 4 x 2^-52 x min_samples x its norm as loaded counts as dependent and gets coefficient 0 -- a sample with m <= degree
+   distinct stamps (a receiver that repeats stamps) gets the least-squares polynomial of degree m - 1; scikit-learn returns the
+   minimum-norm solution in its own basis (raw t, t^2, ..), which agrees at the sample's stamps and differs away from them. */
 GSF_API int gsf_ransac_poly_batch_dev(gsf_ctx *ctx, const double *t, const double *y, const int64_t *offsets, int64_t P,
                                       const int32_t *sample_idx, int32_t max_trials, int32_t min_samples, int32_t degree,
                                       double residual_threshold, double stop_probability, uint8_t *inlier_mask, int32_t *n_trials,

@@ -375,7 +375,10 @@ def _ransac_poly_fit(t, y, degree, min_samples, thr, max_trials, stop_probabilit
     from sklearn.utils.random import sample_without_replacement
     rs = np.random.mtrand._rand
     n = len(t)
-    X = np.vander(t, degree + 1, increasing=True)                       # [1, t, .., t^d]
+    # window-local time ("Domain of the pre-filter's fit"): the reference hands PolynomialFeatures the raw stamps, and at Unix
+    # magnitude its float64 solve is tens of metres from the least-squares polynomial of the rows it was given; the product and this
+    # restatement follow the exact fit instead, which does not depend on where the clock's zero lies.  (First stamp 0: the same numbers.)
+    X = np.vander(t - t[0], degree + 1, increasing=True) if n else np.vander(t, degree + 1, increasing=True)   # [1, t, .., t^d]
     eps = np.spacing(1)
     best_mask, best_n, best_score, trials, max_tr = None, 1, -np.inf, 0, max_trials
     while trials < max_tr:
