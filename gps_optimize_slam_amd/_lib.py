@@ -83,6 +83,13 @@ class LocalConfig(C.Structure):
                 ("ratio_max", C.c_double)]
 
 
+class LeverConfig(C.Structure):
+    """gsf_lever_config (include/gsf.h): priors, thresholds, rounds and switches of gsf_lever_fit_dev."""
+    _fields_ = [("sigma_fix", C.c_double), ("sigma_prior", C.c_double * 3), ("sigma_rot", C.c_double), ("ratio_max", C.c_double),
+                ("pivot_min", C.c_double), ("weak_ratio", C.c_double), ("conv_tol", C.c_double), ("min_rows", C.c_int32), ("iters", C.c_int32),
+                ("fit_scale", C.c_int32), ("fit_rotation", C.c_int32)]
+
+
 RUN_GPS_EMPTY, RUN_GPS_FEW, RUN_PREFILTER_UNHANDLED, RUN_SIM3_FAILED, RUN_BAD_QUAT = 1, 2, 4, 8, 16      # run_status bits of gsf_run_fusion_batch_dev
 RUN_GT_EMPTY, RUN_GT_FEW, RUN_GT_UNHANDLED, RUN_SLAM_EMPTY = 32, 64, 128, 256                          # ... and of gsf_run_fusion_ragged_dev only
 SIM3_FLAG_SATURATED = 256
@@ -95,6 +102,10 @@ LOC_SCALE, LOC_SIM3, LOC_KMAX = 0, 1, 4096                      # modes of gsf_s
 LOC_EMPTY, LOC_UNSORTED, LOC_TOO_MANY, LOC_SKIPPED = 1, 2, 4, 8   # ... its track_status bits
 KNOT_FEW, KNOT_VAR0, KNOT_SCALE, KNOT_ROT_FALLBACK = 1, 2, 4, 8   # ... its knot_flags bits (the first three make a knot invalid)
 LP_BRIDGED, LP_HELD, LP_GLOBAL, LP_BAD_QUAT, LP_TRACK = 1, 2, 4, 8, 16      # pose_flags bits of gsf_sim3_local_apply_dev
+LEVER_FEW, LEVER_VAR0, LEVER_SINGULAR, LEVER_SCALE, LEVER_WEAK_X, LEVER_WEAK_Y, LEVER_WEAK_Z = 1, 2, 4, 8, 16, 32, 64      # flags bits of gsf_lever_fit_dev
+LEVER_NOT_CONVERGED, LEVER_TRACK = 128, 256                      # ... (the first four and LEVER_TRACK: the track keeps its starting values)
+LEVER_KEPT = LEVER_FEW | LEVER_VAR0 | LEVER_SINGULAR | LEVER_SCALE | LEVER_TRACK
+LVP_BAD_QUAT = 1                                                # pose_flags bit of gsf_lever_apply_dev
 STREAM_F64, STREAM_I64, STREAM_LAYOUT_VERSION = 22, 6, 1      # state sizes per track and layout version of the streaming fusion (gsf_stream_*)
 STREAM_FULL, STREAM_BAD_STATE = 256, 512                        # ... and its status bits, beside the ST_* ones
 CLK_NONE, CLK_AT_EDGE, CLK_FLAT = 1, 2, 4                       # clk_status bits of gsf_clock_offset_search_dev
@@ -188,6 +199,8 @@ SIGNATURES = {
     "gsf_innovation_gate_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _i32, _f64, _i32] + [_vp] * 4),
     "gsf_sim3_local_fit_dev": (C.c_int, [_vp] * 6 + [_i64, _vp, _vp, _vp, C.POINTER(LocalConfig), _i32] + [_vp] * 8),
     "gsf_sim3_local_apply_dev": (C.c_int, [_vp] * 5 + [_i64, _vp, _vp, _vp, _f64, _i32] + [_vp] * 10),
+    "gsf_lever_fit_dev": (C.c_int, [_vp] * 6 + [_i64] + [_vp] * 5 + [C.POINTER(LeverConfig)] + [_vp] * 11),
+    "gsf_lever_apply_dev": (C.c_int, [_vp] * 4 + [_i64, _vp, _vp, _f64, _vp, _vp]),
     "gsf_stream_open_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 5),
     "gsf_stream_append_dev": (C.c_int, [_vp, C.POINTER(EkfConfig), _i64, _i64] + [_vp] * 18),
     "gsf_stream_gather_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 9),

@@ -1682,6 +1682,151 @@ def refuse_local(rb, r, la, want_cov=False, skip_seconds=5.0, config=None):
                      err_stats3=torch.stack([x[0] for x in rows]), errors3=torch.stack([x[1] for x in rows]))
 
 
+# ---------------------------------------------------------------------------- antenna lever arm (gsf_lever_fit_dev / gsf_lever_apply_dev)
+def _lever_config(sigma_fix, sigma_prior, sigma_rot, fit_scale, fit_rotation, iters, min_rows, ratio_max, pivot_min, weak_ratio, conv_tol):
+    """the arguments of the lever-arm fit as a gsf_lever_config, checked as the entry checks them (these errors need no device)"""
+    c = _lib.LeverConfig()
+    sp = tuple(float(v) for v in ((sigma_prior,) * 3 if isinstance(sigma_prior, (int, float)) else sigma_prior))
+    if len(sp) != 3:
+        raise ValueError("lever arm: sigma_prior must be one number or three")
+    c.sigma_fix, c.sigma_rot, c.ratio_max, c.pivot_min = float(sigma_fix), float(sigma_rot), float(ratio_max), float(pivot_min)
+    c.sigma_prior[0], c.sigma_prior[1], c.sigma_prior[2] = sp
+    c.weak_ratio, c.conv_tol, c.min_rows, c.iters = float(weak_ratio), float(conv_tol), int(min_rows), int(iters)
+    c.fit_scale, c.fit_rotation = int(bool(fit_scale)), int(bool(fit_rotation))
+    if not (0.0 < c.sigma_fix < float("inf")):
+        raise ValueError("lever arm: sigma_fix must be positive and finite")
+    if not (all(v > 0.0 for v in sp) and c.sigma_rot > 0.0):
+        raise ValueError("lever arm: sigma_prior and sigma_rot must be positive (inf: no prior)")
+    if not 1 <= c.iters <= 8:
+        raise ValueError("lever arm: iters must be in [1, 8]")
+    if c.min_rows < 1:
+        raise ValueError("lever arm: min_rows must be >= 1")
+    if not (c.ratio_max >= 1.0 and c.pivot_min >= 0.0 and c.weak_ratio >= 0.0 and c.conv_tol >= 0.0):
+        raise ValueError("lever arm: ratio_max must be >= 1, pivot_min, weak_ratio and conv_tol >= 0")
+    return c
+
+
+class LeverArm:
+    """Result of lever_fit_ragged for B tracks (definitions: include/gsf.h, gsf_lever_fit_dev).  Device tensors: l (B,3) = the antenna offset
+    in the sensor frame, l_cov (B,3,3), R (B,9), t (B,3), s (B,) = the Sim3 fitted with it, n_rows, n_bad_quat, flags (B,) int32
+    (_lib.LEVER_* bits), rms_before, rms_after, last_step (B,); sigma_prior (3 floats) and valid (P,) = the mask of the fit.  A track with
+    any of _lib.LEVER_KEPT carries its starting values."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def sigma(self):
+        """(B,3): the square roots of the diagonal of l_cov"""
+        return torch.sqrt(torch.diagonal(self.l_cov, dim1=1, dim2=2))
+
+    @property
+    def observed(self):
+        """(B,3) bool: the axis is not flagged WEAK (the data, not the prior, decided it)"""
+        bits = torch.tensor([_lib.LEVER_WEAK_X, _lib.LEVER_WEAK_Y, _lib.LEVER_WEAK_Z], dtype=torch.int32, device=self.flags.device)
+        return (self.flags[:, None] & bits[None, :]) == 0
+
+    @property
+    def fitted(self):
+        """(B,) bool: the track carries a fit, not its starting values"""
+        return (self.flags & _lib.LEVER_KEPT) == 0
+
+    def table(self):
+        """one line per track, on the host: l, sigma, the observed axes, rows, RMS before -> after, flags"""
+        l, sg, ob = self.l.cpu().numpy(), self.sigma.cpu().numpy(), self.observed.cpu().numpy()
+        n, fl = self.n_rows.cpu().numpy(), self.flags.cpu().numpy()
+        rb_, ra = self.rms_before.cpu().numpy(), self.rms_after.cpu().numpy()
+        lines = ["track      l_x      l_y      l_z   sigma_x  sigma_y  sigma_z  observed  rows  rms_before  rms_after  flags"]
+        for b in range(len(n)):
+            axes = "".join(a if o else "-" for a, o in zip("xyz", ob[b]))
+            lines.append(f"{b:5d} {l[b, 0]:8.3f} {l[b, 1]:8.3f} {l[b, 2]:8.3f}  {sg[b, 0]:8.3f} {sg[b, 1]:8.3f} {sg[b, 2]:8.3f}  {axes:>8s} {n[b]:5d}  {rb_[b]:10.4f} {ra[b]:10.4f}  {fl[b]:5d}")
+        return "\n".join(lines)
+
+
+def lever_apply_ragged(quat, xyz, offsets, R, l, sign=-1):
+    """xyz + sign R (M(quat) l) per pose (gsf_lever_apply_dev): quat (P,4), xyz (P,3), offsets (B+1,) int64, R (B,9), l (B,3).  sign = -1
+    moves fixes from the antenna to the camera, +1 from the camera to the antenna; pass the identity as R when quat is already a world
+    quaternion (a fused one).  A NaN fix stays NaN; a quaternion that cannot be normalised gives a NaN row and _lib.LVP_BAD_QUAT.  One
+    launch on torch's current stream.  Returns xyz_out (P,3), pose_flags (P,) int32."""
+    if sign not in (-1, 1):
+        raise ValueError("lever_apply_ragged: sign must be -1 (antenna -> camera) or +1 (camera -> antenna)")
+    B = _offsets_chk(offsets)
+    P = int(xyz.shape[0]) if xyz.dim() == 2 else -1
+    _chk(quat, torch.float64, (P, 4), "quat"); _chk(xyz, torch.float64, (P, 3), "xyz")
+    _chk(R, torch.float64, (B, 9), "R"); _chk(l, torch.float64, (B, 3), "l")
+    out = torch.empty_like(xyz)
+    fl = torch.empty((P,), dtype=torch.int32, device=xyz.device)
+    check(_lib.load().gsf_lever_apply_dev(context().handle, _p(quat), _p(xyz), _p(offsets), B, _p(R), _p(l), float(sign), _p(out), _p(fl)))
+    return out, fl
+
+
+def lever_fit_ragged(pos, quat, gps, valid, offsets, R, t, s, l0=None, sigma_fix=0.5, sigma_prior=(1.0, 1.0, 1.0), sigma_rot=0.05, fit_scale=True,
+                     fit_rotation=True, iters=4, min_rows=8, ratio_max=2.0, pivot_min=1e-10, weak_ratio=0.5, conv_tol=1e-6, run_status=None):
+    """The antenna lever arm of B ragged tracks on torch's current stream (gsf_lever_fit_dev; definitions in include/gsf.h): a joint
+    Gauss-Newton over scale, translation, lever arm and a rotation increment from the starting values R (B,9), t (B,3), s (B,) -- each
+    track's global Sim3 -- and l0 (B,3) (None: zero), `iters` rounds.  pos (P,3), quat (P,4): the original SLAM tracks; gps (P,3) / valid
+    (P,) uint8 as the time alignment returns them.  sigma_fix: the noise of a fix; sigma_prior (one number or three, metres; inf: none): the
+    prior of l about l0 per sensor axis; sigma_rot (radians; inf: none): the prior of the accumulated rotation.  run_status (B,) int32:
+    tracks with a non-zero word are not read (_lib.LEVER_TRACK).  Returns a LeverArm."""
+    cfg = _lever_config(sigma_fix, sigma_prior, sigma_rot, fit_scale, fit_rotation, iters, min_rows, ratio_max, pivot_min, weak_ratio, conv_tol)
+    B = _offsets_chk(offsets)
+    P = int(pos.shape[0]) if pos.dim() == 2 else -1
+    _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat"); _chk(gps, torch.float64, (P, 3), "gps")
+    _chk(valid, torch.uint8, (P,), "valid")
+    _chk(R, torch.float64, (B, 9), "R"); _chk(t, torch.float64, (B, 3), "t"); _chk(s, torch.float64, (B,), "s")
+    dev = pos.device
+    f = dict(dtype=torch.float64, device=dev)
+    i = dict(dtype=torch.int32, device=dev)
+    if l0 is None:
+        l0 = torch.zeros((B, 3), **f)
+    _chk(l0, torch.float64, (B, 3), "l0")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    lv = LeverArm(R=torch.empty((B, 9), **f), t=torch.empty((B, 3), **f), s=torch.empty((B,), **f), l=torch.empty((B, 3), **f),
+                  l_cov=torch.empty((B, 3, 3), **f), n_rows=torch.empty((B,), **i), n_bad_quat=torch.empty((B,), **i),
+                  rms_before=torch.empty((B,), **f), rms_after=torch.empty((B,), **f), last_step=torch.empty((B,), **f),
+                  flags=torch.empty((B,), **i), sigma_prior=tuple(cfg.sigma_prior), sigma_fix=cfg.sigma_fix, valid=valid, l0=l0)
+    check(_lib.load().gsf_lever_fit_dev(context().handle, _p(pos), _p(quat), _p(gps), _p(valid), _p(offsets), B, _p(R), _p(t), _p(s), _p(l0),
+                                        _p(run_status), C.byref(cfg), _p(lv.R), _p(lv.t), _p(lv.s), _p(lv.l), _p(lv.l_cov), _p(lv.n_rows),
+                                        _p(lv.n_bad_quat), _p(lv.rms_before), _p(lv.rms_after), _p(lv.last_step), _p(lv.flags)))
+    return lv
+
+
+def lever_fit_fused(rb, r, valid=None, **kw):
+    """lever_fit_ragged on the result r of run_fusion_ragged / run_fusion_batch for the batch rb: the run's global Sim3, the aligned fixes,
+    their mask and run_status are r's (valid=: another mask over the same rows, e.g. g.valid(k) of gate_fused, as at smooth_fused)."""
+    v = (r.valid.reshape(-1) if valid is None else valid).contiguous()
+    return lever_fit_ragged(rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4), r.aligned.reshape(-1, 3), v, rb.slam_offsets, r.R, r.t, r.s,
+                            run_status=r.run_status, **kw)
+
+
+def refuse_lever(rb, r, lv, want_cov=False, skip_seconds=5.0, config=None):
+    """Fuse again with the fixes moved from the antenna to the camera under the lever arm lv (lever_fit_fused): lever_apply_ragged on
+    r.aligned under lv.R / lv.l, the initial pose of every track = row 0 of apply_sim3_batch under lv.R / lv.t / lv.s, the existing
+    ekf_fuse_ragged on the ORIGINAL SLAM poses -- no fuse kernel knows of the lever arm --, optionally ekf_covariance_ragged, and step 6's
+    nearest-fix error rows for the raw SLAM track, the Sim3-aligned one under lv and the fused one, all against the de-levered fixes.
+    A pose whose quaternion cannot be normalised has a NaN fix and is fused as a pose without one.  Returns a RunResult in the shape of
+    refuse_local's -- pos, quat, status, valid, err_stats / errors of the fused track, cov, init_pos, init_quat, err_stats3 (3,B,4) /
+    errors3 (3,P) -- plus gps_camera (P,3), the de-levered fixes, and lever_flags (P,) int32."""
+    ts, pos, quat = rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4)
+    aligned, valid, offsets = r.aligned.reshape(-1, 3).contiguous(), lv.valid, rb.slam_offsets
+    B, P = _offsets_chk(offsets), int(ts.numel())
+    dev = ts.device
+    gc, lf = lever_apply_ragged(quat, aligned, offsets, lv.R, lv.l, sign=-1)
+    sp, _, _ = apply_sim3_batch(pos, quat, offsets, lv.R, lv.t, lv.s)
+    if P:
+        first = torch.clamp(offsets[:-1], max=P - 1)                      # (an empty track's row is never read)
+        one = torch.arange(B + 1, dtype=torch.int64, device=dev)
+        ip, iq, _ = apply_sim3_batch(pos[first].contiguous(), quat[first].contiguous(), one, lv.R, lv.t, lv.s)
+    else:
+        ip, iq = torch.zeros((B, 3), dtype=torch.float64, device=dev), torch.zeros((B, 4), dtype=torch.float64, device=dev)
+    po, qo, st = ekf_fuse_ragged(ts, pos, quat, gc, valid, offsets, ip, iq, config=config)
+    cov = ekf_covariance_ragged(ts, quat, gc, valid, offsets, config=config, run_status=r.run_status) if want_cov else None
+    rows = _step6_rows(ts, offsets, (pos, sp, po), gc, valid, skip_seconds)
+    return RunResult(pos=po, quat=qo, status=st, valid=valid, err_stats=rows[2][0], errors=rows[2][1], cov=cov, init_pos=ip, init_quat=iq,
+                     err_stats3=torch.stack([x[0] for x in rows]), errors3=torch.stack([x[1] for x in rows]), gps_camera=gc, lever_flags=lf)
+
+
 class PoseQuery:
     """The fused track at query stamps (query_poses_ragged), flat over the M queries: pos (M,3), quat (M,4), flags (M,) uint8 of _lib.Q_* bits,
     index (M,) int32 = the bracket's first pose relative to its track (-1: none), pose_flags (M,) uint8 or None = the _lib.POSE_* bits of

@@ -760,4 +760,38 @@ int gsf_sim3_local_apply_dev(gsf_ctx* ctx, const double* ts, const double* pos, 
                               pos_out, quat_out, scale_at, pose_flags);
 }
 
+// antenna lever arm: device forms only (include/gsf.h; the Python binding uploads host arrays itself)
+int gsf_lever_fit_dev(gsf_ctx* ctx, const double* pos, const double* quat, const double* gps, const uint8_t* valid, const int64_t* offsets,
+                      int64_t B, const double* R, const double* t, const double* s, const double* l0, const int32_t* run_status,
+                      const gsf_lever_config* cfg, double* R_out, double* t_out, double* s_out, double* l_out, double* l_cov, int32_t* n_rows,
+                      int32_t* n_bad_quat, double* rms_before, double* rms_after, double* last_step, int32_t* flags)
+{
+    GSF_REQUIRE(ctx && cfg && offsets, "ctx/cfg/offsets is NULL");
+    GSF_REQUIRE(B >= 0 && B <= 0x7fffffff, "bad B");
+    GSF_REQUIRE(cfg->iters >= 1 && cfg->iters <= 8, "iters must be in [1, 8]");
+    GSF_REQUIRE(cfg->min_rows >= 1, "min_rows must be >= 1");
+    GSF_REQUIRE(cfg->sigma_fix > 0.0 && cfg->sigma_fix < INFINITY, "sigma_fix must be positive and finite");
+    GSF_REQUIRE(cfg->sigma_prior[0] > 0.0 && cfg->sigma_prior[1] > 0.0 && cfg->sigma_prior[2] > 0.0 && cfg->sigma_rot > 0.0,
+                "sigma_prior and sigma_rot must be positive (infinite: no prior)");
+    GSF_REQUIRE(cfg->ratio_max >= 1.0 && cfg->pivot_min >= 0.0 && cfg->weak_ratio >= 0.0 && cfg->conv_tol >= 0.0,
+                "ratio_max must be >= 1, pivot_min, weak_ratio and conv_tol >= 0");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(pos && quat && gps && valid && R && t && s && l0, "NULL input array");
+    GSF_REQUIRE(R_out && t_out && s_out && l_out && l_cov && n_rows && n_bad_quat && rms_before && rms_after && last_step && flags, "NULL output array");
+    return launch_lever_fit(ctx, pos, quat, gps, valid, offsets, B, R, t, s, l0, run_status, cfg, R_out, t_out, s_out, l_out, l_cov, n_rows,
+                            n_bad_quat, rms_before, rms_after, last_step, flags);
+}
+
+int gsf_lever_apply_dev(gsf_ctx* ctx, const double* quat, const double* xyz, const int64_t* offsets, int64_t B, const double* R, const double* l,
+                        double sign, double* xyz_out, int32_t* pose_flags)
+{
+    GSF_REQUIRE(ctx && offsets, "ctx/offsets is NULL");
+    GSF_REQUIRE(B >= 0 && B <= 0x7fffffff, "bad B");
+    GSF_REQUIRE(sign == 1.0 || sign == -1.0, "sign must be +1 or -1");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(quat && xyz && R && l, "NULL input array");
+    GSF_REQUIRE(xyz_out && pose_flags, "NULL output array");
+    return launch_lever_apply(ctx, quat, xyz, offsets, B, R, l, sign, xyz_out, pose_flags);
+}
+
 }  // extern "C"

@@ -147,6 +147,14 @@ int launch_local_apply(gsf_ctx* ctx, const double* ts, const double* pos, const 
                        const double* knot_s, const int32_t* knot_flags, const int32_t* n_knots, const int32_t* track_status, double* pos_out,
                        double* quat_out, double* scale_at, int32_t* pose_flags);
 
+// antenna lever arm (gsf_lever.hip): the bodies of gsf_lever_fit_dev / gsf_lever_apply_dev, arguments checked by the caller
+int launch_lever_fit(gsf_ctx* ctx, const double* pos, const double* quat, const double* gps, const uint8_t* valid, const int64_t* offsets, int64_t B,
+                     const double* R, const double* t, const double* s, const double* l0, const int32_t* run_status, const gsf_lever_config* cfg,
+                     double* R_out, double* t_out, double* s_out, double* l_out, double* l_cov, int32_t* n_rows, int32_t* n_bad_quat,
+                     double* rms_before, double* rms_after, double* last_step, int32_t* flags);
+int launch_lever_apply(gsf_ctx* ctx, const double* quat, const double* xyz, const int64_t* offsets, int64_t B, const double* R, const double* l,
+                       double sign, double* xyz_out, int32_t* pose_flags);
+
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
 int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);
 int launch_gps_prefilter_auto(gsf_ctx* ctx, const double* t, const double* pos, const int64_t* offsets, const int32_t* counts, int64_t B,

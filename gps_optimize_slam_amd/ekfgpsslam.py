@@ -652,6 +652,47 @@ def align_trajectory_local(slam_data, aligned_gps, valid_mask, R, t, s, spacing=
             "knot_rms": h(la.knot_rms[0, :K]), "knot_flags": h(la.knot_flags[0, :K]), "knot_valid": ok}
 
 
+def estimate_lever_arm(slam_data, aligned_gps, valid_mask, R, t, s, l0=None, sigma_fix=0.5, sigma_prior=(1.0, 1.0, 1.0), sigma_rot=0.05,
+                       fit_scale=True, fit_rotation=True, iters=4, min_rows=8, ratio_max=2.0):
+    """The GNSS antenna's offset from the camera for one track on NumPy arrays (batch.lever_fit_ragged; definitions in include/gsf.h,
+    gsf_lever_fit_dev): a fix measures s R pos + t + R M(q) l, and l (sensor frame, metres) is fitted jointly with s, t and a rotation
+    increment from the track's global Sim3 R, t, s (compute_sim3_transform_robust) on the usable rows of aligned_gps / valid_mask (what
+    dynamic_time_alignment returned).  Returns a dict of host values: 'l' (3,), 'l_cov' (3,3), 'sigma' (3,), 'observed' (3,) bool (an axis the
+    data did not observe stays at its prior: a ground vehicle never observes the one along its yaw axis), 'R' (3,3), 't' (3,), 's', 'n_rows',
+    'n_bad_quat', 'rms_before', 'rms_after', 'last_step', 'flags' (LEVER_* bits of _lib), 'fitted' (False: the starting values came back)."""
+    import torch
+    from . import batch as gb
+    gb._lever_config(sigma_fix, sigma_prior, sigma_rot, fit_scale, fit_rotation, iters, min_rows, ratio_max, 1e-10, 0.5, 1e-6)   # (argument errors need no device)
+    n = len(slam_data["positions"])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.array(a, dtype=dt, order="C").reshape(shape)).to(dev)     # (a copy: the caller's arrays may be read-only)
+    lv = gb.lever_fit_ragged(up(slam_data["positions"], (n, 3)), up(slam_data["quaternions"], (n, 4)), up(aligned_gps, (n, 3)),
+                             up(np.asarray(valid_mask) != 0, (n,), np.uint8), torch.tensor([0, n], dtype=torch.int64, device=dev), up(R, (1, 9)),
+                             up(t, (1, 3)), up(s, (1,)), l0=None if l0 is None else up(l0, (1, 3)), sigma_fix=sigma_fix, sigma_prior=sigma_prior,
+                             sigma_rot=sigma_rot, fit_scale=fit_scale, fit_rotation=fit_rotation, iters=iters, min_rows=min_rows, ratio_max=ratio_max)
+    h = lambda x: x.cpu().numpy()
+    return {"l": h(lv.l[0]), "l_cov": h(lv.l_cov[0]), "sigma": h(lv.sigma[0]), "observed": h(lv.observed[0]), "R": h(lv.R[0]).reshape(3, 3), "t": h(lv.t[0]),
+            "s": float(lv.s[0].item()), "n_rows": int(lv.n_rows[0].item()), "n_bad_quat": int(lv.n_bad_quat[0].item()),
+            "rms_before": float(lv.rms_before[0].item()), "rms_after": float(lv.rms_after[0].item()), "last_step": float(lv.last_step[0].item()),
+            "flags": int(lv.flags[0].item()), "fitted": bool(lv.fitted[0].item())}
+
+
+def remove_lever_arm(quaternions, gps, R, l, sign=-1):
+    """gps + sign R (M(q) l) for one track on NumPy arrays (batch.lever_apply_ragged): sign = -1 moves fixes from the antenna to the camera
+    under the SLAM quaternions (n,4), the Sim3 rotation R (3,3) and the lever arm l (3,); +1 moves them back.  A NaN fix stays NaN, a
+    quaternion that cannot be normalised gives a NaN row.  Returns (gps_out (n,3), pose_flags (n,))."""
+    import torch
+    from . import batch as gb
+    if sign not in (-1, 1):
+        raise ValueError("remove_lever_arm: sign must be -1 (antenna -> camera) or +1 (camera -> antenna)")
+    n = len(gps)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape: torch.from_numpy(np.array(a, dtype=np.float64, order="C").reshape(shape)).to(dev)
+    out, fl = gb.lever_apply_ragged(up(quaternions, (n, 4)), up(gps, (n, 3)), torch.tensor([0, n], dtype=torch.int64, device=dev), up(R, (1, 9)),
+                                    up(l, (1, 3)), sign=sign)
+    return out.cpu().numpy(), fl.cpu().numpy()
+
+
 class FusionSession:
     """One track fused as it grows (batch.FusionStream with one track; host arrays in, host arrays out): push() takes the next poses and
     returns their fused rows and how far the track is final.  init_pos (3,) / init_quat (4,) = the Sim3-transformed pose 0, as at

@@ -909,6 +909,73 @@ GSF_API int gsf_sim3_local_apply_dev(gsf_ctx *ctx, const double *ts, const doubl
                                      const int32_t *n_knots, const int32_t *track_status, double *pos_out, double *quat_out,
                                      double *scale_at, int32_t *pose_flags);
 
+/* ---- antenna lever arm: fit the GNSS offset per track, take it out of fixes ---------------------------------------------------------------
+   Every other entry treats a fix as a measurement of the pose itself.  On a vehicle the antenna is not at the camera, and a fix measures
+       gps_i = s R pos_i + t + R M(q_i) l + noise
+   with l the antenna offset in the sensor frame (metres) and M(q) the rotation matrix of the normalised SLAM quaternion (SciPy's
+   convention); R M(q_i) is the orientation gsf_apply_sim3_batch_dev writes.  GNSS never touches the quaternion, so the world orientation
+   of every pose is known before the filter runs and a fix can be moved from the antenna to the camera in a pre-pass,
+   gps'_i = gps_i - R M(q_i) l; every existing entry is then fed those fixes unchanged.  The reference has no such step.
+   In, per track b = rows offsets[b] .. offsets[b + 1]: pos[.][3], quat[.][4] of the original SLAM track; gps[.][3] / valid as
+   dynamic_time_alignment returns them (NaN allowed); the starting values R[9], t[3], s (the track's global Sim3) and l0[3]; run_status
+   (may be NULL).  Stamps are not read.
+   [rows]  a row is USABLE when valid != 0, its fix and its position are finite and its quaternion can be normalised (|q| > 1e-9, the
+     rule of ExtendedKalmanFilter.normalize_quaternion; a NaN fails every comparison).  n_rows counts them; n_bad_quat counts the rows whose
+     only defect is the quaternion.
+   [shift]  by the first usable row f:  v_i = pos_i - pos_f,  u_i = R^T (gps_i - gps_f): no UTM-sized number enters a sum.
+   [unknowns]  ten: s, c[3] with t = R (c - s pos_f) + gps_f, l[3], a rotation increment dtheta[3].
+   [iteration]  from (R, t, s, l0) with phi = 0, for `iters` rounds (1 .. 8; a fixed count, no convergence exit):
+     w_i = s v_i + c + M_i l,  r_i = u_i - w_i,  J_i = [ v_i | I | M_i | -[w_i]x ];  N = sum J^T J + priors,  g = sum J^T r + priors;
+     priors: weight (sigma_fix / sigma_prior[j])^2 on l_j towards l0_j, (sigma_fix / sigma_rot)^2 on phi + dtheta towards 0, an infinite
+     sigma is weight 0;  N d = g by Cholesky on D N D, D = diag(N)^(-1/2);
+     s += d_s, c += d_c, l += d_l, phi += d_theta, R <- R exp([d_theta]x) (Rodrigues).
+   [switches]  fit_scale = 0 / fit_rotation = 0 pin s / dtheta: the unknown's row and column of N become the identity's, its g entry 0.
+   Out, per track: R[9], t[3], s, l[3]; l_cov[9] = the l block of sigma_fix^2 N^-1 of the last round; n_rows, n_bad_quat; rms_before /
+   rms_after = the RMS of r_i over the usable rows at the starting / final values (NaN without a usable row); last_step = the largest
+   |d_l| component of the last round; flags.
+   [flags]  GSF_LEVER_FEW (n_rows < min_rows), GSF_LEVER_VAR0 (sum |v_i - mean v|^2 / n < 1e-12), GSF_LEVER_SINGULAR (in any round a
+     pivot of the scaled Cholesky -- the value under its square root -- is <= pivot_min or not finite, or a step is not finite),
+     GSF_LEVER_SCALE (after any round s <= 1e-6 or s / s_start outside [1 / ratio_max, ratio_max]) and GSF_LEVER_TRACK (run_status != 0:
+     the rows are not read, n_rows = 0): the track keeps its starting R, t, s, l0 BYTE FOR BYTE, l_cov is diag(sigma_prior^2), rms_after =
+     rms_before and last_step is NaN.  GSF_LEVER_WEAK_X/Y/Z: l_cov[jj] > weak_ratio sigma_prior[j]^2 (the data did not observe that
+     axis; a ground vehicle never observes the one along its yaw axis).  GSF_LEVER_NOT_CONVERGED: last_step > conv_tol.
+   Every call writes every output byte.  One wave per track, no LDS, no atomics, no workspace.
+   gsf_lever_apply_dev:  xyz_out_i = xyz_i + sign R (M(q_i) l), R[9] and l[3] per track; sign = -1 moves antenna to camera, +1 camera to
+   antenna; pass the identity as R when quat is already a world quaternion (a fused one).  A component whose shift is exactly 0 returns
+   the input's bytes (so l = 0 returns xyz), a NaN fix stays NaN, a quaternion that cannot be normalised gives a NaN row and
+   GSF_LVP_BAD_QUAT (the filter then treats the pose as having no fix).  Nothing outside a track's rows is written.  One thread per pose.
+   Device pointers, asynchronous on the context's stream.  There is no host-pointer form: the Python binding uploads host arrays itself. */
+typedef struct gsf_lever_config {
+    double sigma_fix;       /* noise of a fix, metres (> 0)                                  [iteration] */
+    double sigma_prior[3];  /* prior sigma of l about l0 per sensor axis, metres (inf: none) [iteration] */
+    double sigma_rot;       /* prior sigma of the accumulated rotation, radians (inf: none)  [iteration] */
+    double ratio_max;       /* largest s / s_start and s_start / s, >= 1, default 2          [flags] */
+    double pivot_min;       /* smallest pivot of the scaled Cholesky, default 1e-10          [flags] */
+    double weak_ratio;      /* l_cov[jj] / sigma_prior[j]^2 above which an axis is weak, default 0.5 */
+    double conv_tol;        /* last_step above which a fit is not converged, default 1e-6 m  [flags] */
+    int32_t min_rows;       /* fewest usable rows, >= 1, default 8                           [flags] */
+    int32_t iters;          /* rounds, 1 .. 8, default 4                                     [iteration] */
+    int32_t fit_scale;      /* 0: s stays at its starting value                              [switches] */
+    int32_t fit_rotation;   /* 0: R stays at its starting value                              [switches] */
+} gsf_lever_config;
+#define GSF_LEVER_FEW 1             /* flags: fewer than min_rows usable rows */
+#define GSF_LEVER_VAR0 2            /* ... the usable SLAM positions do not move */
+#define GSF_LEVER_SINGULAR 4        /* ... a pivot <= pivot_min or not finite */
+#define GSF_LEVER_SCALE 8           /* ... s <= 1e-6 or s / s_start outside [1 / ratio_max, ratio_max] */
+#define GSF_LEVER_WEAK_X 16         /* ... l_cov[0] > weak_ratio sigma_prior[0]^2 */
+#define GSF_LEVER_WEAK_Y 32         /* ... l_cov[4] > weak_ratio sigma_prior[1]^2 */
+#define GSF_LEVER_WEAK_Z 64         /* ... l_cov[8] > weak_ratio sigma_prior[2]^2 */
+#define GSF_LEVER_NOT_CONVERGED 128 /* ... last_step > conv_tol */
+#define GSF_LEVER_TRACK 256         /* ... run_status != 0 */
+#define GSF_LVP_BAD_QUAT 1          /* pose_flags of gsf_lever_apply_dev: the quaternion could not be normalised, NaN row */
+GSF_API int gsf_lever_fit_dev(gsf_ctx *ctx, const double *pos, const double *quat, const double *gps, const uint8_t *valid,
+                              const int64_t *offsets, int64_t B, const double *R, const double *t, const double *s, const double *l0,
+                              const int32_t *run_status, const gsf_lever_config *cfg, double *R_out, double *t_out, double *s_out,
+                              double *l_out, double *l_cov, int32_t *n_rows, int32_t *n_bad_quat, double *rms_before, double *rms_after,
+                              double *last_step, int32_t *flags);
+GSF_API int gsf_lever_apply_dev(gsf_ctx *ctx, const double *quat, const double *xyz, const int64_t *offsets, int64_t B, const double *R,
+                                const double *l, double sign, double *xyz_out, int32_t *pose_flags);
+
 /* ---- pose queries: the fused track at any stamp, sensor points into the track's frame ----------------------------------------------------
    The fused track exists at the SLAM stamps; LiDAR returns, other exposures, map points and a second receiver have stamps of their own.
    These entries evaluate the track between its poses with the rule the filter itself uses for orientations (quaternion_nlerp,
