@@ -1522,6 +1522,150 @@ def refuse_gated(rb, r, g, k=0, want_cov=False, skip_seconds=5.0, config=None):
     return RunResult(pos=po, quat=qo, status=st, valid=vk, err_stats=stats, errors=errors, cov=cov)
 
 
+# ---------------------------------------------------------------------------- per-fix GNSS noise (gsf_ekf_smooth_weighted_dev, gsf_fix_var_at_poses_dev)
+class WeightedTrack(SmoothedTrack):
+    """ekf_smooth_weighted_ragged's result: a SmoothedTrack of the filter and smoother run with a measurement variance per pose, plus
+    nis (P,) or None = the normalised innovation squared of every used row (NaN elsewhere; mean 3 for a consistent filter) and
+    bad_sigma (P,) bool = the rows flagged _lib.POSE_BAD_SIGMA: a fix whose variance was not usable and that was treated as missing."""
+
+    def __init__(self, pos, quat, cov, pos_filt, cov_filt, flags, status, offsets, nis=None):
+        super().__init__(pos, quat, cov, pos_filt, cov_filt, flags, status, offsets)
+        self.nis = nis
+
+    @property
+    def bad_sigma(self):
+        return (self.flags & _lib.POSE_BAD_SIGMA) != 0
+
+    def mean_nis(self):
+        """(B,) mean of nis over the used rows of every track (NaN for a track without one; needs want_nis=True)"""
+        if self.nis is None:
+            raise ValueError("WeightedTrack.mean_nis: nis was not asked for (want_nis=True)")
+        B, P = int(self.offsets.numel()) - 1, int(self.nis.numel())
+        used = ~torch.isnan(self.nis)
+        n = (self.offsets[1:] - self.offsets[:-1]).to(self.nis.device)
+        track = torch.repeat_interleave(torch.arange(B, dtype=torch.int64, device=self.nis.device), n, output_size=P)
+        zero = torch.zeros((B,), dtype=torch.float64, device=self.nis.device)
+        total = zero.index_add(0, track, torch.where(used, self.nis, torch.zeros_like(self.nis)))
+        count = zero.index_add(0, track, used.to(torch.float64))
+        return total / count
+
+
+def ekf_smooth_weighted_ragged(ts, pos, quat, gps, valid, meas_var, offsets, init_pos, init_quat, config=None, run_status=None, want_filtered=False,
+                               want_nis=False):
+    """ekf_smooth_ragged with a measurement variance per pose (gsf_ekf_smooth_weighted_dev; definition: include/gsf.h), one launch on torch's
+    current stream.  meas_var (P,3) float64 = the variance of fix i per axis in the unit of config['ekf']['meas_noise_diag'], which is not
+    read.  A variance is usable when 1e-8 <= v <= 1e8; a row with a fix but an unusable variance is a pose without a fix in every respect
+    and is flagged POSE_BAD_SIGMA -- unless all three are +inf ("no information": no fix, no flag).  The other arguments as
+    ekf_smooth_ragged; want_nis: also the normalised innovation squared of every used row.  Returns a WeightedTrack."""
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid"); _chk(meas_var, torch.float64, (P, 3), "meas_var")
+    _chk(init_pos, torch.float64, (B, 3), "init_pos"); _chk(init_quat, torch.float64, (B, 4), "init_quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    cfg = EkfConfig.from_config(config or CONFIG)
+    f = dict(dtype=torch.float64, device=ts.device)
+    st = WeightedTrack(torch.empty((P, 3), **f), torch.empty((P, 4), **f), torch.empty((P, 7), **f),
+                       torch.empty((P, 3), **f) if want_filtered else None, torch.empty((P, 7), **f) if want_filtered else None,
+                       torch.empty((P,), dtype=torch.uint8, device=ts.device), torch.empty((B,), dtype=torch.int32, device=ts.device), offsets,
+                       torch.empty((P,), **f) if want_nis else None)
+    check(_lib.load().gsf_ekf_smooth_weighted_dev(context().handle, _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(meas_var), _p(offsets),
+                                                  _p(init_pos), _p(init_quat), _p(run_status), C.byref(cfg), B, _p(st.pos), _p(st.quat), _p(st.cov),
+                                                  _p(st.pos_filt), _p(st.cov_filt), _p(st.flags), _p(st.status), _p(st.nis)))
+    return st
+
+
+def fix_var_at_poses_ragged(ts, slam_offsets, gps_t, gps_offsets, fix_var, keep=None, valid=None):
+    """Per-fix variances carried onto SLAM stamps (gsf_fix_var_at_poses_dev; definition: include/gsf.h): ts (P,) with slam_offsets (B+1,),
+    gps_t (T,) ascending per log with gps_offsets (B+1,), fix_var (T,3), keep (T,) uint8 = the pre-filter's mask (None: all kept), valid
+    (P,) uint8 or None.  A pose takes, per axis, the larger variance of the kept fixes that bracket its stamp; +inf x3 where valid is 0 or
+    a side of the bracket is missing.  ValueError where the offsets do not end at the rows given (the kernel would hand the poses behind
+    the last offset to the last track).  Returns pose_var (P,3), the meas_var of ekf_smooth_weighted_ragged."""
+    B = _offsets_chk(slam_offsets)
+    if _offsets_chk(gps_offsets) != B:
+        raise ValueError("fix_var_at_poses_ragged: slam_offsets and gps_offsets must describe the same tracks")
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    T = int(gps_t.shape[0]) if gps_t.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(gps_t, torch.float64, (T,), "gps_t"); _chk(fix_var, torch.float64, (T, 3), "fix_var")
+    if keep is not None:
+        _chk(keep, torch.uint8, (T,), "keep")
+    if valid is not None:
+        _chk(valid, torch.uint8, (P,), "valid")
+    ends = torch.stack((slam_offsets[0], slam_offsets[-1], gps_offsets[0], gps_offsets[-1])).cpu().tolist()      # one small copy to the host
+    if ends != [0, P, 0, T]:
+        raise ValueError(f"fix_var_at_poses_ragged: slam_offsets must run from 0 to the {P} poses given and gps_offsets from 0 to the {T} fixes given "
+                         f"(they run {ends[0]}..{ends[1]} and {ends[2]}..{ends[3]})")
+    out = torch.empty((P, 3), dtype=torch.float64, device=ts.device)
+    check(_lib.load().gsf_fix_var_at_poses_dev(context().handle, _p(ts), _p(slam_offsets), _p(gps_t), _p(gps_offsets), _p(keep), _p(fix_var),
+                                               _p(valid), B, P, _p(out)))
+    return out
+
+
+def read_gnss_quality(paths):
+    """The columns behind the fourth of each GNSS text file (GPSmerge.py:41-60 writes numsats and velmode there; load_gps_data and
+    RaggedGeodeticBatch.from_files drop them), parsed as _read_gnss_file parses the file, in from_files order: a flat (T, C) float64 numpy
+    array on the host whose rows line up with the batch's gps_t.  ValueError naming the file if it has no such column, or another count
+    of them than the files before it."""
+    import numpy as np
+    parts, C_ = [], None
+    for path in paths:
+        try:
+            try:
+                raw = np.loadtxt(path, delimiter=" ")
+            except ValueError:
+                raw = np.loadtxt(path, delimiter=",")
+        except Exception as e:
+            raise ValueError(f"GNSS file {path}: {e}") from e
+        if raw.ndim == 1:
+            raw = raw.reshape(1, -1)
+        if raw.shape[1] < 4:                                             # an empty file included: _read_gnss_file raises on it as well
+            raise ValueError(f"GNSS file {path}: needs at least 4 columns (ts lat lon alt), got {raw.shape[1]}")
+        if raw.shape[1] < 5:
+            raise ValueError(f"GNSS file {path}: no quality column behind ts lat lon alt ({raw.shape[1]} columns)")
+        if C_ is not None and raw.shape[1] - 4 != C_:
+            raise ValueError(f"GNSS file {path}: {raw.shape[1] - 4} quality columns, the files before it have {C_}")
+        C_ = raw.shape[1] - 4
+        parts.append(np.asarray(raw[:, 4:], dtype=np.float64))
+    if not parts:
+        return np.zeros((0, 0))
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
+def quality_to_var(codes, table, default=float("inf")):
+    """A lookup from an integer quality column (velmode, an NMEA fix type, ...) to a variance triple: codes (T,) of any integer or float
+    dtype, table = {code: (var_x, var_y, var_z)} (e.g. {4: (s_h**2, s_h**2, s_v**2)} for RTK-fixed) -> (T,3) float64 on codes' device;
+    a code the table does not hold gets `default` on all three axes (+inf: "no information", the fix is not used and not flagged)."""
+    codes = torch.as_tensor(codes)
+    out = torch.full((int(codes.numel()), 3), float(default), dtype=torch.float64, device=codes.device)
+    flat = codes.reshape(-1)
+    for code, var in table.items():
+        v = torch.as_tensor([float(x) for x in var], dtype=torch.float64, device=codes.device)
+        if v.numel() != 3:
+            raise ValueError(f"quality_to_var: code {code} needs three variances")
+        out[flat == code] = v
+    return out
+
+
+def smooth_weighted_fused(rb, r, fix_var, valid=None, config=None, skip_seconds=5.0):
+    """ekf_smooth_weighted_ragged on the result r of run_fusion_ragged for the batch rb.  fix_var (T,3) = a variance per fix of rb's logs
+    (quality_to_var of read_gnss_quality's columns, or a receiver's own figures); fix_var_at_poses_ragged carries it onto the SLAM stamps
+    through the fixes the pre-filter kept (r.gps_keep) and the mask (r.valid, or valid=: another mask over the same rows, e.g. g.valid(k)
+    of gate_fused); the initial pose of every track is built as sweep_noise_fused builds it.  Returns the WeightedTrack (with the filter's
+    own track and nis) carrying pose_var (P,3) and step 6's nearest-fix error of four tracks against the fixes of the mask: err_stats4
+    (4,B,4) = {raw SLAM, Sim3, weighted filter, weighted smoother} x {count, mean, median, RMSE}, errors4 (4,P) (NaN where not evaluated)."""
+    ts, aligned, offsets = rb.ts.reshape(-1), r.aligned.reshape(-1, 3), rb.slam_offsets
+    v = (r.valid.reshape(-1) if valid is None else valid).contiguous()
+    pose_var = fix_var_at_poses_ragged(ts, offsets, rb.gps_t, rb.gps_offsets, fix_var, keep=r.gps_keep, valid=v)
+    ip, iq = _fused_init_pose(rb, r)
+    st = ekf_smooth_weighted_ragged(ts, rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4), aligned, v, pose_var, offsets, ip, iq, config=config,
+                                    run_status=r.run_status, want_filtered=True, want_nis=True)
+    rows = _step6_rows(ts, offsets, (rb.pos.reshape(-1, 3), r.sim3_pos.reshape(-1, 3), st.pos_filt, st.pos), aligned, v, skip_seconds)
+    st.err_stats4, st.errors4 = torch.stack([x[0] for x in rows]), torch.stack([x[1] for x in rows])
+    st.valid, st.init_pos, st.init_quat, st.pose_var = v, ip, iq, pose_var
+    return st
+
+
 # ---------------------------------------------------------------------------- local Sim3 alignment (gsf_sim3_local_fit_dev / _apply_dev)
 _LOCAL_MODES = {"scale": _lib.LOC_SCALE, "sim3": _lib.LOC_SIM3}
 

@@ -794,4 +794,30 @@ int gsf_lever_apply_dev(gsf_ctx* ctx, const double* quat, const double* xyz, con
     return launch_lever_apply(ctx, quat, xyz, offsets, B, R, l, sign, xyz_out, pose_flags);
 }
 
+// per-fix GNSS noise: device forms only (include/gsf.h; the Python binding uploads host arrays itself)
+int gsf_ekf_smooth_weighted_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                                const double* meas_var, const int64_t* offsets, const double* init_pos, const double* init_quat,
+                                const int32_t* run_status, const gsf_ekf_config* cfg, int64_t B, double* pos_out, double* quat_out,
+                                double* cov_out, double* pos_filt, double* cov_filt, uint8_t* pose_flags, int32_t* status, double* nis)
+{
+    GSF_REQUIRE(ctx && cfg && offsets, "ctx/cfg/offsets is NULL");
+    GSF_REQUIRE(B >= 0, "negative B");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(ts && pos && quat && gps && valid && meas_var && init_pos && init_quat && pos_out && quat_out && cov_out, "NULL array");
+    GSF_REQUIRE(B <= (int64_t)0x7fffffff, "B too large for one launch");
+    return launch_ekf_smooth_weighted(ctx, ts, pos, quat, gps, valid, meas_var, offsets, init_pos, init_quat, run_status, cfg, B, pos_out, quat_out,
+                                      cov_out, pos_filt, cov_filt, pose_flags, status, nis);
+}
+
+int gsf_fix_var_at_poses_dev(gsf_ctx* ctx, const double* ts, const int64_t* slam_offsets, const double* gps_t, const int64_t* gps_offsets,
+                             const uint8_t* gps_keep, const double* fix_var, const uint8_t* valid, int64_t B, int64_t P, double* pose_var)
+{
+    GSF_REQUIRE(ctx && slam_offsets && gps_offsets, "ctx/slam_offsets/gps_offsets is NULL");
+    GSF_REQUIRE(B >= 0 && P >= 0, "negative B or P");
+    if (B == 0 || P == 0) return GSF_OK;
+    GSF_REQUIRE(P <= (int64_t)0x7fffffff * 256, "P too large for one launch");
+    GSF_REQUIRE(ts && pose_var, "NULL array");                           // (gps_t / fix_var may be NULL when every log is empty)
+    return launch_fix_var_at_poses(ctx, ts, slam_offsets, gps_t, gps_offsets, gps_keep, fix_var, valid, B, P, pose_var);
+}
+
 }  // extern "C"

@@ -154,6 +154,13 @@ int launch_lever_fit(gsf_ctx* ctx, const double* pos, const double* quat, const 
                      double* rms_before, double* rms_after, double* last_step, int32_t* flags);
 int launch_lever_apply(gsf_ctx* ctx, const double* quat, const double* xyz, const int64_t* offsets, int64_t B, const double* R, const double* l,
                        double sign, double* xyz_out, int32_t* pose_flags);
+// per-fix GNSS noise (gsf_weighted.hip): the weighted whole-track smoother, and per-fix variances carried onto SLAM stamps
+int launch_ekf_smooth_weighted(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                               const double* meas_var, const int64_t* offsets, const double* init_pos, const double* init_quat,
+                               const int32_t* run_status, const gsf_ekf_config* cfg, int64_t B, double* pos_out, double* quat_out, double* cov_out,
+                               double* pos_filt, double* cov_filt, uint8_t* pose_flags, int32_t* status, double* nis);
+int launch_fix_var_at_poses(gsf_ctx* ctx, const double* ts, const int64_t* slam_offsets, const double* gps_t, const int64_t* gps_offsets,
+                            const uint8_t* gps_keep, const double* fix_var, const uint8_t* valid, int64_t B, int64_t P, double* pose_var);
 
 // filter_gps_outliers_ransac as a whole, windows found on the device (gsf_gpsfilter.hip); counts (may be NULL): log b = rows offsets[b] .. +counts[b]
 int check_gps_prefilter(const gsf_prefilter_config* f, int32_t max_log_rows, int64_t B, int* jseq_elems = nullptr, size_t* lds = nullptr);

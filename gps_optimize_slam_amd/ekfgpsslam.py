@@ -515,6 +515,25 @@ def ekf_smooth_aligned(timestamps, positions, quaternions, aligned_gps, valid_ma
             "status": int(r.status[0].item())}
 
 
+def ekf_smooth_aligned_weighted(timestamps, positions, quaternions, aligned_gps, valid_mask, meas_var, init_pos, init_quat, global_config=None):
+    """ekf_smooth_aligned with a measurement variance per pose (gsf_ekf_smooth_weighted_dev; definition: include/gsf.h): meas_var (n,3) =
+    the variance of every aligned fix per axis, in the unit of meas_noise_diag (which is not read).  A fix whose variance is not usable
+    (outside 1e-8 .. 1e8, NaN) is treated as missing and flagged _lib.POSE_BAD_SIGMA; three +inf mean "no information" and flag nothing.
+    Host arrays -> ekf_smooth_aligned's dict plus 'nis' (n,): the normalised innovation squared of the used rows, NaN elsewhere."""
+    import torch
+    from . import batch as gb
+    ts = f64(timestamps).ravel()
+    n = ts.size
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(shape)).to(dev)
+    r = gb.ekf_smooth_weighted_ragged(up(ts, (n,)), up(positions, (n, 3)), up(quaternions, (n, 4)), up(aligned_gps, (n, 3)),
+                                      up(valid_mask, (n,), np.uint8), up(meas_var, (n, 3)), torch.tensor([0, n], dtype=torch.int64, device=dev),
+                                      up(init_pos, (1, 3)), up(init_quat, (1, 4)), config=global_config, want_filtered=True, want_nis=True)
+    h = lambda t: t.cpu().numpy()
+    return {"pos": h(r.pos), "quat": h(r.quat), "cov": h(r.cov), "pos_filt": h(r.pos_filt), "cov_filt": h(r.cov_filt), "flags": h(r.flags),
+            "status": int(r.status[0].item()), "nis": h(r.nis)}
+
+
 def smooth_trajectory(slam_data_in, gps_data_in, sim3_pos_initial, sim3_quat_initial, global_config):
     """apply_ekf_correction's arguments, the whole-track smoother's result: the same alignment call (ref :847), the initial pose = row 0 of
     the Sim3-transformed track, then ekf_smooth_aligned.  Returns its dict; an empty track gives empty arrays (ref :835)."""

@@ -630,6 +630,54 @@ GSF_API int gsf_ekf_smooth_ragged_dev(gsf_ctx *ctx, const double *ts, const doub
                                       const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B, double *pos_out, double *quat_out,
                                       double *cov_out, double *pos_filt, double *cov_filt, uint8_t *pose_flags, int32_t *status);
 
+/* ---- per-fix GNSS noise: the whole-track filter and smoother with a measurement variance per pose ------------------------------------------
+   Every other filter entry weighs every fix with the one meas_noise_diag of its cfg.  Receivers report how good each fix is (NMEA GST, fix
+   type, satellite count; GPSmerge.py:41-60 writes numsats and velmode behind lat lon alt), and an RTK-fixed fix and a single-point fix
+   under trees differ by four orders of magnitude in variance.  This entry is gsf_ekf_smooth_ragged_dev with R replaced by the row's own.
+   meas_var[P][3] = the measurement variance of pose i per position axis, in the unit of meas_noise_diag (a variance: np.diag of it is R,
+   EKFGPSSLAM.py:686).  cfg's meas_noise_diag is not read.
+   Usable -- a variance v is usable when 1e-8 <= v <= 1e8 (finite, inside the stated range of meas_noise_diag, both ends included).  There
+   is no bound on the ratio of two variances of a track, nor on the ratio of two steps: rows at both ends of the range may follow each
+   other, over long and short steps (the variance scans rescale their composed maps; the argument stands above variance_scan_w in
+   gsf_weighted.hip).  P0 and Q dt as gsf_ekf_config states them.
+   Available -- avail[i] = the smoother's avail[i] (i >= 1, valid[i] != 0, fix i free of NaN; :867-869) AND all three variances of row i
+   usable.  A row that would be available but for its variances is a pose without a fix IN EVERY RESPECT -- the outage structure, the
+   sharp-turn decision, flags, spans and the reach of the backward pass are those of the same call with valid[i] = 0 -- and it carries
+   GSF_POSE_BAD_SIGMA.  Exception: all three variances +inf, the caller's way of saying "no information": no fix, and no bit.
+   meas_var of row 0 decides nothing (pose 0 takes no update; its outage state is the raw valid[0], :848), nor does meas_var of a row
+   whose mask byte is clear or whose fix holds a NaN: any bytes there change no output byte and set no bit.
+   Filter and smoother -- exactly as documented above gsf_ekf_smooth_ragged_dev, with r_i = meas_var[i] for R on every available row:
+   k = Pp / (Pp + r_i), the Joseph Pf = (1-k) Pp (1-k) + k r_i k, g = w k (z - xp) with the one-step blend w at a sharp-turn recovery;
+   A[k] = Pf[k] / Pp[k+1] and the e and d suffix scans read Pf, g and dt only and are unchanged.
+   nis[P] (may be NULL) = sum over the three axes of y_c^2 / (Pp_c + r_ic) on GSF_POSE_GNSS_USED rows, NaN elsewhere; y = z - xp is formed
+   relative to init_pos and is the innovation before any blend.  Mean 3 for a consistent filter: the caller's check on the variances given.
+   Everything else -- inputs, outputs and which may be NULL, run_status (NaN rows, nis included, zero flags, status 0, inputs not read),
+   empty tracks, pose_flags, status words -- as gsf_ekf_smooth_ragged_dev.  Every call writes every output byte.  With meas_var[i] =
+   cfg's meas_noise_diag on every row the variances are that entry's bit for bit (three scans here where axes with equal noise share one
+   there: the same values).  One wave per track, two passes, no workspace, any track length.  Device pointers, asynchronous on the
+   context's stream; there is no host-pointer form. */
+#define GSF_POSE_BAD_SIGMA 32 /* gsf_ekf_smooth_weighted_dev: the row had a fix, but a variance that is not usable (and not all three +inf) */
+GSF_API int gsf_ekf_smooth_weighted_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
+                                        const uint8_t *valid, const double *meas_var, const int64_t *offsets, const double *init_pos,
+                                        const double *init_quat, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
+                                        double *pos_out, double *quat_out, double *cov_out, double *pos_filt, double *cov_filt,
+                                        uint8_t *pose_flags, int32_t *status, double *nis);
+/* Per-fix variances carried onto SLAM stamps: pose_var[P][3] for gsf_ekf_smooth_weighted_dev from fix_var[T][3] of the GNSS logs.
+   In: ts[P] with slam_offsets int64[B+1]; gps_t[T] with gps_offsets int64[B+1] (ascending stamps per log); gps_keep[T] = the pre-filter's
+   mask (NULL: every fix kept); fix_var[T][3]; valid[P] (may be NULL).  For pose i of track b:
+   - valid given and valid[i] == 0: +inf x3, and the log is not read;
+   - otherwise, among the KEPT fixes of log b, lo = the last with stamp <= ts[i] and hi = the first with stamp >= ts[i]; either missing
+     (a pose before the first or after the last kept fix, an empty log, a NaN stamp): +inf x3;
+   - otherwise per axis the larger of the two variances; a NaN in either gives NaN, which the filter then flags.  A pose on a kept fix's
+     stamp takes that fix's own variance; with repeated stamps the larger of the last and the first of them.
+   The aligned fix is an interpolant of its neighbours (dynamic_time_alignment, :325-387), so the worse neighbour bounds it; the cubic
+   spline reaches further than the bracket -- a stated approximation, and nis is the caller's check on it.  One thread per pose: a binary
+   search on the log's stamps, then a walk over removed fixes; nothing outside [gps_offsets[b], gps_offsets[b+1]) is read, whatever the
+   stamps hold.  Device pointers, asynchronous on the context's stream. */
+GSF_API int gsf_fix_var_at_poses_dev(gsf_ctx *ctx, const double *ts, const int64_t *slam_offsets, const double *gps_t,
+                                     const int64_t *gps_offsets, const uint8_t *gps_keep, const double *fix_var, const uint8_t *valid,
+                                     int64_t B, int64_t P, double *pose_var);
+
 /* ---- EKF noise sweep: innovation statistics of the filter for K noise candidates per track ------------------------------------------------
    CONFIG['ekf'] (initial_cov_diag, process_noise_diag, meas_noise_diag, EKFGPSSLAM.py:25-27) is tuned by hand; the standard way to choose
    and check such values is the filter's own innovation sequence: its normalised innovation squared (NIS; mean 3 for a consistent 3-axis
