@@ -14,8 +14,7 @@
 // At a recovery b that is not a sharp turn, rows a..b-1 are rewritten with the closed form: those of this chunk in registers, those of
 // earlier chunks by reading Pf[k] back from cov_out, 64 rows at a time on chunk boundaries -- so every lane re-reads rows it stored itself,
 // and each row is rewritten at most once per track.
-#include "gsf_wave_common.hpp"
-#include "gsf_cov_core.hpp"
+#include "gsf_track_chunk.hpp"
 
 namespace {
 
@@ -47,10 +46,8 @@ __global__ __launch_bounds__(64) void ekf_cov_kernel(const CovArgs a, const EkfC
     const double* __restrict__ gpsb = a.gps + base * 3;
     const double* __restrict__ quatb = a.quat + base * 4;
     const uint8_t* __restrict__ valb = a.valid + base;
-    int same_axis[3] = { -1, -1, -1 };
-    if (cfg.P0[1] == cfg.P0[0] && cfg.Qps[1] == cfg.Qps[0] && cfg.Rm[1] == cfg.Rm[0]) same_axis[1] = 0;
-    if (cfg.P0[2] == cfg.P0[0] && cfg.Qps[2] == cfg.Qps[0] && cfg.Rm[2] == cfg.Rm[0]) same_axis[2] = 0;
-    else if (cfg.P0[2] == cfg.P0[1] && cfg.Qps[2] == cfg.Qps[1] && cfg.Rm[2] == cfg.Rm[1]) same_axis[2] = 1;
+    int same1, same2;
+    same_axes(cfg.P0, cfg.Qps, cfg.Rm, same1, same2);
 
     // carried from chunk to chunk (wave-uniform): Pf of the last pose, its stamp, the sum of dt so far, the open outage
     double cP[3] = { cfg.P0[0], cfg.P0[1], cfg.P0[2] };
@@ -84,13 +81,9 @@ __global__ __launch_bounds__(64) void ekf_cov_kernel(const CovArgs a, const EkfC
 
         // ---- filtered variances: position axes by the scans (ref :712-713, :723-731), quaternion axes by one prefix sum of dt
         AxisVar v0, v1, v2;
-        variance_chunk<6>(cfg, same_axis[1], same_axis[2], dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
+        variance_chunk<6>(cfg, same1, same2, dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
         const double Pf[3] = { v0.Pf, v1.Pf, v2.Pf }, Pm[3] = { v0.Pm, v1.Pm, v2.Pm };
-        double dsum = stepping ? dt : 0.0;
-#define GSF_SSTAGE(CTRL, RM) { dsum += dpp0<CTRL, RM>(dsum); }
-        GSF_SCAN_STAGES(GSF_SSTAGE)
-#undef GSF_SSTAGE
-        const double S = c_sum + dsum;
+        const double S = c_sum + wave_prefix(stepping ? dt : 0.0);
         double Pq[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) Pq[c] = cfg.P0[3 + c] + cfg.Qps[3 + c] * S;

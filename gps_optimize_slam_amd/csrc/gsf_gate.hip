@@ -1,17 +1,15 @@
 // gsf_gate.hip -- innovation gate: reject the GNSS fixes the filter disbelieves, K gates per track in one launch (gsf_innovation_gate_dev).
 //
-// One wave per (track, gate), 64 poses per chunk.  What does not depend on a rejection is formed once per chunk -- the rows, dt, the
-// "fix usable" ballot, the yaw-rate test of EVERY adjacent pair, d[i] -- exactly as the outage study's base pass forms it.  What does
-// depend on it -- the availability mask, the outage structure and the blend weight of a sharp-turn recovery, variance_chunk() and the
-// three affine scans of the noise sweep -- runs inside a speculate-and-repair loop (gsf_gate_core.hpp): scan under the current
+// One wave per (track, gate), 64 poses per chunk.  What does not depend on a rejection is formed once per chunk with the shared chunk body of
+// gsf_track_chunk.hpp -- the rows, dt, the "fix usable" ballot, the yaw-rate test of EVERY adjacent pair, d[i].  What does depend on it
+// -- the availability mask, the outage structure and the blend weight of a sharp-turn recovery, variance_chunk() and the three
+// position scans -- runs inside a speculate-and-repair loop (gsf_gate_core.hpp): scan under the current
 // rejection mask, ballot the lanes that are tested, applied and over the gate, settle the LOWEST one (every decision before it is
 // final), scan again.  The ballot decides the trip count, so the loop is wave-uniform: one pass for a chunk without a rejection, one
 // more per rejection.  The carries (variance, position, outage state, the run of rejected fixes) are taken from the settled pass only.
 // No LDS, no atomics, nothing shared between gates: a gate's rows are the same bytes for any K, any order and any neighbours.  A second
 // small kernel ors the per-(track, gate) words into gate_status[B] in a fixed order.  Definitions: include/gsf.h.
-#include "gsf_wave_common.hpp"
-#include "gsf_cov_core.hpp"
-#include "gsf_sweep_core.hpp"
+#include "gsf_track_chunk.hpp"
 #include "gsf_gate_core.hpp"
 
 namespace {
@@ -71,85 +69,32 @@ __global__ __launch_bounds__(64) void innovation_gate_kernel(const GateArgs a, c
     // ---- carried from chunk to chunk (wave-uniform), from the settled pass only
     double cP[3] = { cfg.P0[0], cfg.P0[1], cfg.P0[2] };                   // Pf of the last pose (pose 0: P0)
     double cx[3] = { 0.0, 0.0, 0.0 };                                     // its position relative to init_pos
-    int same1 = -1, same2 = -1;                                           // axes with identical (P0, Q, R) share their variance scan
-    if (cfg.P0[1] == cfg.P0[0] && cfg.Qps[1] == cfg.Qps[0] && cfg.Rm[1] == cfg.Rm[0]) same1 = 0;
-    if (cfg.P0[2] == cfg.P0[0] && cfg.Qps[2] == cfg.Qps[0] && cfg.Rm[2] == cfg.Rm[0]) same2 = 0;
-    else if (cfg.P0[2] == cfg.P0[1] && cfg.Qps[2] == cfg.Qps[1] && cfg.Rm[2] == cfg.Rm[1]) same2 = 1;
-    const Vec3 p0{ a.init_pos[b * 3], a.init_pos[b * 3 + 1], a.init_pos[b * 3 + 2] };
-    Quat cq = ekf_normalize(Quat{ a.init_quat[b * 4], a.init_quat[b * 4 + 1], a.init_quat[b * 4 + 2], a.init_quat[b * 4 + 3] });   // ref :842, :683
-    chunk_arrived(nxt);
-    Vec3 c_po = lane_bcast(nxt.p, 0);                                     // "previous original pose" of pose 0 is pose 0 itself (ref :858)
-    Quat c_r; bool c_ok = quat_unit(lane_bcast(nxt.q, 0), c_r);
-    double c_t = lane_bcast(nxt.t, 0);
-    const double t_arm = c_t + a.arm_seconds;                             // fixes with a later stamp are tested
+    int same1, same2;
+    same_axes(cfg.P0, cfg.Qps, cfg.Rm, same1, same2);
+    TrackCarry tc = track_carry_init(a.init_pos, a.init_quat, b, nxt, cfg);
+    bool c_ok = tc.first_ok;                                             // a local, not a member of the carry: gsf_track_chunk.hpp
+    const double t_arm = tc.c_t + a.arm_seconds;                          // fixes with a later stamp are tested
     const bool test_all = !(a.arm_seconds > 0.0);
-    Quat Cq = lane_bcast(quat_mul(cq, quat_conj(c_r)), 0);               // q_i = Cq r_i while every quaternion is valid (see wave_serial_chunks)
-    bool cq_fresh = true;
-    OutageCarry oc{ true, 0, false };
-    const double wgt_sharp = (cfg.sharp_turn_steps > 1) ? 1.0 / (double)cfg.sharp_turn_steps : 1.0;   // ref :752-768, :889
-    u64 unsorted_m = (c_t != c_t) ? 1ull : 0ull;                          // a NaN first stamp
+    u64 unsorted_m = (tc.c_t != tc.c_t) ? 1ull : 0ull;                    // a NaN first stamp
     GateCounts cnt = gate_counts_init();
     double nis_max = 0.0, nis_sum = 0.0;                                  // over the tested fixes that were applied
 
     for (int64_t c0 = 0; c0 < N; c0 += 64) {
-        const int64_t i = c0 + lane;
-        const int L = (int)((N - c0 < 64) ? (N - c0 - 1) : 63);
-        const bool active = i < N, stepping = active && i != 0;
         const ChunkIn in = nxt;
         nxt = load_chunk(tsb, posb, quatb, gpsb, valb, c0 + 64 + lane, N);   // the next chunk's rows are requested before this chunk's scans (clamped past the end)
-        const double t = in.t;
-        const Vec3 p = in.p, z = in.z;
-        // ---- calculate_relative_pose (ref :77-92) against the previous lane / the carry
-        Quat r; const bool ok = quat_unit(in.q, r);
-        const double t_pr = prev_lane(c_t, t);
-        const Vec3 p_pr{ prev_lane(c_po.x, p.x), prev_lane(c_po.y, p.y), prev_lane(c_po.z, p.z) };
-        const u64 act_m = mask_first(L + 1);
-        const u64 ok_mask = __ballot(ok);
-        const u64 both_m = ((ok_mask << 1) | (c_ok ? 1ull : 0ull)) & ok_mask;
-        const bool both_ok = (both_m >> lane) & 1ull;
-        const double dt = fmax(1e-6, t - t_pr);                          // ref :865
-        unsorted_m |= __ballot(stepping && !(t >= t_pr));                 // a stamp below the one before it, or a NaN one
-        const bool vraw = in.v != 0;
-        const bool fix = stepping && vraw && !(isnan(z.x) || isnan(z.y) || isnan(z.z));   // ref :867-869: usable before any rejection
-        const u64 fix_m = __ballot(fix) & act_m;
-        const u64 tested_m = test_all ? fix_m : (fix_m & __ballot(t > t_arm));
-        // ---- the yaw-rate test of EVERY adjacent pair: a rejection may put any of them inside an outage
-        const Quat r_pr = prev_lane(c_r, r);
-        bool fpair = false;
-        if (stepping && t > t_pr) fpair = !both_ok || yaw_rate_exceeds_body(r_pr, r, t - t_pr, cfg.yaw_thr_rad);   // :817, :821-824
-        const u64 pair_m = __ballot(fpair);
+        const ChunkFront f = chunk_front(in, tc, c_ok, c0, N, lane);
+        const int64_t i = f.i;
+        const int L = f.L;
+        const bool active = f.active, stepping = f.stepping, fix = f.fix;   // fix: usable before any rejection
+        const double dt = f.dt;
+        unsorted_m |= __ballot(stepping && !(f.t >= f.t_pr));             // a stamp below the one before it, or a NaN one
+        const u64 fix_m = __ballot(fix) & f.act_m;
+        const u64 tested_m = test_all ? fix_m : (fix_m & __ballot(f.t > t_arm));
+        const u64 pair_m = yaw_pair_mask<true>(f, 0ull, cfg.yaw_thr_rad, lane);   // EVERY adjacent pair: a rejection may put any of them inside an outage
 
-        // ---- predicted displacement d[i] (ref :707), as the pose kernels form it: one rotation by the wave-uniform Cq while every
-        // quaternion is valid, else calculate_relative_pose per pose and a prefix product of the increments
-        const Vec3 dp{ p.x - p_pr.x, p.y - p_pr.y, p.z - p_pr.z };
-        Vec3 u;
-        const bool telescope = c_ok && ((ok_mask & act_m) == act_m);
-        if (telescope) {
-            u = quat_rotate(Cq, dp);
-            u.x = stepping ? u.x : 0.0; u.y = stepping ? u.y : 0.0; u.z = stepping ? u.z : 0.0;
-            cq_fresh = false;
-        } else {
-            if (!cq_fresh) { cq = quat_mul(Cq, c_r); cq_fresh = true; }
-            const Quat r1i = quat_conj(r_pr);
-            Vec3 dpl = quat_rotate(r1i, dp);
-            Quat dq = quat_mul(r1i, r);
-            const bool move = stepping && both_ok;
-            dpl.x = move ? dpl.x : 0.0; dpl.y = move ? dpl.y : 0.0; dpl.z = move ? dpl.z : 0.0;
-            dq.x = move ? dq.x : 0.0; dq.y = move ? dq.y : 0.0; dq.z = move ? dq.z : 0.0; dq.w = move ? dq.w : 1.0;
-            Quat D = dq;
-            const Quat QID{ 0.0, 0.0, 0.0, 1.0 };
-#define GSF_QSTAGE(CTRL, RM) { const Quat o = dpp<CTRL, RM>(QID, D); D = quat_mul(o, D); }
-            GSF_SCAN_STAGES(GSF_QSTAGE)
-#undef GSF_QSTAGE
-            const Quat qi = ekf_normalize(quat_mul(cq, D));
-            const Quat q_prev = prev_lane(cq, qi);
-            u = quat_rotate(q_prev, dpl);
-            u.x = stepping ? u.x : 0.0; u.y = stepping ? u.y : 0.0; u.z = stepping ? u.z : 0.0;
-            cq = lane_bcast(qi, L);
-            if (((ok_mask >> L) & 1ull) != 0ull) Cq = lane_bcast(quat_mul(cq, quat_conj(lane_bcast(r, L))), 0);
-        }
+        const Vec3 u = orientation_step<false>(tc, c_ok, f).u;                 // the predicted displacement d[i] (ref :707)
         const double d[3] = { u.x, u.y, u.z };
-        const double zr[3] = { z.x - p0.x, z.y - p0.y, z.z - p0.z };       // relative to init_pos: y is a difference of two UTM northings
+        const double zr[3] = { f.z.x - tc.p0.x, f.z.y - tc.p0.y, f.z.z - tc.p0.z };   // relative to init_pos: y is a difference of two UTM northings
 
         // ---- speculate and repair: the filter under the current rejection mask, then the lowest lane over the gate is settled
         GateRepair g{ 0ull, 0ull, 0 };
@@ -158,16 +103,11 @@ __global__ __launch_bounds__(64) void innovation_gate_kernel(const GateArgs a, c
         for (;;) {
             const bool avail = fix && !((g.rej >> lane) & 1ull);          // a rejected fix is a pose without a fix, in every respect
             // outage structure and the sharp-turn decision under this mask: gsf_ekf_cov_ragged_dev's (gsf_cov_core.hpp)
-            av_m = __ballot(i == 0 ? vraw : avail) & act_m;               // pose 0: the raw mask byte (:848)
-            om = outage_masks(act_m, av_m, c0 == 0, oc.prev_avail);
+            av_m = avail_mask(f, avail);
+            om = outage_masks(f.act_m, av_m, c0 == 0, tc.oc.prev_avail);
             f_mask = pair_m & om.pair;
-            u64 sharp_m = 0ull;
-            for (u64 rm = om.rec; rm != 0ull; rm &= rm - 1ull) {
-                const int rl = __builtin_ctzll(rm);
-                const OutageSeg sg = outage_closed_at(om.start, f_mask, rl, c0, oc.ostart, oc.seg_sharp, cfg.yaw_thr_rad < 0.0);
-                if (sg.sharp) sharp_m |= 1ull << rl;
-            }
-            const double wgt = ((sharp_m >> lane) & 1ull) ? wgt_sharp : 1.0;   // the one-step blend at a sharp-turn recovery, else a hard update
+            const u64 sharp_m = sharp_recoveries(om, f_mask, c0, tc.oc, cfg.yaw_thr_rad < 0.0);
+            const double wgt = ((sharp_m >> lane) & 1ull) ? tc.wgt_sharp : 1.0;   // the one-step blend at a sharp-turn recovery, else a hard update
             // variances, gains and the three affine scans of the noise sweep, cfg's own noise
             AxisVar v0, v1, v2;
             variance_chunk<6>(cfg, same1, same2, dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
@@ -176,13 +116,9 @@ __global__ __launch_bounds__(64) void innovation_gate_kernel(const GateArgs a, c
             double y[3], S[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                Affine m = sweep_affine(avail, kg[c] * wgt, d[c], zr[c]);
-#define GSF_ASTAGE(CTRL, RM) { const Affine o{ dpp<CTRL, RM>(1.0, m.a), dpp0<CTRL, RM>(m.b) }; m = affine_compose(m, o); }
-                GSF_SCAN_STAGES(GSF_ASTAGE)
-#undef GSF_ASTAGE
-                x[c] = affine_apply(m, cx[c]);                            // p[i] - init_pos
-                const double pm = prev_lane(cx[c], x[c]) + d[c];          // p-[i] - init_pos (ref :707)
-                y[c] = zr[c] - pm;                                        // ref :722
+                const AxisPos ap = position_axis(avail, kg[c] * wgt, d[c], zr[c], cx[c]);
+                x[c] = ap.x;                                              // p[i] - init_pos
+                y[c] = zr[c] - ap.pm;                                     // ref :722
                 S[c] = Pm[c] + cfg.Rm[c];                                 // ref :723
             }
             nis = gate_nis(y, S);                                         // of the predicted state: the same whether the fix is applied or not
@@ -205,8 +141,8 @@ __global__ __launch_bounds__(64) void innovation_gate_kernel(const GateArgs a, c
         gate_chunk_counts(cnt, fix_m, tested_m, g.rej, g.forced, c0);
 #pragma unroll
         for (int c = 0; c < 3; ++c) { cP[c] = lane_bcast(Pf[c], L); cx[c] = lane_bcast(x[c], L); }
-        oc = outage_carry(oc, av_m, om.start, f_mask, L, c0);
-        c_po = lane_bcast(p, L); c_r = lane_bcast(r, L); c_ok = ((ok_mask >> L) & 1ull) != 0ull; c_t = lane_bcast(t, L);
+        track_carry_next(tc, f, c0, av_m, om.start, f_mask);
+        c_ok = last_ok(f);
     }
 
     if (unsorted_m != 0ull) {                                             // no filter run is defined: NaN rows, the mask as it came

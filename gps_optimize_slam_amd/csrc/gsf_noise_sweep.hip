@@ -2,16 +2,14 @@
 //
 // The state quaternion is never touched by GNSS, so the world-frame odometry increments d[i] = R(q_state[i-1]) dp_local[i]
 // are the same for every (P0, Q, R); RTS rewrites outputs only (ref :918-922), so the innovations do not depend on it.  One wave therefore
-// reads a chunk of 64 poses ONCE (89 B per pose), forms what every candidate shares -- dt, the "fix used" flags, the outage structure and
-// the blend weight of a sharp-turn recovery, d[i] -- and then runs its group of candidates one after the other on registers: the variance
+// reads a chunk of 64 poses ONCE (89 B per pose), forms what every candidate shares with the shared chunk body of gsf_track_chunk.hpp -- dt,
+// the "fix used" flags, the outage structure and the blend weight of a sharp-turn recovery, d[i] -- and then runs its group of candidates one after the other on registers: the variance
 // scans of the pose kernels (variance_chunk) give Pp and the gain, three affine scans give the positions, the twelve terms of
 // gsf_sweep_core.hpp are summed with one wave_sum16, and nothing is written per pose (except the optional trace of one candidate).
 // Grid: B x ceil(K / KC) workgroups of one wave; lane l of a wave holds the noise values, the carry and the twelve accumulators of the
 // l-th candidate of its group and hands them to the wave with v_readlane, so a candidate's arithmetic is the same instructions on the
 // same operands whatever its group: its row is the same bytes for every KC.  Definitions: include/gsf.h; KC: sweep_group(), gsf_wave_route.hpp.
-#include "gsf_wave_common.hpp"
-#include "gsf_cov_core.hpp"
-#include "gsf_sweep_core.hpp"
+#include "gsf_track_chunk.hpp"
 
 namespace {
 
@@ -67,93 +65,35 @@ __global__ __launch_bounds__(64, 2) void noise_sweep_kernel(const SweepArgs a, c
     for (int j = 0; j < SWEEP_NSTAT; ++j) acc[j] = 0.0;
 
     // ---- carried from chunk to chunk, the same for every candidate (wave-uniform)
-    const Vec3 p0{ a.init_pos[b * 3], a.init_pos[b * 3 + 1], a.init_pos[b * 3 + 2] };
-    Quat cq = ekf_normalize(Quat{ a.init_quat[b * 4], a.init_quat[b * 4 + 1], a.init_quat[b * 4 + 2], a.init_quat[b * 4 + 3] });   // ref :842, :683
-    chunk_arrived(nxt);
-    Vec3 c_po = lane_bcast(nxt.p, 0);                                     // "previous original pose" of pose 0 is pose 0 itself (ref :858)
-    Quat c_r; bool c_ok = quat_unit(lane_bcast(nxt.q, 0), c_r);
-    double c_t = lane_bcast(nxt.t, 0);
-    const double t_count = c_t + a.skip_seconds;                          // updates with a later stamp are counted
+    TrackCarry tc = track_carry_init(a.init_pos, a.init_quat, b, nxt, cfg);
+    const double t_count = tc.c_t + a.skip_seconds;                       // updates with a later stamp are counted
     const bool count_all = !(a.skip_seconds > 0.0);
-    Quat Cq = lane_bcast(quat_mul(cq, quat_conj(c_r)), 0);               // q_i = Cq r_i while every quaternion is valid (see wave_serial_chunks)
-    bool cq_fresh = true;
-    OutageCarry oc{ true, 0, false };
+    bool c_ok = tc.first_ok;                                             // a local, not a member of the carry: gsf_track_chunk.hpp
     bool c_counted = false;                                               // the last pose of the chunk before was a counted update
-    const double wgt_sharp = (cfg.sharp_turn_steps > 1) ? 1.0 / (double)cfg.sharp_turn_steps : 1.0;   // ref :752-768, :889
 
     for (int64_t c0 = 0; c0 < N; c0 += 64) {
-        const int64_t i = c0 + lane;
-        const int L = (int)((N - c0 < 64) ? (N - c0 - 1) : 63);
-        const bool active = i < N, stepping = active && i != 0;
         const ChunkIn in = nxt;
         nxt = load_chunk(tsb, posb, quatb, gpsb, valb, c0 + 64 + lane, N);   // the next chunk's rows are requested before this chunk's scans (clamped past the end)
-        const double t = in.t;
-        const Vec3 p = in.p, z = in.z;
-        // ---- calculate_relative_pose (ref :77-92) against the previous lane / the carry
-        Quat r; const bool ok = quat_unit(in.q, r);
-        const double t_pr = prev_lane(c_t, t);
-        const Vec3 p_pr{ prev_lane(c_po.x, p.x), prev_lane(c_po.y, p.y), prev_lane(c_po.z, p.z) };
-        const u64 act_m = mask_first(L + 1);
-        const u64 ok_mask = __ballot(ok);
-        const u64 both_m = ((ok_mask << 1) | (c_ok ? 1ull : 0ull)) & ok_mask;
-        const bool both_ok = (both_m >> lane) & 1ull;
-        const double dt = fmax(1e-6, t - t_pr);                          // ref :865
-        const bool vraw = in.v != 0;
-        const bool avail = stepping && vraw && !(isnan(z.x) || isnan(z.y) || isnan(z.z));   // ref :867-869
+        const ChunkFront f = chunk_front(in, tc, c_ok, c0, N, lane);
+        const int64_t i = f.i;
+        const int L = f.L;
+        const bool active = f.active, stepping = f.stepping, avail = f.fix;
+        const double dt = f.dt;
         // ---- outage structure and the sharp-turn decision: gsf_ekf_cov_ragged_dev's (gsf_cov_core.hpp)
-        const u64 avail_m = __ballot(avail) & act_m;
-        const u64 av_m = __ballot(i == 0 ? vraw : avail) & act_m;         // pose 0: the raw mask byte (:848)
-        const OutageMasks om = outage_masks(act_m, av_m, c0 == 0, oc.prev_avail);
-        const Quat r_pr = prev_lane(c_r, r);
-        u64 f_mask = 0ull;
-        if (om.pair != 0ull) {
-            const bool outpair = (om.pair >> lane) & 1ull;
-            bool f = false;
-            if (outpair && t > t_pr) f = !both_ok || yaw_rate_exceeds_body(r_pr, r, t - t_pr, cfg.yaw_thr_rad);   // :817, :821-824
-            f_mask = __ballot(f);
-        }
-        u64 sharp_m = 0ull;
-        for (u64 rm = om.rec; rm != 0ull; rm &= rm - 1ull) {
-            const int rl = __builtin_ctzll(rm);
-            const OutageSeg sg = outage_closed_at(om.start, f_mask, rl, c0, oc.ostart, oc.seg_sharp, cfg.yaw_thr_rad < 0.0);
-            if (sg.sharp) sharp_m |= 1ull << rl;
-        }
-        const double wgt = ((sharp_m >> lane) & 1ull) ? wgt_sharp : 1.0;   // the one-step blend at a sharp-turn recovery, else a hard update
+        const u64 avail_m = __ballot(avail) & f.act_m;
+        const u64 av_m = avail_mask(f, avail);
+        const OutageMasks om = outage_masks(f.act_m, av_m, c0 == 0, tc.oc.prev_avail);
+        const u64 f_mask = yaw_pair_mask<false>(f, om.pair, cfg.yaw_thr_rad, lane);
+        const u64 sharp_m = sharp_recoveries(om, f_mask, c0, tc.oc, cfg.yaw_thr_rad < 0.0);
+        const double wgt = ((sharp_m >> lane) & 1ull) ? tc.wgt_sharp : 1.0;   // the one-step blend at a sharp-turn recovery, else a hard update
         // ---- which updates are counted (U) and which pairs (i - 1, i) lie in U
-        const u64 cnt_m = count_all ? avail_m : (avail_m & __ballot(t > t_count));
+        const u64 cnt_m = count_all ? avail_m : (avail_m & __ballot(f.t > t_count));
         const u64 cntp_m = (cnt_m << 1) | (c_counted ? 1ull : 0ull);
         const bool counted = (cnt_m >> lane) & 1ull, counted_prev = (cntp_m >> lane) & 1ull;
 
-        // ---- predicted displacement d[i] (ref :707), as the pose kernels form it: one rotation by the wave-uniform Cq while every
-        // quaternion is valid, else calculate_relative_pose per pose and a prefix product of the increments
-        const Vec3 dp{ p.x - p_pr.x, p.y - p_pr.y, p.z - p_pr.z };
-        Vec3 u;
-        const bool telescope = c_ok && ((ok_mask & act_m) == act_m);
-        if (telescope) {
-            u = quat_rotate(Cq, dp);
-            u.x = stepping ? u.x : 0.0; u.y = stepping ? u.y : 0.0; u.z = stepping ? u.z : 0.0;
-            cq_fresh = false;
-        } else {
-            if (!cq_fresh) { cq = quat_mul(Cq, c_r); cq_fresh = true; }
-            const Quat r1i = quat_conj(r_pr);
-            Vec3 dpl = quat_rotate(r1i, dp);
-            Quat dq = quat_mul(r1i, r);
-            const bool move = stepping && both_ok;
-            dpl.x = move ? dpl.x : 0.0; dpl.y = move ? dpl.y : 0.0; dpl.z = move ? dpl.z : 0.0;
-            dq.x = move ? dq.x : 0.0; dq.y = move ? dq.y : 0.0; dq.z = move ? dq.z : 0.0; dq.w = move ? dq.w : 1.0;
-            Quat D = dq;
-            const Quat QID{ 0.0, 0.0, 0.0, 1.0 };
-#define GSF_QSTAGE(CTRL, RM) { const Quat o = dpp<CTRL, RM>(QID, D); D = quat_mul(o, D); }
-            GSF_SCAN_STAGES(GSF_QSTAGE)
-#undef GSF_QSTAGE
-            const Quat qi = ekf_normalize(quat_mul(cq, D));
-            const Quat q_prev = prev_lane(cq, qi);
-            u = quat_rotate(q_prev, dpl);
-            cq = lane_bcast(qi, L);
-            if (((ok_mask >> L) & 1ull) != 0ull) Cq = lane_bcast(quat_mul(cq, quat_conj(lane_bcast(r, L))), 0);
-        }
+        const Vec3 u = orientation_step<false>(tc, c_ok, f).u;                 // the predicted displacement d[i] (ref :707)
         const double d[3] = { u.x, u.y, u.z };
-        const double zr[3] = { z.x - p0.x, z.y - p0.y, z.z - p0.z };       // relative to init_pos: y is a difference of two UTM northings
+        const double zr[3] = { f.z.x - tc.p0.x, f.z.y - tc.p0.y, f.z.z - tc.p0.z };   // relative to init_pos: y is a difference of two UTM northings
 
         // ---- the candidates of the group, one after the other: one code path, a run-time loop
         for (int kk = 0; kk < kc; ++kk) {
@@ -165,23 +105,17 @@ __global__ __launch_bounds__(64, 2) void noise_sweep_kernel(const SweepArgs a, c
                 P0k[c] = ck[c]; kcfg.Qps[c] = ck[3 + c]; kcfg.Rm[c] = ck[6 + c];
                 cP[c] = lane_bcast(mPf[c], kk); cx[c] = lane_bcast(mp[c], kk); cnu[c] = lane_bcast(mnu[c], kk);
             }
-            int same1 = -1, same2 = -1;                                   // axes with identical (P0, Q, R) share their variance scan
-            if (P0k[1] == P0k[0] && kcfg.Qps[1] == kcfg.Qps[0] && kcfg.Rm[1] == kcfg.Rm[0]) same1 = 0;
-            if (P0k[2] == P0k[0] && kcfg.Qps[2] == kcfg.Qps[0] && kcfg.Rm[2] == kcfg.Rm[0]) same2 = 0;
-            else if (P0k[2] == P0k[1] && kcfg.Qps[2] == kcfg.Qps[1] && kcfg.Rm[2] == kcfg.Rm[1]) same2 = 1;
+            int same1, same2;
+            same_axes(P0k, kcfg.Qps, kcfg.Rm, same1, same2);
             AxisVar v0, v1, v2;
             variance_chunk<6>(kcfg, same1, same2, dt, stepping, avail, cP[0], cP[1], cP[2], v0, v1, v2);
             const double Pf[3] = { v0.Pf, v1.Pf, v2.Pf }, Pm[3] = { v0.Pm, v1.Pm, v2.Pm }, kg[3] = { v0.kg, v1.kg, v2.kg };
             double x[3], y[3], S[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                Affine m = sweep_affine(avail, kg[c] * wgt, d[c], zr[c]);
-#define GSF_ASTAGE(CTRL, RM) { const Affine o{ dpp<CTRL, RM>(1.0, m.a), dpp0<CTRL, RM>(m.b) }; m = affine_compose(m, o); }
-                GSF_SCAN_STAGES(GSF_ASTAGE)
-#undef GSF_ASTAGE
-                x[c] = affine_apply(m, cx[c]);                            // p[i] - init_pos
-                const double pm = prev_lane(cx[c], x[c]) + d[c];          // p-[i] - init_pos (ref :707)
-                y[c] = zr[c] - pm;                                        // ref :722
+                const AxisPos ap = position_axis(avail, kg[c] * wgt, d[c], zr[c], cx[c]);
+                x[c] = ap.x;                                              // p[i] - init_pos
+                y[c] = zr[c] - ap.pm;                                     // ref :722
                 S[c] = Pm[c] + kcfg.Rm[c];                                // ref :723
             }
             double nu[3], nu_prev[3], term[SWEEP_NSTAT];
@@ -210,9 +144,9 @@ __global__ __launch_bounds__(64, 2) void noise_sweep_kernel(const SweepArgs a, c
         }
 
         // ---- carry to the next 64 poses (from the last active lane L)
-        oc = outage_carry(oc, av_m, om.start, f_mask, L, c0);
+        track_carry_next(tc, f, c0, av_m, om.start, f_mask);
         c_counted = ((cnt_m >> L) & 1ull) != 0ull;
-        c_po = lane_bcast(p, L); c_r = lane_bcast(r, L); c_ok = ((ok_mask >> L) & 1ull) != 0ull; c_t = lane_bcast(t, L);
+        c_ok = last_ok(f);
     }
     if (strow && lane < kc) {
 #pragma unroll

@@ -794,9 +794,29 @@ __device__ __forceinline__ double pow2_rcp_below(const double d)
 // q dt and r compare.  Powers of two commute with every rounding of the products below and of moebius_apply() (no entry is subnormal on either side
 // wherever the unscaled form stayed in range), so the variances are the ones of the unscaled form BIT FOR BIT there -- the default
 // CONFIG included.  Stated range (include/gsf.h): 0 <= P0 <= 1e8, 1e-8 <= R <= 1e8, 0 <= Q dt <= 1e14.
-template <int NS = 6>
+// RESCALE (per-row r: the weighted smoother, rr of the lane's own row).  What keeps a factor S_i / D_i small is P_{i-1} <= D_i.  With steps of
+// one length it holds whatever the r_i are: P_{i-1} <= min(r_{i-1}, P_{i-2} + q dt), so rows alternating between 1e8 and 1e-8 under an even
+// dt give factors below 4 (the unrescaled product of a chunk stays below 1e21 there).  It fails when the variance a row inherits is large
+// against its OWN step and r: a long step (P climbs by q dt, up to 1e14) followed by a short one with a fix.  With one r that needs rows
+// WITHOUT a fix on the long steps -- with a fix on every row P < r <= D bounds every factor by 4, the argument above -- and the plain scan
+// leaves the doubles there as well (an outage pose per long step, r = 1e-8, 32 times a chunk).  With r_i per row it happens with a fix on
+// every row: r = 1e8 on the long steps lets P reach 1e8, r = 1e-8 on a step of q dt = 1e-7 behind it gives a factor of 1e15, and a chunk
+// holds 32 such pairs (1e480; tests/weighted_ref.long_short_track).  So the step scaling stays as it is, and with RESCALE the COMPOSED map
+// of every lane is scaled again by the power of two that brings its own D into [1, 2), after the third stage (maps of up to 8 poses: at most
+// 4 such pairs of at most (1e8 + 1e14) / 1e-8 = 1e22, entries below 1e92 times 2^8) and after the fifth.  A Moebius map is unchanged by a
+// common factor, per lane.  Relative to its D a composed map has B / D = the variance it gives P = 0 (at most 64 (1e8 + 1e14)), C / D <=
+// the sum of 1 / r_i over its fixes (the information they can add: at most 64e8), A / D <= 1 + (B / D)(C / D) (the derivative of a
+// posterior by its prior is at most 1): every entry is at most 1e26 after a rescale, 1e52 and 1e104 after the next two stages, and
+// moebius_apply() multiplies by P <= 1e8 + 64e14.  D >= 1 throughout (a product of scaled D_i plus non-negative terms), so the rescale
+// never sees zero or a subnormal.  Entries that shrink (A: a chain of r_i / D_i) only underflow towards 0, as with one r.  Powers of two
+// commute with every rounding here, so wherever the unrescaled product stays in range -- with meas_var equal to cfg's R on every row
+// included -- the variances are the plain scan's BIT FOR BIT.  Stated range (include/gsf.h): P0 and Q dt as gsf_ekf_config states them,
+// 1e-8 <= r_i <= 1e8 for every row, no bound on the ratio of two rows and none on the ratio of two steps.  The scan with one r does NOT
+// take the rescales: they would turn a NaN of its overflow cases into a number.
+template <int NS = 6, bool RESCALE = false>
 __device__ __forceinline__ Moebius variance_scan(const double q, const double rr, const double dt, const bool stepping, const bool avail)
 {
+    static_assert(!RESCALE || NS == 6, "the rescaled scan runs all six stages");
     const double b0 = q * dt;
     double A = 1.0, Bm = stepping ? b0 : 0.0, Cm = 0.0, Dm = 1.0;
     if (avail) { const double d = b0 + rr, sc = pow2_rcp_below(d); A = rr * sc; Bm = (rr * b0) * sc; Cm = sc; Dm = d * sc; }
@@ -805,7 +825,17 @@ __device__ __forceinline__ Moebius variance_scan(const double q, const double rr
         const double oA = dpp<CTRL, RM>(1.0, A), oB = dpp0<CTRL, RM>(Bm), oC = dpp0<CTRL, RM>(Cm), oD = dpp<CTRL, RM>(1.0, Dm); \
         const double nA = A * oA + Bm * oC, nB = A * oB + Bm * oD, nC = Cm * oA + Dm * oC, nD = Cm * oB + Dm * oD;                  \
         A = nA; Bm = nB; Cm = nC; Dm = nD; }
-    GSF_SCAN_STAGES_N(NS, GSF_MSTAGE)
+#define GSF_MRESCALE { const double sc = pow2_rcp_below(Dm); A *= sc; Bm *= sc; Cm *= sc; Dm *= sc; }
+    if constexpr (RESCALE) {
+        GSF_MSTAGE(DPP_ROW_SHR1, 0xf) GSF_MSTAGE(DPP_ROW_SHR2, 0xf) GSF_MSTAGE(DPP_ROW_SHR4, 0xf)
+        GSF_MRESCALE
+        GSF_MSTAGE(DPP_ROW_SHR8, 0xf) GSF_MSTAGE(DPP_ROW_BCAST15, 0xa)
+        GSF_MRESCALE
+        GSF_MSTAGE(DPP_ROW_BCAST31, 0xc)
+    } else {
+        GSF_SCAN_STAGES_N(NS, GSF_MSTAGE)
+    }
+#undef GSF_MRESCALE
 #undef GSF_MSTAGE
     return Moebius{ A, Bm, Cm, Dm };
 }
@@ -819,10 +849,10 @@ __device__ __forceinline__ AxisVar variance_finish(const Moebius& m, const doubl
     v.kg = v.Pm * fast_rcp(v.Pm + rr);                                   // Kalman gain if the fix is used
     return v;
 }
-template <int NS = 6>
+template <int NS = 6, bool RESCALE = false>
 __device__ __forceinline__ AxisVar variance_axis(const double q, const double rr, const double dt, const bool stepping, const bool avail, const double cPc)
 {
-    return variance_finish(variance_scan<NS>(q, rr, dt, stepping, avail), q, rr, dt, cPc);
+    return variance_finish(variance_scan<NS, RESCALE>(q, rr, dt, stepping, avail), q, rr, dt, cPc);
 }
 // (scalar arguments and constant indices only: a helper that indexes its caller's arrays dynamically puts them into scratch)
 // NS: scan stages the chunk needs (GSF_SCAN_STAGES_N) -- same bits for every NS that covers the chunk's last active lane

@@ -638,8 +638,8 @@ GSF_API int gsf_ekf_smooth_ragged_dev(gsf_ctx *ctx, const double *ts, const doub
    EKFGPSSLAM.py:686).  cfg's meas_noise_diag is not read.
    Usable -- a variance v is usable when 1e-8 <= v <= 1e8 (finite, inside the stated range of meas_noise_diag, both ends included).  There
    is no bound on the ratio of two variances of a track, nor on the ratio of two steps: rows at both ends of the range may follow each
-   other, over long and short steps (the variance scans rescale their composed maps; the argument stands above variance_scan_w in
-   gsf_weighted.hip).  P0 and Q dt as gsf_ekf_config states them.
+   other, over long and short steps (the variance scans rescale their composed maps; the argument stands above variance_scan in
+   gsf_wave_common.hpp).  P0 and Q dt as gsf_ekf_config states them.
    Available -- avail[i] = the smoother's avail[i] (i >= 1, valid[i] != 0, fix i free of NaN; :867-869) AND all three variances of row i
    usable.  A row that would be available but for its variances is a pose without a fix IN EVERY RESPECT -- the outage structure, the
    sharp-turn decision, flags, spans and the reach of the backward pass are those of the same call with valid[i] = 0 -- and it carries

@@ -1,4 +1,4 @@
-// TEST-ONLY host harness: compiles the GSF_HD rules of gsf_weighted_core.hpp (what gsf_weighted.hip calls per lane / per thread) with g++ as
+// TEST-ONLY host harness: compiles the GSF_HD rules of gsf_weighted_core.hpp (what gsf_smooth.hip and gsf_weighted.hip call per lane / per thread) with g++ as
 // a STAND-ALONE PROGRAM, so that tests/test_weighted_host.py can run it plain and under -fsanitize=address,undefined and compare what it
 // writes with tests/weighted_ref.py bit for bit.  Never shipped, never loaded by the package.
 //

@@ -200,7 +200,7 @@ def test_restatement_against_the_50_digit_yardstick_at_the_ends_of_the_range(yar
 @pytest.mark.parametrize("config", ["default", "axes-differ"])
 def test_long_and_short_steps_need_the_rescaled_scan(yard, config):
     """r at both ends of the range AND steps of 1e14 s followed by repeated stamps: the product of a chunk's scaled steps leaves the doubles
-    (variance_scan as it stands returns NaN), variance_scan_w's two rescales keep it in range, and the result is the yardstick's"""
+    (variance_scan as it stands returns NaN), the two rescales of variance_scan<6, true> keep it in range, and the result is the yardstick's"""
     cfg = full_cfg({} if config == "default" else AXES_DIFFER)
     name, ts, pos, quat, aligned, valid, ip, iq, mv = W.long_short_track()
     P0, Q = (np.array(cfg["ekf"][k], float)[:3] for k in ("initial_cov_diag", "process_noise_diag"))

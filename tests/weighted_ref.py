@@ -319,7 +319,7 @@ def _pow2_rcp_below(d):
 def scan_variances(dt, avail, r, q, P0, rescale):
     """Pf (n,) of ONE axis as the wave kernels form it: chunks of 64 poses, every used fix's Moebius step scaled by a power of two, the six
     scan stages of GSF_SCAN_STAGES (row_shr 1, 2, 4, 8, row_bcast 15 and 31) composed lane by lane, the carry applied at the end.
-    rescale: variance_scan_w's rescale of every lane's composed map after the third and the fifth stage (False: variance_scan as it stands)."""
+    rescale: variance_scan<6, true>'s rescale of every lane's composed map after the third and the fifth stage (False: variance_scan as it stands)."""
     n = len(dt)
     Pf = np.empty(n)
     Pf[0] = P0
