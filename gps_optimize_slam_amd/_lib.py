@@ -18,6 +18,7 @@ ST_HAD_OUTAGE, ST_RTS_APPLIED, ST_SHARP_TURN, ST_ENDED_IN_OUTAGE, ST_BAD_QUAT = 
 POSE_GNSS_USED, POSE_IN_OUTAGE, POSE_SMOOTHED, POSE_SHARP_TURN = 1, 2, 4, 8          # per-pose flags of gsf_ekf_cov_ragged_dev
 POSE_SPAN_START = 16                                                                 # ... and of gsf_ekf_smooth_ragged_dev: first row of a smoothing span
 POSE_BAD_SIGMA = 32                                                                  # ... and of gsf_ekf_smooth_weighted_dev: a fix with an unusable variance
+REWEIGHT_HUBER, REWEIGHT_CAUCHY, REWEIGHT_MAX_ROUNDS = 0, 1, 32                       # GSF_REWEIGHT_*: the losses of gsf_ekf_smooth_reweighted_dev
 
 
 class GsfError(RuntimeError):
@@ -196,6 +197,7 @@ SIGNATURES = {
     "gsf_ekf_cov_ragged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _vp]),
     "gsf_ekf_smooth_ragged_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64] + [_vp] * 7),
     "gsf_ekf_smooth_weighted_dev": (C.c_int, [_vp] * 11 + [C.POINTER(EkfConfig), _i64] + [_vp] * 8),
+    "gsf_ekf_smooth_reweighted_dev": (C.c_int, [_vp] * 11 + [C.POINTER(EkfConfig), _i64, _i32, _f64, _i32] + [_vp] * 11),
     "gsf_fix_var_at_poses_dev": (C.c_int, [_vp] * 8 + [_i64, _i64, _vp]),
     "gsf_ekf_noise_sweep_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _i32, _f64, _i32, _i32] + [_vp] * 7),
     "gsf_outage_study_dev": (C.c_int, [_vp] * 10 + [C.POINTER(EkfConfig), _i64, _vp, _vp, _vp, _i32, _i32] + [_vp] * 6),

@@ -1666,6 +1666,91 @@ def smooth_weighted_fused(rb, r, fix_var, valid=None, config=None, skip_seconds=
     return st
 
 
+# ---------------------------------------------------------------------------- robust smoothing (gsf_ekf_smooth_reweighted_dev)
+_LOSSES = {"huber": _lib.REWEIGHT_HUBER, "cauchy": _lib.REWEIGHT_CAUCHY}
+
+
+class ReweightedTrack(WeightedTrack):
+    """ekf_smooth_reweighted_ragged's result: the WeightedTrack of the LAST solve (nis under its effective variances), plus weight (P,) =
+    the weights computed from that solve's track (NaN on rows without an update), rounds_used (B,) int32 = the reweighted solves done,
+    w_change (B,) = the largest step of a weight in the last solve (0 at a fixed point), and meas_var (P,3) = the variances given."""
+
+    def __init__(self, pos, quat, cov, pos_filt, cov_filt, flags, status, offsets, nis, weight, rounds_used, w_change, meas_var):
+        super().__init__(pos, quat, cov, pos_filt, cov_filt, flags, status, offsets, nis)
+        self.weight, self.rounds_used, self.w_change, self.meas_var = weight, rounds_used, w_change, meas_var
+
+    def downweighted(self, below=0.5):
+        """(P,) bool: the used rows whose weight fell below `below` -- the fixes the loss disbelieves"""
+        return self.weight < below                                      # (NaN compares false)
+
+    def effective_var(self):
+        """(P,3): min(meas_var / weight, 1e8) on the used rows -- what one more solve would run with -- and meas_var elsewhere"""
+        cap = torch.full_like(self.meas_var, 1e8)
+        return torch.where(torch.isnan(self.weight)[:, None], self.meas_var, torch.minimum(self.meas_var / self.weight[:, None], cap))
+
+
+def ekf_smooth_reweighted_ragged(ts, pos, quat, gps, valid, offsets, init_pos, init_quat, meas_var=None, loss="huber", c2=None, rounds=5, config=None,
+                                 run_status=None, want_filtered=False, want_nis=False):
+    """The weighted smoother made robust by iteratively reweighted least squares, every round inside ONE launch
+    (gsf_ekf_smooth_reweighted_dev; definition: include/gsf.h).  Solve 0 is ekf_smooth_weighted_ragged on meas_var (P,3) -- None:
+    config['ekf']['meas_noise_diag'] on every row; after each solve every used fix's residual against the smoothed track gives u2 (with the
+    GIVEN variance) and a weight -- loss 'huber': 1 for u2 <= c2, else sqrt(c2 / u2); 'cauchy': 1 / (1 + u2 / c2) -- and the next solve runs
+    with min(meas_var / w, 1e8).  c2: a chi-square threshold of 3 degrees of freedom (None: chi2_gate(0.95) = 7.81).  It stops after
+    `rounds` reweighted solves (0..32) or, per track, at a fixed point of the weights.  The other arguments as ekf_smooth_weighted_ragged.
+    Returns a ReweightedTrack."""
+    if loss not in _LOSSES:
+        raise ValueError(f"ekf_smooth_reweighted_ragged: loss must be 'huber' or 'cauchy', got {loss!r}")
+    c2 = chi2_gate(0.95) if c2 is None else float(c2)
+    if not (0.0 < c2 < float("inf")):
+        raise ValueError(f"ekf_smooth_reweighted_ragged: c2 must be finite and > 0, got {c2!r}")
+    if not (isinstance(rounds, int) and 0 <= rounds <= _lib.REWEIGHT_MAX_ROUNDS):
+        raise ValueError(f"ekf_smooth_reweighted_ragged: rounds must be an int in [0, {_lib.REWEIGHT_MAX_ROUNDS}], got {rounds!r}")
+    B = _offsets_chk(offsets)
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(gps, torch.float64, (P, 3), "gps"); _chk(valid, torch.uint8, (P,), "valid")
+    if meas_var is not None:
+        _chk(meas_var, torch.float64, (P, 3), "meas_var")
+    _chk(init_pos, torch.float64, (B, 3), "init_pos"); _chk(init_quat, torch.float64, (B, 4), "init_quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    cfg = EkfConfig.from_config(config or CONFIG)
+    f = dict(dtype=torch.float64, device=ts.device)
+    given = meas_var if meas_var is not None else torch.tensor(list(cfg.meas_noise_diag)[:3], **f).expand(P, 3)
+    st = ReweightedTrack(torch.empty((P, 3), **f), torch.empty((P, 4), **f), torch.empty((P, 7), **f),
+                         torch.empty((P, 3), **f) if want_filtered else None, torch.empty((P, 7), **f) if want_filtered else None,
+                         torch.empty((P,), dtype=torch.uint8, device=ts.device), torch.empty((B,), dtype=torch.int32, device=ts.device), offsets,
+                         torch.empty((P,), **f) if want_nis else None, torch.empty((P,), **f),
+                         torch.empty((B,), dtype=torch.int32, device=ts.device), torch.empty((B,), **f), given)
+    check(_lib.load().gsf_ekf_smooth_reweighted_dev(context().handle, _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(meas_var), _p(offsets),
+                                                    _p(init_pos), _p(init_quat), _p(run_status), C.byref(cfg), B, _LOSSES[loss], c2, rounds,
+                                                    _p(st.pos), _p(st.quat), _p(st.cov), _p(st.pos_filt), _p(st.cov_filt), _p(st.flags),
+                                                    _p(st.status), _p(st.nis), _p(st.weight), _p(st.rounds_used), _p(st.w_change)))
+    return st
+
+
+def smooth_reweighted_fused(rb, r, fix_var=None, valid=None, loss="huber", c2=None, rounds=5, config=None, skip_seconds=5.0):
+    """ekf_smooth_reweighted_ragged on the result r of run_fusion_ragged for the batch rb, built like smooth_weighted_fused: fix_var (T,3)
+    (None: the config's meas_noise_diag for every fix) is carried onto the SLAM stamps by fix_var_at_poses_ragged through the fixes the
+    pre-filter kept and the mask (r.valid, or valid=: another mask over the same rows, e.g. g.valid(k) of gate_fused).  Returns the
+    ReweightedTrack (with the filter's own track and nis) carrying pose_var (P,3) or None, smoothed_pos (P,3) = the weighted smoother's
+    track before any round (one more launch, rounds = 0), and step 6's nearest-fix error of four tracks against the fixes of the mask:
+    err_stats4 (4,B,4) = {raw SLAM, Sim3, the weighted smoother, the reweighted smoother} x {count, mean, median, RMSE}, errors4 (4,P)
+    (NaN where not evaluated).  The fixes of the mask include the outliers: the figures say how far each track follows them."""
+    ts, aligned, offsets = rb.ts.reshape(-1), r.aligned.reshape(-1, 3), rb.slam_offsets
+    v = (r.valid.reshape(-1) if valid is None else valid).contiguous()
+    pose_var = None if fix_var is None else fix_var_at_poses_ragged(ts, offsets, rb.gps_t, rb.gps_offsets, fix_var, keep=r.gps_keep, valid=v)
+    ip, iq = _fused_init_pose(rb, r)
+    st = ekf_smooth_reweighted_ragged(ts, rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4), aligned, v, offsets, ip, iq, meas_var=pose_var, loss=loss, c2=c2,
+                                      rounds=rounds, config=config, run_status=r.run_status, want_filtered=True, want_nis=True)
+    base = ekf_smooth_reweighted_ragged(ts, rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4), aligned, v, offsets, ip, iq, meas_var=pose_var, loss=loss, c2=c2,
+                                        rounds=0, config=config, run_status=r.run_status)
+    rows = _step6_rows(ts, offsets, (rb.pos.reshape(-1, 3), r.sim3_pos.reshape(-1, 3), base.pos, st.pos), aligned, v, skip_seconds)
+    st.err_stats4, st.errors4 = torch.stack([x[0] for x in rows]), torch.stack([x[1] for x in rows])
+    st.valid, st.init_pos, st.init_quat, st.pose_var, st.smoothed_pos = v, ip, iq, pose_var, base.pos
+    return st
+
+
 # ---------------------------------------------------------------------------- local Sim3 alignment (gsf_sim3_local_fit_dev / _apply_dev)
 _LOCAL_MODES = {"scale": _lib.LOC_SCALE, "sim3": _lib.LOC_SIM3}
 

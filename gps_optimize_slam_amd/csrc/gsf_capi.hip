@@ -11,6 +11,7 @@
 #include "gsf_sweep_core.hpp"
 #include "gsf_outage_core.hpp"
 #include "gsf_gate_core.hpp"
+#include "gsf_reweight_core.hpp"
 
 namespace gsf {
 
@@ -807,6 +808,23 @@ int gsf_ekf_smooth_weighted_dev(gsf_ctx* ctx, const double* ts, const double* po
     GSF_REQUIRE(B <= (int64_t)0x7fffffff, "B too large for one launch");
     return launch_ekf_smooth_weighted(ctx, ts, pos, quat, gps, valid, meas_var, offsets, init_pos, init_quat, run_status, cfg, B, pos_out, quat_out,
                                       cov_out, pos_filt, cov_filt, pose_flags, status, nis);
+}
+
+// robust smoothing: device form only (include/gsf.h).  meas_var may be NULL: cfg's meas_noise_diag on every row
+int gsf_ekf_smooth_reweighted_dev(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                                  const double* meas_var, const int64_t* offsets, const double* init_pos, const double* init_quat,
+                                  const int32_t* run_status, const gsf_ekf_config* cfg, int64_t B, int32_t loss, double c2, int32_t rounds,
+                                  double* pos_out, double* quat_out, double* cov_out, double* pos_filt, double* cov_filt, uint8_t* pose_flags,
+                                  int32_t* status, double* nis, double* weight, int32_t* rounds_used, double* w_change)
+{
+    GSF_REQUIRE(ctx && cfg && offsets, "ctx/cfg/offsets is NULL");
+    GSF_REQUIRE(B >= 0, "negative B");
+    GSF_REQUIRE(gsf::reweight_args_ok(loss, c2, rounds), "loss must be GSF_REWEIGHT_HUBER or _CAUCHY, c2 finite and > 0, rounds in [0, 32]");
+    if (B == 0) return GSF_OK;
+    GSF_REQUIRE(ts && pos && quat && gps && valid && init_pos && init_quat && pos_out && quat_out && cov_out && weight, "NULL array");
+    GSF_REQUIRE(B <= (int64_t)0x7fffffff, "B too large for one launch");
+    return launch_ekf_smooth_reweighted(ctx, ts, pos, quat, gps, valid, meas_var, offsets, init_pos, init_quat, run_status, cfg, B, loss, c2, rounds,
+                                        pos_out, quat_out, cov_out, pos_filt, cov_filt, pose_flags, status, nis, weight, rounds_used, w_change);
 }
 
 int gsf_fix_var_at_poses_dev(gsf_ctx* ctx, const double* ts, const int64_t* slam_offsets, const double* gps_t, const int64_t* gps_offsets,

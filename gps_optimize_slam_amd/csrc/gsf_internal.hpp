@@ -154,7 +154,13 @@ int launch_lever_fit(gsf_ctx* ctx, const double* pos, const double* quat, const 
                      double* rms_before, double* rms_after, double* last_step, int32_t* flags);
 int launch_lever_apply(gsf_ctx* ctx, const double* quat, const double* xyz, const int64_t* offsets, int64_t B, const double* R, const double* l,
                        double sign, double* xyz_out, int32_t* pose_flags);
-// per-fix GNSS noise: the weighted whole-track smoother (gsf_smooth.hip, ekf_smooth_kernel<true>), and per-fix variances carried onto SLAM stamps (gsf_weighted.hip)
+// robust smoothing: the weighted smoother with Huber / Cauchy reweighting rounds in one launch (gsf_smooth.hip, ekf_smooth_kernel<SMOOTH_REWEIGHTED>)
+int launch_ekf_smooth_reweighted(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                                 const double* meas_var, const int64_t* offsets, const double* init_pos, const double* init_quat,
+                                 const int32_t* run_status, const gsf_ekf_config* cfg, int64_t B, int32_t loss, double c2, int32_t rounds,
+                                 double* pos_out, double* quat_out, double* cov_out, double* pos_filt, double* cov_filt, uint8_t* pose_flags,
+                                 int32_t* status, double* nis, double* weight, int32_t* rounds_used, double* w_change);
+// per-fix GNSS noise: the weighted whole-track smoother (gsf_smooth.hip, ekf_smooth_kernel<SMOOTH_WEIGHTED>), and per-fix variances carried onto SLAM stamps (gsf_weighted.hip)
 int launch_ekf_smooth_weighted(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
                                const double* meas_var, const int64_t* offsets, const double* init_pos, const double* init_quat,
                                const int32_t* run_status, const gsf_ekf_config* cfg, int64_t B, double* pos_out, double* quat_out, double* cov_out,

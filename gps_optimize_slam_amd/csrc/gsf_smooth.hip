@@ -1,5 +1,7 @@
 // gsf_smooth.hip -- whole-track RTS smoothing: the fixed-interval smoother over the fused track (gsf_ekf_smooth_ragged_dev) and the same
-// smoother with a measurement variance per pose and axis (gsf_ekf_smooth_weighted_dev).  ONE kernel body, ekf_smooth_kernel<WEIGHTED>.
+// smoother with a measurement variance per pose and axis (gsf_ekf_smooth_weighted_dev), and that smoother made robust by Huber / Cauchy
+// reweighting rounds (gsf_ekf_smooth_reweighted_dev).  ONE kernel body, ekf_smooth_kernel<MODE>: SMOOTH_PLAIN, SMOOTH_WEIGHTED (below:
+// WEIGHTED, which SMOOTH_REWEIGHTED is as well) and SMOOTH_REWEIGHTED (below: REWEIGHT).
 //
 // One wave per track, 64 poses per chunk, lane = pose, two passes over the track; no LDS, no workspace, hence no length limit.
 // PASS 1, ascending, is the shared chunk body of gsf_track_chunk.hpp under cfg's own noise: the rows, dt, the "fix used" flags, the outage
@@ -15,6 +17,20 @@
 //    the gain, the Joseph Pf and g use the row's own r through variance_finish() and sweep_affine() as they stand.
 //  * no axis shares a scan with another: three variance scans and three d scans per chunk, whatever cfg holds (measured: DESIGN.md 7n).
 //  * nis[i] = sum_c y_c^2 / (Pp_c + r_ic) on the rows that took an update, NaN elsewhere.
+// REWEIGHT opens a loop over the SOLVES around both passes (one trip in the other two modes, where it folds away): solve 0 under the
+// given variances, then up to `rounds` solves under r_eff = min(v / w, 1e8) (gsf_reweight_core.hpp), stopped per track at a fixed point
+// of the weights.  meas_var may be NULL there: cfg's R on every row.
+//  * pass 1 of a solve loads weight[i] beside the row's variances, a chunk ahead like them, and forms r_eff for the rows that take an
+//    update; availability is judged on the GIVEN variances, and r_eff of a used row is usable, so every solve sees the same outages,
+//    sharp-turn decisions, spans, flags and quaternions.  Solve 0 runs on w = 1.0: v / 1.0 and the min return v's bits.
+//  * pass 1 parks the RELATIVE filtered position in the track's own pos_out row; pass 2 forms init_pos + xr with pass 1's expression
+//    (the bytes the weighted mode stores) and + e on the rows a later fix reaches, and rewrites every row.
+//  * pass 2 also loads the row's fix and given variances and forms res = (z - init_pos) - (xr + e), u2 and the weight of the NEXT
+//    solve, stores it (NaN on rows without an update), and keeps the ballot "some used weight is not the one its solve used" and the
+//    largest step of a weight.  The stop is wave-uniform.
+//  * row k stays on lane k mod 64 in both passes and all solves: a lane reads back only rows it stored itself, program order is enough
+//    (as for the parked cov_out row).  `weight` is neither restrict nor nontemporal.  The clamped load of an idle lane may touch another
+//    lane's row: `avail` (pass 1) and `used` (pass 2) end it before any operand.
 // PASS 2, descending over the same chunk boundaries, re-reads the parked row, the stamp and the filtered position, forms A from Pf[k], Q
 // and dt[k+1], and runs the e scans and the d scans of include/gsf.h as SUFFIX scans with the carried (e, d, g, Pf, t) of the chunk above.
 // It reads only what pass 1 parked, Q and the stamps: R never enters it.
@@ -29,14 +45,20 @@
 #include "gsf_track_chunk.hpp"
 #include "gsf_smooth_core.hpp"
 #include "gsf_weighted_core.hpp"
+#include "gsf_reweight_core.hpp"
 
 namespace {
+
+enum : int { SMOOTH_PLAIN = 0, SMOOTH_WEIGHTED = 1, SMOOTH_REWEIGHTED = 2 };
 
 struct SmoothArgs {
     const double* ts; const double* pos; const double* quat; const double* gps; const uint8_t* valid; const double* meas_var;   // (WEIGHTED)
     const int64_t* offsets; const int32_t* run_status; const double* init_pos; const double* init_quat;
     double* pos_out; double* quat_out; double* cov_out; double* pos_filt; double* cov_filt; uint8_t* flags; int32_t* status; double* nis;   // (nis: WEIGHTED)
 };
+// (REWEIGHT) what the round loop adds; a parameter of its own BEHIND the others, so that the kernel arguments of the two modes without
+// it lie where they lay and their code is the same instruction for instruction.  meas_var may be NULL in that mode: cfg's R on every row
+struct ReweightArgs { double* weight; int32_t* rounds_used; double* w_change; double c2; int32_t loss, rounds; };
 
 // (WEIGHTED) a row's three variances, clamped like the chunk's rows
 __device__ __forceinline__ void load_row_var(const double* __restrict__ mvb, const int64_t row, const int64_t N, double& v0, double& v1, double& v2)
@@ -45,14 +67,24 @@ __device__ __forceinline__ void load_row_var(const double* __restrict__ mvb, con
     v0 = __builtin_nontemporal_load(&mvb[il * 3]); v1 = __builtin_nontemporal_load(&mvb[il * 3 + 1]); v2 = __builtin_nontemporal_load(&mvb[il * 3 + 2]);
 }
 
-template <bool WEIGHTED>
-__global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, const EkfConfig cfg)
+// (REWEIGHT) ... or, without an array, cfg's R: a wave-uniform choice
+template <bool REWEIGHT>
+__device__ __forceinline__ void row_var(const double* __restrict__ mvb, const EkfConfig& cfg, const int64_t row, const int64_t N, double& v0, double& v1, double& v2)
 {
+    if (REWEIGHT && !mvb) { v0 = cfg.Rm[0]; v1 = cfg.Rm[1]; v2 = cfg.Rm[2]; }
+    else load_row_var(mvb, row, N, v0, v1, v2);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, const EkfConfig cfg, const ReweightArgs rw)
+{
+    constexpr bool WEIGHTED = MODE != SMOOTH_PLAIN, REWEIGHT = MODE == SMOOTH_REWEIGHTED;
     const int lane = (int)threadIdx.x;
     const int64_t b = blockIdx.x;
     const int64_t base = uniform64(a.offsets[b]), N = uniform64(a.offsets[b + 1]) - base;
     if (N <= 0) {                                                         // an empty track (ref :835): no rows
         if (lane == 0 && a.status) a.status[b] = 0;
+        if constexpr (REWEIGHT) if (lane == 0) { if (rw.rounds_used) rw.rounds_used[b] = 0; if (rw.w_change) rw.w_change[b] = 0.0; }
         return;
     }
     double* pob = a.pos_out + base * 3;
@@ -62,13 +94,15 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
     double* cfb = a.cov_filt ? a.cov_filt + base * 7 : nullptr;
     uint8_t* flb = a.flags ? a.flags + base : nullptr;
     double* nib = (WEIGHTED && a.nis) ? a.nis + base : nullptr;
+    double* wtb = REWEIGHT ? rw.weight + base : nullptr;                   // neither restrict nor nontemporal: the rounds' own store, read back by the lane that wrote
     if (a.run_status && a.run_status[b] != 0) {                           // the run stopped before the filter: NaN rows, no flags, inputs not read
         const double nan = __builtin_nan("");
         for (int64_t k = lane; k < N * 7; k += 64) { cob[k] = nan; if (cfb) cfb[k] = nan; }
         for (int64_t k = lane; k < N * 4; k += 64) qob[k] = nan;
         for (int64_t k = lane; k < N * 3; k += 64) { pob[k] = nan; if (pfb) pfb[k] = nan; }
-        for (int64_t k = lane; k < N; k += 64) { if (flb) flb[k] = 0; if (nib) nib[k] = nan; }
+        for (int64_t k = lane; k < N; k += 64) { if (flb) flb[k] = 0; if (nib) nib[k] = nan; if constexpr (REWEIGHT) wtb[k] = nan; }
         if (lane == 0 && a.status) a.status[b] = 0;
+        if constexpr (REWEIGHT) if (lane == 0) { if (rw.rounds_used) rw.rounds_used[b] = 0; if (rw.w_change) rw.w_change[b] = 0.0; }
         return;
     }
     const double* __restrict__ tsb = a.ts + base;
@@ -76,10 +110,16 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
     const double* __restrict__ quatb = a.quat + base * 4;
     const double* __restrict__ gpsb = a.gps + base * 3;
     const uint8_t* __restrict__ valb = a.valid + base;
-    const double* __restrict__ mvb = WEIGHTED ? a.meas_var + base * 3 : nullptr;
+    const double* __restrict__ mvb = (WEIGHTED && (!REWEIGHT || a.meas_var)) ? a.meas_var + base * 3 : nullptr;
+
+    // the solves: ONE without REWEIGHT (the loop folds away); with it solve 0 under the given variances, then up to rw.rounds more under
+    // r_eff = min(v / w, 1e8) with the weights the pass 2 before left in `weight` (gsf_reweight_core.hpp).  s is wave-uniform.
+    for (int32_t s = 0;; ++s) {
     ChunkIn nxt = load_chunk(tsb, posb, quatb, gpsb, valb, lane, N);
     double mv_nxt[3] = { 1.0, 1.0, 1.0 };
-    if constexpr (WEIGHTED) load_row_var(mvb, (int64_t)lane, N, mv_nxt[0], mv_nxt[1], mv_nxt[2]);
+    if constexpr (WEIGHTED) row_var<REWEIGHT>(mvb, cfg, (int64_t)lane, N, mv_nxt[0], mv_nxt[1], mv_nxt[2]);
+    double wt_nxt = 1.0;                                                  // (REWEIGHT) the row's weight; solve 0 runs on 1.0
+    if constexpr (REWEIGHT) if (s > 0) wt_nxt = wtb[lane < N ? lane : N - 1];
 
     int same1 = -1, same2 = -1;                                           // WEIGHTED: no axis shares a scan, and the branches on them fold away
     if constexpr (!WEIGHTED) same_axes(cfg.P0, cfg.Qps, cfg.Rm, same1, same2);
@@ -97,8 +137,10 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
         for (int64_t c0 = 0; c0 < N; c0 += 64) {
             const ChunkIn in = nxt;
             const double mv[3] = { mv_nxt[0], mv_nxt[1], mv_nxt[2] };
+            const double wt = wt_nxt;
             nxt = load_chunk(tsb, posb, quatb, gpsb, valb, c0 + 64 + lane, N);   // the next chunk's rows are requested before this chunk's scans (clamped past the end)
-            if constexpr (WEIGHTED) load_row_var(mvb, c0 + 64 + lane, N, mv_nxt[0], mv_nxt[1], mv_nxt[2]);
+            if constexpr (WEIGHTED) row_var<REWEIGHT>(mvb, cfg, c0 + 64 + lane, N, mv_nxt[0], mv_nxt[1], mv_nxt[2]);
+            if constexpr (REWEIGHT) if (s > 0) { const int64_t in_ = c0 + 64 + lane; wt_nxt = wtb[in_ < N ? in_ : N - 1]; }
             const ChunkFront f = chunk_front(in, tc, c_ok, c0, N, lane);
             const int64_t i = f.i;
             const bool active = f.active, stepping = f.stepping;
@@ -149,7 +191,13 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
             double rr[3] = { cfg.Rm[0], cfg.Rm[1], cfg.Rm[2] };
             if constexpr (WEIGHTED) {
                 // a row that takes no update carries r = 1: nothing of what its meas_var holds reaches an operand
-                rr[0] = avail ? mv[0] : 1.0; rr[1] = avail ? mv[1] : 1.0; rr[2] = avail ? mv[2] : 1.0;
+                // (REWEIGHT: the effective variance, formed for the rows that take an update; wt = 1.0 returns mv's bits.  An idle lane's
+                // clamped wt may be another lane's row, old or new: it ends here)
+                if constexpr (REWEIGHT) {
+                    rr[0] = avail ? reweight_var(mv[0], wt) : 1.0; rr[1] = avail ? reweight_var(mv[1], wt) : 1.0; rr[2] = avail ? reweight_var(mv[2], wt) : 1.0;
+                } else {
+                    rr[0] = avail ? mv[0] : 1.0; rr[1] = avail ? mv[1] : 1.0; rr[2] = avail ? mv[2] : 1.0;
+                }
                 v0 = variance_axis<6, true>(cfg.Qps[0], rr[0], f.dt, stepping, avail, cP[0]);
                 v1 = variance_axis<6, true>(cfg.Qps[1], rr[1], f.dt, stepping, avail, cP[1]);
                 v2 = variance_axis<6, true>(cfg.Qps[2], rr[2], f.dt, stepping, avail, cP[2]);
@@ -181,9 +229,12 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
             // ---- this chunk's rows.  pos_out, the parked cov_out row and the flags are read again by pass 2: plain stores
             chunk_arrived(nxt);
             if constexpr (WEIGHTED) asm volatile("" :: "v"(mv_nxt[0]), "v"(mv_nxt[1]), "v"(mv_nxt[2]) : "memory");
+            if constexpr (REWEIGHT) asm volatile("" :: "v"(wt_nxt) : "memory");
             if (active) {
                 const double xf[3] = { tc.p0.x + x[0], tc.p0.y + x[1], tc.p0.z + x[2] };
-                pob[i * 3] = xf[0]; pob[i * 3 + 1] = xf[1]; pob[i * 3 + 2] = xf[2];
+                // (REWEIGHT parks the RELATIVE position: pass 2 forms the residual from it and p0 + x with the expression above)
+                if constexpr (REWEIGHT) { pob[i * 3] = x[0]; pob[i * 3 + 1] = x[1]; pob[i * 3 + 2] = x[2]; }
+                else { pob[i * 3] = xf[0]; pob[i * 3 + 1] = xf[1]; pob[i * 3 + 2] = xf[2]; }
                 __builtin_nontemporal_store(qi.x, &qob[i * 4]); __builtin_nontemporal_store(qi.y, &qob[i * 4 + 1]);
                 __builtin_nontemporal_store(qi.z, &qob[i * 4 + 2]); __builtin_nontemporal_store(qi.w, &qob[i * 4 + 3]);
                 cob[i * 7] = smooth_tag(Pf[0], avail); cob[i * 7 + 1] = Pf[1]; cob[i * 7 + 2] = Pf[2];
@@ -209,6 +260,10 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
         double c_e[3] = { 0.0, 0.0, 0.0 }, c_d[3] = { 0.0, 0.0, 0.0 }, c_g[3] = { 0.0, 0.0, 0.0 }, c_Pf[3] = { 0.0, 0.0, 0.0 };
         double c_t = 0.0;
         bool c_fix = false, c_start = true, c_reach = false, any_reached = false;
+        // (REWEIGHT) init_pos again, "some used row's weight is not the one its solve used", and the largest step of a weight
+        double p0[3] = { 0.0, 0.0, 0.0 }, w_step = 0.0;
+        u64 changed_m = 0ull;
+        if constexpr (REWEIGHT) { p0[0] = a.init_pos[b * 3]; p0[1] = a.init_pos[b * 3 + 1]; p0[2] = a.init_pos[b * 3 + 2]; }
         for (int64_t c0 = ((N - 1) >> 6) << 6; c0 >= 0; c0 -= 64) {
             const int64_t kr = c0 + 63 - lane;                            // the row of this SCAN lane
             const int64_t io = c0 + lane;                                  // the row this lane loads and stores: one it stored itself in pass 1
@@ -222,6 +277,14 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
             const double t_io = tsb[il];
             uint32_t fl_io = 0u;
             if (flb) fl_io = flb[il];
+            // (REWEIGHT) the row's fix, its given variances and the weight its solve used (this lane's own store; solve 0: 1.0)
+            double z_io[3] = { 0.0, 0.0, 0.0 }, v_io[3] = { 1.0, 1.0, 1.0 }, w_used = 1.0;
+            if constexpr (REWEIGHT) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) z_io[c] = gpsb[il * 3 + c];
+                row_var<true>(mvb, cfg, io, N, v_io[0], v_io[1], v_io[2]);
+                if (s > 0) w_used = wtb[il];
+            }
             const double S = smooth_untag(w[6]);
             const double Pf_io[3] = { smooth_untag(w[0]), w[1], w[2] };
             // ---- into scan order: scan lane j holds row c0 + 63 - j, so the row after is the lane before
@@ -280,14 +343,45 @@ __global__ __launch_bounds__(64) void ekf_smooth_kernel(const SmoothArgs a, cons
                 }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) cob[io * 7 + 3 + c] = quat_axis_var(cfg, c, S);
-                if (reached_io) {
+                if constexpr (REWEIGHT) {                                 // the parked row is relative: every row is rewritten
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const double xa = p0[c] + xf[c];                  // pass 1's xf
+                        const double xs = xa + e_io[c];
+                        pob[io * 3 + c] = reached_io ? xs : xa;
+                    }
+                    if (reached_io && flb) flb[io] = (uint8_t)(fl_io | POSE_SMOOTHED);
+                } else if (reached_io) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) pob[io * 3 + c] = xf[c] + e_io[c];
                     if (flb) flb[io] = (uint8_t)(fl_io | POSE_SMOOTHED);
                 }
             }
+            if constexpr (REWEIGHT) {
+                // ---- the weights of the next solve fall out here: the residual of every used row against the smoothed track (e_io is 0
+                // on a row no later fix reaches), relative to init_pos.  Idle lanes hold whatever their clamped loads gave: `used` ends it.
+                const bool used = act_io && smooth_tag_of(w[0]);
+                double res[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { const double zr = z_io[c] - p0[c]; res[c] = reweight_residual(zr, xf[c], e_io[c]); }
+                const double u2 = reweight_u2(res[0], res[1], res[2], v_io[0], v_io[1], v_io[2]);
+                const double w_new = reweight_weight(rw.loss, u2, rw.c2);
+                changed_m |= __ballot(used && !reweight_same_bits(w_new, w_used));
+                w_step = fmax(w_step, used ? fabs(w_new - w_used) : 0.0);
+                if (act_io) wtb[io] = used ? w_new : __builtin_nan("");
+            }
         }
         if (lane == 0 && a.status) a.status[b] = status | (any_reached ? ST_RTS_APPLIED : 0);
+        if constexpr (REWEIGHT) {
+            // stop after rw.rounds reweighted solves, or at a fixed point: the next solve would run on the same bytes (wave-uniform)
+            if (s >= rw.rounds || changed_m == 0ull) {
+                for (int off = 32; off > 0; off >>= 1) w_step = fmax(w_step, __shfl_xor(w_step, off, 64));
+                if (lane == 0) { if (rw.rounds_used) rw.rounds_used[b] = s; if (rw.w_change) rw.w_change[b] = w_step; }
+                break;
+            }
+        }
+    }
+    if constexpr (!REWEIGHT) break;
     }
 }
 
@@ -307,7 +401,7 @@ extern "C" int gsf_ekf_smooth_ragged_dev(gsf_ctx* ctx, const double* ts, const d
     const EkfConfig k = to_core(cfg);
     const SmoothArgs a{ ts, pos, quat, gps, valid, nullptr, offsets, run_status, init_pos, init_quat, pos_out, quat_out, cov_out, pos_filt, cov_filt,
                         pose_flags, status, nullptr };
-    hipLaunchKernelGGL(ekf_smooth_kernel<false>, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, k);
+    hipLaunchKernelGGL(ekf_smooth_kernel<SMOOTH_PLAIN>, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, k, ReweightArgs{});
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }
@@ -323,7 +417,24 @@ int launch_ekf_smooth_weighted(gsf_ctx* ctx, const double* ts, const double* pos
     const EkfConfig k = to_core(cfg);
     const SmoothArgs a{ ts, pos, quat, gps, valid, meas_var, offsets, run_status, init_pos, init_quat, pos_out, quat_out, cov_out, pos_filt,
                         cov_filt, pose_flags, status, nis };
-    hipLaunchKernelGGL(ekf_smooth_kernel<true>, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, k);
+    hipLaunchKernelGGL(ekf_smooth_kernel<SMOOTH_WEIGHTED>, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, k, ReweightArgs{});
+    GSF_HIP(hipGetLastError());
+    return GSF_OK;
+}
+
+// robust smoothing: the same kernel with its round loop open (arguments checked by the entry, gsf_capi.hip)
+int launch_ekf_smooth_reweighted(gsf_ctx* ctx, const double* ts, const double* pos, const double* quat, const double* gps, const uint8_t* valid,
+                                 const double* meas_var, const int64_t* offsets, const double* init_pos, const double* init_quat,
+                                 const int32_t* run_status, const gsf_ekf_config* cfg, int64_t B, int32_t loss, double c2, int32_t rounds,
+                                 double* pos_out, double* quat_out, double* cov_out, double* pos_filt, double* cov_filt, uint8_t* pose_flags,
+                                 int32_t* status, double* nis, double* weight, int32_t* rounds_used, double* w_change)
+{
+    GSF_HIP(hipSetDevice(ctx->device));
+    const EkfConfig k = to_core(cfg);
+    const SmoothArgs a{ ts, pos, quat, gps, valid, meas_var, offsets, run_status, init_pos, init_quat, pos_out, quat_out, cov_out, pos_filt,
+                        cov_filt, pose_flags, status, nis };
+    const ReweightArgs rw{ weight, rounds_used, w_change, c2, loss, rounds };
+    hipLaunchKernelGGL(ekf_smooth_kernel<SMOOTH_REWEIGHTED>, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, k, rw);
     GSF_HIP(hipGetLastError());
     return GSF_OK;
 }

@@ -1,5 +1,6 @@
 // gsf_weighted.hip -- per-fix GNSS noise: the kernel that carries per-fix variances onto SLAM stamps (gsf_fix_var_at_poses_dev).  The
-// filter and smoother that take them, gsf_ekf_smooth_weighted_dev, are ekf_smooth_kernel<true> of gsf_smooth.hip.
+// filter and smoother that take them, gsf_ekf_smooth_weighted_dev and gsf_ekf_smooth_reweighted_dev, are ekf_smooth_kernel<SMOOTH_WEIGHTED>
+// and <SMOOTH_REWEIGHTED> of gsf_smooth.hip, launched from there: the kernel lives in that unit.
 #include "gsf_wave_common.hpp"
 #include "gsf_weighted_core.hpp"
 

@@ -1,4 +1,4 @@
-// gsf_weighted_core.hpp -- per-fix measurement noise (gsf_ekf_smooth_weighted_dev, gsf_fix_var_at_poses_dev): the rules of ekf_smooth_kernel<true> (gsf_smooth.hip) and gsf_weighted.hip
+// gsf_weighted_core.hpp -- per-fix measurement noise (gsf_ekf_smooth_weighted_dev, gsf_fix_var_at_poses_dev): the rules of ekf_smooth_kernel<SMOOTH_WEIGHTED> (gsf_smooth.hip) and gsf_weighted.hip
 // that are plain host/device C++ (definitions: include/gsf.h, "per-fix GNSS noise").
 //
 //  * which variance is usable, what a row's three variances make of the row (usable / bad / "no information"), and the row's availability:

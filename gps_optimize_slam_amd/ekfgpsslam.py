@@ -534,6 +534,28 @@ def ekf_smooth_aligned_weighted(timestamps, positions, quaternions, aligned_gps,
             "status": int(r.status[0].item()), "nis": h(r.nis)}
 
 
+def ekf_smooth_aligned_reweighted(timestamps, positions, quaternions, aligned_gps, valid_mask, init_pos, init_quat, meas_var=None, loss="huber",
+                                  c2=None, rounds=5, global_config=None):
+    """ekf_smooth_aligned_weighted made robust: Huber / Cauchy reweighting rounds in one launch (gsf_ekf_smooth_reweighted_dev; definition:
+    include/gsf.h).  meas_var (n,3) or None (the config's meas_noise_diag on every row); loss 'huber' or 'cauchy'; c2 a chi-square
+    threshold of 3 degrees of freedom (None: the 95 % quantile, 7.81); rounds 0..32.  Host arrays -> ekf_smooth_aligned_weighted's dict
+    of the last solve plus 'weight' (n,) (NaN on rows without an update), 'rounds_used' and 'w_change'."""
+    import torch
+    from . import batch as gb
+    ts = f64(timestamps).ravel()
+    n = ts.size
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a, shape, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).reshape(shape)).to(dev)
+    r = gb.ekf_smooth_reweighted_ragged(up(ts, (n,)), up(positions, (n, 3)), up(quaternions, (n, 4)), up(aligned_gps, (n, 3)),
+                                        up(valid_mask, (n,), np.uint8), torch.tensor([0, n], dtype=torch.int64, device=dev), up(init_pos, (1, 3)),
+                                        up(init_quat, (1, 4)), meas_var=None if meas_var is None else up(meas_var, (n, 3)), loss=loss, c2=c2,
+                                        rounds=rounds, config=global_config, want_filtered=True, want_nis=True)
+    h = lambda t: t.cpu().numpy()
+    return {"pos": h(r.pos), "quat": h(r.quat), "cov": h(r.cov), "pos_filt": h(r.pos_filt), "cov_filt": h(r.cov_filt), "flags": h(r.flags),
+            "status": int(r.status[0].item()), "nis": h(r.nis), "weight": h(r.weight), "rounds_used": int(r.rounds_used[0].item()),
+            "w_change": float(r.w_change[0].item())}
+
+
 def smooth_trajectory(slam_data_in, gps_data_in, sim3_pos_initial, sim3_quat_initial, global_config):
     """apply_ekf_correction's arguments, the whole-track smoother's result: the same alignment call (ref :847), the initial pose = row 0 of
     the Sim3-transformed track, then ekf_smooth_aligned.  Returns its dict; an empty track gives empty arrays (ref :835)."""

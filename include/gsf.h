@@ -662,6 +662,43 @@ GSF_API int gsf_ekf_smooth_weighted_dev(gsf_ctx *ctx, const double *ts, const do
                                         const double *init_quat, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
                                         double *pos_out, double *quat_out, double *cov_out, double *pos_filt, double *cov_filt,
                                         uint8_t *pose_flags, int32_t *status, double *nis);
+/* ---- robust smoothing: Huber / Cauchy reweighting rounds of the weighted smoother, in one launch --------------------------------------------
+   gsf_ekf_smooth_weighted_dev is a least-squares estimator: a multipath fix 25 m off pulls the smoothed track with the full weight of its
+   stated variance.  The RANSAC pre-filter works on the log before alignment; the innovation gate is causal, all-or-nothing, and keeps one
+   R per run.  This entry is the M-estimator a smoother takes, solved by iteratively reweighted least squares: every round smooths the
+   track, forms each used fix's residual against the SMOOTHED track (which has seen the fixes on both sides), turns it into a weight and
+   inflates that fix's variance by 1 / weight.  One kernel: the weight of the next round falls out of the backward pass.
+   Solve 0 -- gsf_ekf_smooth_weighted_dev on meas_var[P][3].  meas_var may be NULL here: cfg's meas_noise_diag on every row.
+   Residual -- after a solve, on every GSF_POSE_GNSS_USED row: res_c = (z_c - init_pos_c) - (xr_c + e_c), xr = the filtered position relative
+   to init_pos, e = the smoother's correction (0 where no later fix reaches the row); u2 = sum_c res_c^2 / meas_var_ic with the GIVEN
+   variance, not the inflated one.  Relative to init_pos: formed from UTM positions the residual would carry 1e-9 m of rounding.
+   Weight -- loss GSF_REWEIGHT_HUBER: w = 1 for u2 <= c2, else sqrt(c2 / u2); GSF_REWEIGHT_CAUCHY: w = 1 / (1 + u2 / c2).  Both are
+   continuous in u2.  c2 is a threshold on a chi-square of 3 degrees of freedom (7.81: 95 %).  weight[i] is NaN on rows without an update.
+   Effective variance -- the next solve runs with r_eff_ic = min(meas_var_ic / w_i, 1e8): inside the usable range whatever w is (w = 0, from
+   u2 = inf, gives 1e8), so availability is judged on the GIVEN variances once, and outages, sharp-turn decisions, spans, flags, status and
+   quaternions are the same in every solve.
+   Stop -- after `rounds` reweighted solves (0 <= rounds <= 32), or for a track as soon as every weight just computed equals, bit for bit,
+   the weight its solve used (solve 0 used 1.0 everywhere): the next solve would reproduce the same bytes.  rounds_used[B] (may be NULL) =
+   the reweighted solves done; w_change[B] (may be NULL) = max |w_new - w_used| over the used rows of the last solve, 0 at a fixed point
+   and on a track without a used row.
+   Out -- everything gsf_ekf_smooth_weighted_dev returns (nis included) is of the LAST solve, under its effective variances.  weight[P]
+   (required) is the rounds' own store and holds, on return, the weights computed from the last solve's track; its incoming bytes are
+   not read.  Two laws: (A) rounds = 0 returns gsf_ekf_smooth_weighted_dev's bytes on every shared output (with meas_var NULL: those of
+   that entry fed cfg's meas_noise_diag on every row); (B) rounds = R returns the bytes of gsf_ekf_smooth_weighted_dev fed
+   min(meas_var / w, 1e8) on the rows where w is a number and meas_var elsewhere, w = the weight output of the call with rounds = R - 1.
+   run_status[b] != 0: NaN rows (weight included), rounds_used 0, w_change 0.  An empty track has no rows, status 0, rounds_used 0,
+   w_change 0.  c2 not finite or <= 0, another loss, rounds outside [0, 32]: GSF_ERR_INVALID_ARG.  Everything else as
+   gsf_ekf_smooth_weighted_dev.  One wave per track, two passes per solve (between them the track's own pos_out row holds the filtered
+   position relative to init_pos), no workspace, any track length.  Device pointers, asynchronous on the context's stream; there is no
+   host-pointer form. */
+#define GSF_REWEIGHT_HUBER 0
+#define GSF_REWEIGHT_CAUCHY 1
+GSF_API int gsf_ekf_smooth_reweighted_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const double *gps,
+                                          const uint8_t *valid, const double *meas_var, const int64_t *offsets, const double *init_pos,
+                                          const double *init_quat, const int32_t *run_status, const gsf_ekf_config *cfg, int64_t B,
+                                          int32_t loss, double c2, int32_t rounds, double *pos_out, double *quat_out, double *cov_out,
+                                          double *pos_filt, double *cov_filt, uint8_t *pose_flags, int32_t *status, double *nis,
+                                          double *weight, int32_t *rounds_used, double *w_change);
 /* Per-fix variances carried onto SLAM stamps: pose_var[P][3] for gsf_ekf_smooth_weighted_dev from fix_var[T][3] of the GNSS logs.
    In: ts[P] with slam_offsets int64[B+1]; gps_t[T] with gps_offsets int64[B+1] (ascending stamps per log); gps_keep[T] = the pre-filter's
    mask (NULL: every fix kept); fix_var[T][3]; valid[P] (may be NULL).  For pose i of track b:
