@@ -110,6 +110,7 @@ LEVER_KEPT = LEVER_FEW | LEVER_VAR0 | LEVER_SINGULAR | LEVER_SCALE | LEVER_TRACK
 LVP_BAD_QUAT = 1                                                # pose_flags bit of gsf_lever_apply_dev
 STREAM_F64, STREAM_I64, STREAM_LAYOUT_VERSION = 22, 6, 1      # state sizes per track and layout version of the streaming fusion (gsf_stream_*)
 STREAM_FULL, STREAM_BAD_STATE = 256, 512                        # ... and its status bits, beside the ST_* ones
+STREAM_LAG_MAX, STREAM_LAG_F64 = 512, 12                        # the largest lag of gsf_stream_append_lag_dev and the doubles of a ring_lag row
 CLK_NONE, CLK_AT_EDGE, CLK_FLAT = 1, 2, 4                       # clk_status bits of gsf_clock_offset_search_dev
 QT_EMPTY, QT_UNSORTED, QT_SKIPPED, QT_BAD_EXTRINSIC = 1, 2, 4, 8    # track_state bits of gsf_pose_query_dev / gsf_georef_points_dev
 Q_EXACT, Q_BEFORE, Q_AFTER, Q_GAP, Q_NAN, Q_TRACK, Q_BAD_QUAT = 1, 2, 4, 8, 16, 32, 64      # ... and their q_flags bits
@@ -209,6 +210,7 @@ SIGNATURES = {
     "gsf_stream_open_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 5),
     "gsf_stream_append_dev": (C.c_int, [_vp, C.POINTER(EkfConfig), _i64, _i64] + [_vp] * 18),
     "gsf_stream_gather_dev": (C.c_int, [_vp, _i64, _i64] + [_vp] * 9),
+    "gsf_stream_append_lag_dev": (C.c_int, [_vp, C.POINTER(EkfConfig), _i64, _i64, _i64] + [_vp] * 26),
     "gsf_pose_query_dev": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 6),
     "gsf_pose_query": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 6),
     "gsf_georef_points_dev": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 9),

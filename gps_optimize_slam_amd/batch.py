@@ -2177,11 +2177,18 @@ class StreamStep:
     """What FusionStream.append returns: pos (P,3) / quat (P,4) = the fused rows of this call's segments as they stand when the call ends,
     cov (P,7) = the filtered covariance diagonal after each pose; n_total (B,) int64 = poses each track holds; n_final (B,): rows
     [0, n_final) will never be written again; revised_from (B,) = the smallest global index this call wrote; status (B,) int32 = the
-    accumulated _lib.ST_* bits as of now | _lib.STREAM_FULL (this segment was refused: NaN rows, track untouched) | _lib.STREAM_BAD_STATE."""
-    __slots__ = ("pos", "quat", "cov", "n_total", "n_final", "revised_from", "status")
+    accumulated _lib.ST_* bits as of now | _lib.STREAM_FULL (this segment was refused: NaN rows, track untouched) | _lib.STREAM_BAD_STATE.
+    A stream with a lag also fills pos_smooth (P,3) / var_smooth (P,3) / flags_smooth (P,) uint8 = the smoothed rows that BECAME FINAL in
+    this call, in the segments' ragged shape: row j of track b's segment is final row smooth_from[b] + j, the rest of the segment's rows
+    are NaN (flags 0); flags = _lib.POSE_SMOOTHED | _lib.POSE_SPAN_START; smooth_from / n_smooth_final (B,) int64 = the number of final
+    smoothed rows before and after the call.  Without a lag the five are None.  Iteration yields the first seven fields only."""
+    __slots__ = ("pos", "quat", "cov", "n_total", "n_final", "revised_from", "status", "pos_smooth", "var_smooth", "flags_smooth", "smooth_from",
+                 "n_smooth_final")
 
-    def __init__(self, pos, quat, cov, n_total, n_final, revised_from, status):
+    def __init__(self, pos, quat, cov, n_total, n_final, revised_from, status, pos_smooth=None, var_smooth=None, flags_smooth=None, smooth_from=None,
+                 n_smooth_final=None):
         self.pos, self.quat, self.cov, self.n_total, self.n_final, self.revised_from, self.status = pos, quat, cov, n_total, n_final, revised_from, status
+        self.pos_smooth, self.var_smooth, self.flags_smooth, self.smooth_from, self.n_smooth_final = pos_smooth, var_smooth, flags_smooth, smooth_from, n_smooth_final
 
     def __iter__(self):
         return iter((self.pos, self.quat, self.cov, self.n_total, self.n_final, self.revised_from, self.status))
@@ -2200,10 +2207,18 @@ class FusionStream:
     they are at ekf_fuse_ragged: the Sim3-transformed pose 0.  How a track is cut into appends does not change one bit of any output.
     Capacity: a track whose open outage plus new segment exceeds `cap` rows is refused (StreamStep.status & _lib.STREAM_FULL) and left
     untouched; give the stream a larger cap, append shorter segments, or reopen() that track.  Every call is one launch on torch's current
-    stream."""
+    stream.
+    lag = L (1 .. _lib.STREAM_LAG_MAX) adds a fixed-lag RTS smoother: every row is also smoothed with the fixes of the next L rows of its
+    span (gsf_stream_append_lag_dev); row i is final once the track holds i + L + 1 poses, the rows above are provisional -- the whole-track
+    smoother's answer on what has arrived -- and rewritten by every append.  The stream then owns three more rings (ring_lag, ring_spos,
+    ring_svar), an append is two launches and also refuses a track with min(L, n_total) + segment length > cap; everything else an append
+    returns is what it returns without a lag, bit for bit."""
 
-    def __init__(self, B, cap, init_pos, init_quat, config=None, device="cuda"):
+    def __init__(self, B, cap, init_pos, init_quat, config=None, device="cuda", lag=None):
         self.B, self.cap = _stream_sizes_chk(B, cap)
+        self.lag = None if lag is None else int(lag)
+        if self.lag is not None and not 1 <= self.lag <= _lib.STREAM_LAG_MAX:
+            raise ValueError(f"FusionStream: lag in 1 .. {_lib.STREAM_LAG_MAX} expected, got {lag}")
         self.config = config or CONFIG
         self._cfg = EkfConfig.from_config(self.config)
         dev = torch.device(device)
@@ -2211,6 +2226,9 @@ class FusionStream:
         self.state_f64 = torch.empty((_lib.STREAM_F64, self.B), **f)
         self.state_i64 = torch.empty((_lib.STREAM_I64, self.B), dtype=torch.int64, device=dev)
         self.ring_t, self.ring_pos, self.ring_quat = torch.empty((self.B, self.cap), **f), torch.empty((self.B, self.cap, 3), **f), torch.empty((self.B, self.cap, 4), **f)
+        if self.lag is not None:
+            self.ring_lag = torch.empty((self.B, self.cap, _lib.STREAM_LAG_F64), **f)
+            self.ring_spos, self.ring_svar = torch.empty((self.B, self.cap, 3), **f), torch.empty((self.B, self.cap, 3), **f)
         if init_pos is not None:
             self.reopen(None, init_pos, init_quat)
 
@@ -2243,6 +2261,15 @@ class FusionStream:
         i = dict(dtype=torch.int64, device=dev)
         s = StreamStep(torch.empty((P, 3), **f), torch.empty((P, 4), **f), torch.empty((P, 7), **f) if want_cov else None, torch.empty((B,), **i),
                        torch.empty((B,), **i), torch.empty((B,), **i), torch.empty((B,), dtype=torch.int32, device=dev))
+        if self.lag is not None:
+            s.pos_smooth, s.var_smooth, s.flags_smooth = torch.empty((P, 3), **f), torch.empty((P, 3), **f), torch.empty((P,), dtype=torch.uint8, device=dev)
+            s.smooth_from, s.n_smooth_final = torch.empty((B,), **i), torch.empty((B,), **i)
+            check(_lib.load().gsf_stream_append_lag_dev(context(dev).handle, C.byref(self._cfg), B, self.cap, self.lag, _p(self.state_f64), _p(self.state_i64),
+                                                        _p(self.ring_t), _p(self.ring_pos), _p(self.ring_quat), _p(self.ring_lag), _p(self.ring_spos),
+                                                        _p(self.ring_svar), _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(seg_offsets), _p(s.pos),
+                                                        _p(s.quat), _p(s.cov), _p(s.n_total), _p(s.n_final), _p(s.revised_from), _p(s.status),
+                                                        _p(s.pos_smooth), _p(s.var_smooth), _p(s.flags_smooth), _p(s.smooth_from), _p(s.n_smooth_final)))
+            return s
         check(_lib.load().gsf_stream_append_dev(context(dev).handle, C.byref(self._cfg), B, self.cap, _p(self.state_f64), _p(self.state_i64), _p(self.ring_t),
                                                 _p(self.ring_pos), _p(self.ring_quat), _p(ts), _p(pos), _p(quat), _p(gps), _p(valid), _p(seg_offsets),
                                                 _p(s.pos), _p(s.quat), _p(s.cov), _p(s.n_total), _p(s.n_final), _p(s.revised_from), _p(s.status)))
@@ -2251,6 +2278,19 @@ class FusionStream:
     def rows(self, lo, counts):
         """rows [lo[b], lo[b] + counts[b]) of every track from the ring: ts (P,), pos (P,3), quat (P,4), out_offsets (B+1,); a row the ring
         no longer holds (or does not hold yet) is NaN.  lo / counts: (B,) int64 tensors or sequences (sequences cost no device read)."""
+        t, p, q, off = self._gather(lo, counts, self.ring_pos, True)
+        return t, p, q, off
+
+    def rows_smoothed(self, lo, counts):
+        """the same rows of the smoothed rings of a stream with a lag: ts (P,), pos (P,3), var (P,3), out_offsets (B+1,) -- final below
+        n_smooth_final, provisional above (two gathers: the variances' ring has the positions' layout)"""
+        if self.lag is None:
+            raise ValueError("FusionStream.rows_smoothed: the stream was opened without a lag")
+        t, p, _, off = self._gather(lo, counts, self.ring_spos, False)
+        _, v, _, _ = self._gather(lo, counts, self.ring_svar, False)
+        return t, p, v, off
+
+    def _gather(self, lo, counts, ring_pos, want_quat):
         dev = self.device
         host_counts = not torch.is_tensor(counts)
         lo = torch.as_tensor(lo, dtype=torch.int64).to(dev).contiguous()
@@ -2265,8 +2305,8 @@ class FusionStream:
         P = int(off_h[-1])
         off = off_h.to(dev)
         f = dict(dtype=torch.float64, device=dev)
-        t, p, q = torch.empty((P,), **f), torch.empty((P, 3), **f), torch.empty((P, 4), **f)
-        check(_lib.load().gsf_stream_gather_dev(context(dev).handle, self.B, self.cap, _p(self.state_i64), _p(self.ring_t), _p(self.ring_pos),
+        t, p, q = torch.empty((P,), **f), torch.empty((P, 3), **f), torch.empty((P, 4), **f) if want_quat else None
+        check(_lib.load().gsf_stream_gather_dev(context(dev).handle, self.B, self.cap, _p(self.state_i64), _p(self.ring_t), _p(ring_pos),
                                                 _p(self.ring_quat), _p(lo), _p(off), _p(t), _p(p), _p(q)))
         return t, p, q, off
 
@@ -2276,8 +2316,11 @@ class FusionStream:
 
     def state_dict(self):
         """the checkpoint: plain tensors (safe to .cpu() and save) from which from_state continues with the same bits"""
-        return dict(version=_lib.STREAM_LAYOUT_VERSION, B=self.B, cap=self.cap, config=self.config, state_f64=self.state_f64.clone(),
-                    state_i64=self.state_i64.clone(), ring_t=self.ring_t.clone(), ring_pos=self.ring_pos.clone(), ring_quat=self.ring_quat.clone())
+        d = dict(version=_lib.STREAM_LAYOUT_VERSION, B=self.B, cap=self.cap, config=self.config, state_f64=self.state_f64.clone(),
+                 state_i64=self.state_i64.clone(), ring_t=self.ring_t.clone(), ring_pos=self.ring_pos.clone(), ring_quat=self.ring_quat.clone())
+        if self.lag is not None:                                         # (a stream without a lag: the keys it always had)
+            d.update(lag=self.lag, ring_lag=self.ring_lag.clone(), ring_spos=self.ring_spos.clone(), ring_svar=self.ring_svar.clone())
+        return d
 
     @classmethod
     def from_state(cls, d, device="cuda"):
@@ -2287,6 +2330,9 @@ class FusionStream:
             raise ValueError(f"FusionStream.from_state: layout version {d.get('version')!r}, this library reads version {_lib.STREAM_LAYOUT_VERSION}")
         B, cap = _stream_sizes_chk(d["B"], d["cap"])
         shapes_ = dict(state_f64=(_lib.STREAM_F64, B), state_i64=(_lib.STREAM_I64, B), ring_t=(B, cap), ring_pos=(B, cap, 3), ring_quat=(B, cap, 4))
+        lag = d.get("lag")
+        if lag is not None:
+            shapes_.update(ring_lag=(B, cap, _lib.STREAM_LAG_F64), ring_spos=(B, cap, 3), ring_svar=(B, cap, 3))
         for k, shp in shapes_.items():
             t = d[k]
             want = torch.int64 if k == "state_i64" else torch.float64
@@ -2295,14 +2341,14 @@ class FusionStream:
         si = d["state_i64"]
         if B and (bool((si[0] != _lib.STREAM_LAYOUT_VERSION).any()) or bool((si[1] != cap).any())):
             raise ValueError("FusionStream.from_state: state_i64 was not written by this layout version for this cap")
-        s = cls(B, cap, None, None, config=d.get("config"), device=device)
+        s = cls(B, cap, None, None, config=d.get("config"), device=device, lag=lag)
         for k in shapes_:
             getattr(s, k).copy_(d[k])
         return s
 
     @classmethod
-    def from_run(cls, rb, r, cap=4096, config=None):
+    def from_run(cls, rb, r, cap=4096, config=None, lag=None):
         """a stream opened from the Sim3-transformed pose 0 of every track of a run_fusion_ragged result r for the batch rb (built as
         gate_fused builds it), on rb's device; feed it rb's poses with r.aligned / r.valid, in pieces"""
         ip, iq = _fused_init_pose(rb, r)
-        return cls(int(ip.shape[0]), cap, ip, iq, config=config, device=ip.device)
+        return cls(int(ip.shape[0]), cap, ip, iq, config=config, device=ip.device, lag=lag)

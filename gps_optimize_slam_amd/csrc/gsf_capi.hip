@@ -33,7 +33,7 @@ int fail_hip(hipError_t e, const char* what)
 
 // growth per slot: the kernel workspace is allocated at exactly the bytes asked for (hundreds of MB at the largest batches: headroom there
 // would be footprint), the others with a quarter on top so that slowly growing calls stop allocating
-static const bool WS_HEADROOM[GSF_WS_COUNT] = { /* KERNEL */ false, /* RNG */ true, /* K2B */ true, /* ROWS */ true, /* RUN */ true };
+static const bool WS_HEADROOM[GSF_WS_COUNT] = { /* KERNEL */ false, /* RNG */ true, /* K2B */ true, /* ROWS */ true, /* RUN */ true, /* STREAM */ true };
 
 int ensure_workspace(gsf_ctx* ctx, int slot, size_t bytes)
 {

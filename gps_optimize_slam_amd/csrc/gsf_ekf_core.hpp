@@ -125,6 +125,15 @@ GSF_HD_COLD bool yaw_rate_exceeds_poly(Quat r1, Quat r2, double dt, double thr) 
 //   void  store(int64_t i, const Vec3& p, const Quat& q);      fused pose i
 //   void  load(int64_t i, Vec3& p, Quat& q) const;             read back a previously stored pose
 //   double stamp(int64_t i) const;                               input stamp i (RTS dt rebuild)
+// Out may also declare
+//   void  predicted(int64_t i, const Vec3& pp, const double* Pp);   x_p[i], P_p[i] of the step that stores pose i next
+// which step() then calls once, right before its store(i, ...); an Out without it compiles to what it compiled to before.
+template <class T> T& out_ref();                                        // (declared only: named inside decltype)
+template <class Out, class = void>
+struct out_takes_predicted { static constexpr bool value = false; };
+template <class Out>
+struct out_takes_predicted<Out, decltype(out_ref<Out>().predicted((int64_t)0, out_ref<const Vec3>(), (const double*)nullptr))> { static constexpr bool value = true; };
+
 template <class Out>
 struct EkfTraj {
     // filter state
@@ -218,6 +227,7 @@ struct EkfTraj {
             }
         }
         prev_avail = avail;                                              // :771, :926
+        if constexpr (out_takes_predicted<Out>::value) out.predicted(i, pp, Pp);
         out.store(i, p, q);                                              // :904
         po_prev = in.p; r_prev = r_cur; ok_prev = ok_cur; t_prev = t;    // :930
     }

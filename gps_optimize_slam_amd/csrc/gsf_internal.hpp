@@ -17,6 +17,7 @@ enum gsf_ws_slot {
     GSF_WS_K2B,      // K2b's rows as floats (screened residual counts, gsf_sim3.hip); grows below robust_chain as well
     GSF_WS_ROWS,     // row mask + flags of the Sim3 row choice for the kernels that take it as a pre-pass (gsf_ekf_block.hip); below robust_chain too
     GSF_WS_RUN,      // temporaries of the whole-run chain (gsf_run.hip), which holds pointers into it while its stages grow the kernel slot
+    GSF_WS_STREAM,   // the per-track plan the forward launch of gsf_stream_append_lag_dev leaves for its back-pass launch (gsf_stream_lag.hip): 16 B per track
     GSF_WS_COUNT
 };
 

@@ -77,7 +77,8 @@ struct RingOut {
     GSF_HD double stamp(int64_t i) const { return rt[slot(i)]; }
 };
 
-GSF_HD void stream_unpack(const double* sf, const int64_t* si, int64_t B, int64_t b, EkfTraj<RingOut>& f)
+template <class Out>
+GSF_HD void stream_unpack(const double* sf, const int64_t* si, int64_t B, int64_t b, EkfTraj<Out>& f)
 {
     const double* s = sf + b;
     f.p = Vec3{ s[0], s[B], s[2 * B] };
@@ -93,7 +94,8 @@ GSF_HD void stream_unpack(const double* sf, const int64_t* si, int64_t B, int64_
     f.status = (int32_t)si[SI_STATUS * B + b];
 }
 
-GSF_HD void stream_pack(double* sf, int64_t* si, int64_t B, int64_t b, const EkfTraj<RingOut>& f, int64_t n_total)
+template <class Out>
+GSF_HD void stream_pack(double* sf, int64_t* si, int64_t B, int64_t b, const EkfTraj<Out>& f, int64_t n_total)
 {
     double* s = sf + b;
     s[0] = f.p.x; s[B] = f.p.y; s[2 * B] = f.p.z;
@@ -148,11 +150,23 @@ GSF_HD void stream_nan_rows(const StreamSeg& g, int64_t lo, int64_t m)
     }
 }
 
+// The parking policy of an append: what, beyond the ring, is kept of every pose's step.  NoPark keeps nothing and is what
+// gsf_stream_append_dev runs; gsf_stream_lag_core.hpp's LagPark keeps the forward quantities of the fixed-lag smoother.  A policy names the
+// Out its filter runs on, may refuse a segment on a capacity rule of its own, and sees every pose right after its step.
+struct NoPark {
+    using Out = RingOut;
+    static constexpr bool parks = false;
+    GSF_HD bool refused(int64_t, int64_t, int64_t) const { return false; }
+    GSF_HD void row(const EkfConfig&, const EkfTraj<RingOut>&, const RingOut&, int64_t, bool) const {}
+};
+
 // One track of gsf_stream_append: continue the filter over rows lo .. lo + m - 1 of the segment arrays.  The first pose a track ever sees is
 // EkfTraj::init, every later one EkfTraj::step; the state is read once, kept in registers, written once.
+template <class Park = NoPark>
 GSF_HD StreamReport stream_append_track(const EkfConfig& cfg, double* sf, int64_t* si, int64_t B, int64_t b, int64_t cap, double* ring_t,
-                                        double* ring_pos, double* ring_quat, const StreamSeg& g, int64_t lo, int64_t m)
+                                        double* ring_pos, double* ring_quat, const StreamSeg& g, int64_t lo, int64_t m, const Park park = Park())
 {
+    using Out = typename Park::Out;
     StreamReport rep;
     m = m < 0 ? 0 : m;
     const int64_t n0 = si[SI_NTOTAL * B + b], os0 = si[SI_OSTART * B + b];
@@ -163,7 +177,7 @@ GSF_HD StreamReport stream_append_track(const EkfConfig& cfg, double* sf, int64_
         return rep;
     }
     const int32_t st0 = (int32_t)si[SI_STATUS * B + b];
-    if (stream_refused(open0, n0, os0, m, cap)) {
+    if (stream_refused(open0, n0, os0, m, cap) || park.refused(n0, m, cap)) {
         stream_nan_rows(g, lo, m);
         rep.n_total = n0; rep.n_final = open0 ? os0 : n0; rep.revised_from = n0;
         rep.status = st0 | (open0 ? ST_ENDED_IN_OUTAGE : 0) | STREAM_FULL;
@@ -174,22 +188,25 @@ GSF_HD StreamReport stream_append_track(const EkfConfig& cfg, double* sf, int64_
         rep.status = st0 | (open0 ? ST_ENDED_IN_OUTAGE : 0);
         return rep;
     }
-    EkfTraj<RingOut> f;
+    EkfTraj<Out> f;
     stream_unpack(sf, si, B, b, f);
-    RingOut out{ ring_t + b * cap, ring_pos + b * cap * 3, ring_quat + b * cap * 4, cap, n0, n0 % cap,
-                 g.pos_out ? g.pos_out + lo * 3 : nullptr, g.quat_out ? g.quat_out + lo * 4 : nullptr, n0 };
+    const RingOut ring{ ring_t + b * cap, ring_pos + b * cap * 3, ring_quat + b * cap * 4, cap, n0, n0 % cap,
+                        g.pos_out ? g.pos_out + lo * 3 : nullptr, g.quat_out ? g.quat_out + lo * 4 : nullptr, n0 };
+    Out out{ ring };
     StepIn nxt = stream_load_step(g, lo);
     for (int64_t j = 0; j < m; ++j) {
         const int64_t i = n0 + j;
         const StepIn in = nxt;
         nxt = stream_load_step(g, lo + (j + 1 < m ? j + 1 : j));         // one pose ahead (clamped re-read at the tail): the rows of a lane are its own
         out.rt[out.slot(i)] = in.t;                                      // the stamp first: a back-pass at this pose reads it
+        [[maybe_unused]] const bool was_outage = !f.prev_avail;                          // (read by a parking policy only)
         if (i == 0) {
             const Vec3 p0 = f.p; const Quat q0 = f.q;
             f.init(cfg, p0, q0, in, out);
         } else {
             f.step(cfg, i, in, out);
         }
+        if constexpr (Park::parks) park.row(cfg, f, out, i, was_outage);
         if (g.cov_out) {
 #pragma unroll
             for (int c = 0; c < 7; ++c) g.cov_out[(lo + j) * 7 + c] = f.P[c];

@@ -740,9 +740,11 @@ class FusionSession:
     ekf_fuse_aligned.  The filter continues exactly where it stopped: the pushes of a track give the bits of one push of the whole track.
     `cap` rows of history are kept for the RTS back-pass; a push longer than cap // 2 poses goes to the device in pieces of that length
     (the split changes no bit).  An outage that does not fit the ring with the next piece raises GsfError, the session staying as it was
-    before that piece: open a session with a larger cap."""
+    before that piece: open a session with a larger cap.
+    lag = L (1 .. min(cap - 1, _lib.STREAM_LAG_MAX)) adds the stream's fixed-lag RTS smoother: push() then also returns the smoothed rows that became final
+    (row i is final once the track holds i + L + 1 poses), and smoothed() the smoothed track so far."""
 
-    def __init__(self, init_pos, init_quat, config=None, cap=4096):
+    def __init__(self, init_pos, init_quat, config=None, cap=4096, lag=None):
         import torch
         from . import batch as gb
         self.cap = int(cap)
@@ -750,9 +752,23 @@ class FusionSession:
         self._dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
         if self._dev is None:
             raise GsfError("torch sees no GPU: a fusion session needs an MI355X (no CPU fallback)")
-        self._s = gb.FusionStream(1, self.cap, f64(init_pos, (1, 3)), f64(init_quat, (1, 4)), config=self.config, device=self._dev)
-        self.n_total = self.n_final = 0
+        if lag is not None and not 1 <= int(lag) < self.cap:
+            raise ValueError(f"FusionSession: lag in 1 .. cap - 1 expected, got {lag}")
+        self.lag = None if lag is None else int(lag)
+        self._s = gb.FusionStream(1, self.cap, f64(init_pos, (1, 3)), f64(init_quat, (1, 4)), config=self.config, device=self._dev, lag=self.lag)
+        self.n_total = self.n_final = self.n_smooth_final = 0
         self.status = 0
+        self._final = [np.empty((0, 3)), np.empty((0, 3)), np.empty((0,), dtype=np.uint8)]     # the final smoothed rows so far: pos, var, flags
+
+    def smoothed(self):
+        """the smoothed track so far: dict(pos (n,3), var (n,3), n_smooth_final) -- rows [0, n_smooth_final) are final, the rows above are the
+        provisional tail as the last push left it (the whole-track smoother's answer on what has arrived)"""
+        if self.lag is None:
+            raise ValueError("FusionSession.smoothed: the session was opened without a lag")
+        k = self.n_total - self.n_smooth_final
+        _, p, v, _ = self._s.rows_smoothed([self.n_smooth_final], [k])
+        return dict(pos=np.concatenate([self._final[0], p.cpu().numpy()]), var=np.concatenate([self._final[1], v.cpu().numpy()]),
+                    n_smooth_final=self.n_smooth_final)
 
     def rows(self, lo, count):
         """rows [lo, lo + count) of the track as they stand: ts, pos, quat (NaN where the ring no longer holds a row)"""
@@ -763,7 +779,8 @@ class FusionSession:
         """ts (m,), pos (m,3), quat (m,4) = the next original SLAM poses, aligned (m,3) / valid (m,) = their time-aligned fixes and mask.
         Returns dict(pos (m,3), quat (m,4), cov (m,7) filtered covariance diagonals, n_total, n_final, revised_from, status): rows
         [0, n_final) of the track are final, rows from revised_from on were written by this push (fetch the ones before this push's
-        own with rows())."""
+        own with rows()).  With a lag also pos_smooth (k,3), var_smooth (k,3), flags_smooth (k,) = the smoothed rows that became final in
+        this push (final rows smooth_from .. smooth_from + k - 1), smooth_from and n_smooth_final."""
         import torch
         ts, pos, quat, aligned = f64(ts).reshape(-1), f64(pos).reshape(-1, 3), f64(quat).reshape(-1, 4), f64(aligned).reshape(-1, 3)
         valid = np.ascontiguousarray(valid, dtype=np.uint8).reshape(-1)
@@ -774,7 +791,8 @@ class FusionSession:
         d = [up(a) for a in (ts, pos, quat, aligned, valid)]
         po, qo, co = np.empty((m, 3)), np.empty((m, 4)), np.empty((m, 7))
         first, revised = self.n_total, self.n_total
-        piece = max(1, self.cap // 2)
+        piece = max(1, self.cap // 2 if self.lag is None else min(self.cap // 2, self.cap - self.lag))
+        smooth_from, new_final = self.n_smooth_final, [[], [], []]
         for lo in range(0, max(m, 1), piece):
             hi = min(m, lo + piece)
             st = self._s.append(*[a[lo:hi].contiguous() for a in d], torch.tensor([0, hi - lo], dtype=torch.int64, device=self._dev))
@@ -789,7 +807,17 @@ class FusionSession:
                 _, po[a - first:lo], qo[a - first:lo] = self.rows(a, start - a)
             revised = min(revised, rf)
             self.n_total, self.n_final, self.status = int(st.n_total[0].item()), int(st.n_final[0].item()), status
-        return dict(pos=po, quat=qo, cov=co, n_total=self.n_total, n_final=self.n_final, revised_from=revised, status=self.status)
+            if self.lag is not None:
+                k = int(st.n_smooth_final[0].item()) - int(st.smooth_from[0].item())
+                for acc, t in zip(new_final, (st.pos_smooth, st.var_smooth, st.flags_smooth)):
+                    acc.append(t[:k].cpu().numpy())
+                self.n_smooth_final = int(st.n_smooth_final[0].item())
+        out = dict(pos=po, quat=qo, cov=co, n_total=self.n_total, n_final=self.n_final, revised_from=revised, status=self.status)
+        if self.lag is not None:
+            got = [np.concatenate(a) if a else e[:0] for a, e in zip(new_final, self._final)]
+            self._final = [np.concatenate([e, g]) for e, g in zip(self._final, got)]
+            out.update(pos_smooth=got[0], var_smooth=got[1], flags_smooth=got[2], smooth_from=smooth_from, n_smooth_final=self.n_smooth_final)
+        return out
 
 
 def ekf_covariances(slam_data_in, gps_data_in, global_config):

@@ -921,6 +921,46 @@ GSF_API int gsf_stream_gather_dev(gsf_ctx *ctx, int64_t B, int64_t cap, const in
                                   const double *ring_pos, const double *ring_quat, const int64_t *lo, const int64_t *out_offsets,
                                   double *ts_out, double *pos_out, double *quat_out);
 
+/* ---- streaming fusion with a fixed-lag RTS smoother ----------------------------------------------------------------------------------------
+   gsf_stream_append_dev returns the causal filter: where GNSS is present row i uses no fix after stamp i.  gsf_stream_append_lag_dev is a
+   SUPERSET of it -- every argument of that entry with the same meaning, the same outputs, state and ring bit for bit -- that also smooths
+   every row with the fixes of the next `lag` rows, at a cost that depends on lag and the new poses, never on the history.
+   With the forward quantities of gsf_ekf_smooth_ragged_dev (xf, Pf filtered; xp, Pp predicted; g = xf - xp; a span starts at row 0 and at
+   every sharp-turn recovery), row i of a track that holds n poses, s(i) the last row of i's span:
+       we(i) = min(i + lag, s(i), n - 1);   e = d = 0 at we(i);   for k = we(i) - 1 .. i:
+           A[k] = Pf[k] / Pp[k+1]  (0 where Pp[k+1] == 0),   e = A[k] (e + g[k+1]),   d = A[k]^2 (d + Pf[k+1] - Pp[k+1])
+       xs[i] = xf[i] + e,   Ps[i] = Pf[i] + d
+   i.e. rts_smoother_segment on rows [i .. we(i)], row i of the whole-track smoother run on the prefix [0 .. min(i + lag, n - 1)].  Rows that no
+   later fix of their span reaches inside the window keep xf, Pf exactly; a zero-variance axis comes back unsmoothed, free of NaN.  The
+   orientation is never touched by a fix: row i's quaternion is the ring's, no smoothed quaternion is produced.
+   Row i is FINAL once i + lag <= n - 1: n_smooth_final = max(0, n - lag).  The rows above are PROVISIONAL: the whole-track smoother's answer
+   on what has arrived so far, rewritten by every call.  How a track is cut into calls does not change one bit of a final row, of
+   smooth_from / n_smooth_final, or of the three rings at equal n_total.
+     lag                 1 .. GSF_STREAM_LAG_MAX.  A property of a stream's life: a final row is the row of the lag in force when it became
+                         final; rows that were final are not revisited when a later call names another lag.
+     ring_lag[B][cap][GSF_STREAM_LAG_F64]   opaque: the forward quantities of every row the ring holds.  Need not be initialised.
+     ring_spos[B][cap][3], ring_svar[B][cap][3]   smoothed position and variance of every row the ring holds (slot i % cap), final below
+                         n_smooth_final, provisional above.  The layout of ring_pos: gsf_stream_gather_dev fetches either in ring_pos's place.
+   New outputs, each may be NULL:
+     spos_out[P][3], svar_out[P][3], sflags_out[P] (uint8)   the rows that BECAME FINAL IN THIS CALL, in the segment's ragged shape: row j of
+                         track b's segment is final row smooth_from[b] + j (a call on m poses finalises at most m rows); the rest of the
+                         segment's rows are NaN, flags 0.  Flags: GSF_POSE_SMOOTHED (a later fix inside the window was applied) and
+                         GSF_POSE_SPAN_START.
+     smooth_from[B], n_smooth_final[B]   the number of final rows before and after the call.
+   CAPACITY.  A track is refused with GSF_STREAM_FULL if gsf_stream_append_dev's rule refuses it or if min(lag, n_total) + segment length
+   > cap (the rows a call's back-pass rewrites need a slot each).  A refused track and one with a bad state leave all three new rings
+   untouched; their new output rows are NaN.
+   Two launches on the context's stream: the append (lane per track) and the back-pass (wave per track, lane = row, <= lag + m rows).  The
+   context keeps 16 bytes per track of workspace between the two (allocated on the first call, gsf_trim releases it). */
+#define GSF_STREAM_LAG_MAX 512
+#define GSF_STREAM_LAG_F64 12
+GSF_API int gsf_stream_append_lag_dev(gsf_ctx *ctx, const gsf_ekf_config *cfg, int64_t B, int64_t cap, int64_t lag, double *state_f64,
+                                      int64_t *state_i64, double *ring_t, double *ring_pos, double *ring_quat, double *ring_lag,
+                                      double *ring_spos, double *ring_svar, const double *ts, const double *pos, const double *quat,
+                                      const double *gps, const uint8_t *valid, const int64_t *seg_offsets, double *pos_out, double *quat_out,
+                                      double *cov_out, int64_t *n_total, int64_t *n_final, int64_t *revised_from, int32_t *status,
+                                      double *spos_out, double *svar_out, uint8_t *sflags_out, int64_t *smooth_from, int64_t *n_smooth_final);
+
 /* ---- local Sim3 alignment: windowed knots against SLAM scale drift ------------------------------------------------------------------------
    The chain fits ONE Sim3 per track (EKFGPSSLAM.py:973-1006) and applies its scale to the whole run, while a monocular front end drifts in
    scale over minutes.  These two entries fit Sim3 KNOTS on a time grid along each track and map every pose by a blend of the neighbouring
