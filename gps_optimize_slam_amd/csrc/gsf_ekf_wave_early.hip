@@ -23,8 +23,14 @@
 //      behind dep_end (behind the gap's row of a track that fits its first segment) are not waited for.  Under "every valid row" nothing is
 //      assumed or chosen: the exact masks, then one block of sums, as in the one-wave kernel's pass.  The closed form (fit_from_partials) is the one-wave kernel's.  A miss in
 //      an early chunk forms that part of the table again from memory, with the NaN test, wave-uniformly;
-//   5. runs wave_serial_chunks<PIPELINE, PREVAR = true, ..., PVCHUNKS>: the first chunks read the table as the two-wave kernel's main wave
-//      does, the chunks behind them run their scans as the one-wave kernel does.  There is one chunk loop per build, chosen by nothing.
+//   5. runs wave_serial_chunks<PIPELINE, PREVAR = true, ..., PVCHUNKS, REGCHUNKS = NCH>: the first chunks read the table as the two-wave
+//      kernel's main wave does, the chunks behind them run their scans as the one-wave kernel does.  The kernel's type carries the number of
+//      chunks, so the chunks are NCH straight-line instances of the ONE chunk body (c0 = 64 k a constant, L = 63 but for the last chunk: the
+//      lane masks built from them fold), and chunk k + 1 takes its stamp, mask byte, SLAM position and fix from the registers of 1 -- the
+//      rolled loop asked memory for all of them again, 12 loads and the address arithmetic of five arrays per chunk.  Only the quaternion
+//      of chunk k + 1 is requested in chunk k (four loads, one address); the last chunk requests nothing.  The registers hold what memory
+//      holds: nothing writes them after 2 (the fall-back pass of 4 reads them), and the idle lanes of a short last chunk hold the last row
+//      by il[] of 1, which is load_chunk's clamp.  The carried-outage patch reads stamps from memory and the LDS ring as before.
 // No load may stay pending on a rare path of 2b or 4: where paths meet the wave would wait for it with vmcnt(0), i.e. for the whole burst.
 // Single stamps and the shift of a track whose first valid row is not row 0 therefore come out of the registers (v_readlane), not from memory.
 // One wave per block: no barrier, no wait on another wave; a wave's LDS operations complete in order.
@@ -47,6 +53,16 @@ namespace {
 // SLOWER -- the closed form's block has no issue slots to spare; HISTORY.md, "Early head")
 #ifndef GSF_EARLY_HEAD
 #define GSF_EARLY_HEAD 0
+#endif
+// The chunk loop's rows from the registers of the burst, one straight-line instance of the chunk body per chunk (1), or from memory again in
+// the rolled loop (0, the A/B form; HISTORY.md, "Early rows from registers")
+#ifndef GSF_EARLY_REGROWS
+#define GSF_EARLY_REGROWS 1
+#endif
+// With GSF_EARLY_REGROWS: every chunk's quaternion requested where it is needed, one chunk ahead (0), or all of them at the end of the burst,
+// behind chunk 0's (1, the A/B form: 32 B/pose more in the phase where the memory system is the limit; HISTORY.md, same section)
+#ifndef GSF_EARLY_QBURST
+#define GSF_EARLY_QBURST 0
 #endif
 // (GSF_EARLY_SKIP_Y, the table without its y rows: gsf_wave_common.hpp, where the chunk loop reads the table)
 
@@ -94,6 +110,13 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     ChunkIn nxt;
     nxt.q = Quat{ __builtin_nontemporal_load(&quatb[il[0] * 4]), __builtin_nontemporal_load(&quatb[il[0] * 4 + 1]),
                   __builtin_nontemporal_load(&quatb[il[0] * 4 + 2]), __builtin_nontemporal_load(&quatb[il[0] * 4 + 3]) };
+#if GSF_EARLY_REGROWS && GSF_EARLY_QBURST
+    Quat qk[NCH];                                                         // (A/B form: vmcnt retires in order, no earlier use waits for these)
+#pragma unroll
+    for (int k = 1; k < NCH; ++k)
+        qk[k] = Quat{ __builtin_nontemporal_load(&quatb[il[k] * 4]), __builtin_nontemporal_load(&quatb[il[k] * 4 + 1]),
+                      __builtin_nontemporal_load(&quatb[il[k] * 4 + 2]), __builtin_nontemporal_load(&quatb[il[k] * 4 + 3]) };
+#endif
 #pragma unroll
     for (int k = NCH; k < 6; ++k) {                                       // (chunks past the end of the track, as the passes' own loads leave them)
         rr.pa[k][0] = rr.pa[k][1] = rr.pa[k][2] = 0.0; rr.pz[k][0] = rr.pz[k][1] = rr.pz[k][2] = 0.0; rr.pt[k] = 0.0; rr.pv[k] = 0u;
@@ -334,7 +357,13 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     GSF_STAMP(6);
 
     // ---- 5. the chunk loop: its first NE chunks as the two-wave kernel's main wave runs them, the rest as the one-wave kernel does
+#if GSF_EARLY_REGROWS && GSF_EARLY_QBURST
+    wave_serial_chunks<PIPELINE, true, true, 1, AXMODE, TAILNS, NE, NCH, true>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, gsf_pv, stride, 0, nullptr, &rr, qk);
+#elif GSF_EARLY_REGROWS
+    wave_serial_chunks<PIPELINE, true, true, 1, AXMODE, TAILNS, NE, NCH>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, gsf_pv, stride, 0, nullptr, &rr);
+#else
     wave_serial_chunks<PIPELINE, true, true, 1, AXMODE, TAILNS, NE>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, gsf_pv, stride);
+#endif
 }
 
 #define GSF_WAVE_EARLY_KERNEL(C_, T_)                                                                                                 \

@@ -1003,14 +1003,22 @@ __device__ __forceinline__ void chunk_head_pin(const ChunkHeadRows& h)
 // guarantees that N is a multiple of 64.
 // PVCHUNKS (early-variance build, gsf_ekf_wave_early.hip): only the first PVCHUNKS chunks -- full ones -- take their variances from the
 // table, the chunks behind them run their scans; 0: PREVAR holds for every chunk.
-template <bool V> struct FromTable { static constexpr bool value = V; };
-template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6, int PVCHUNKS = 0>
+// REGCHUNKS (early-variance build, GSF_EARLY_REGROWS): the track has exactly REGCHUNKS chunks and the caller holds the stamp, mask byte,
+// SLAM position and fix of every one of them in registers (regrows, as its burst left them: idle lanes of a short last chunk hold the
+// last row, load_chunk's clamp).  The chunks then run as REGCHUNKS straight-line instances of the body with c0 a constant; chunk k hands
+// chunk k + 1 those registers and requests its quaternion alone; the last chunk requests nothing.  (REGQUATS: the quaternions are in the
+// caller's registers too, regquats[k], and no chunk requests anything.)  0: the loops below, as every other build runs them.
+template <bool V> struct FromTable { static constexpr bool value = V; static constexpr int regk = -1; };
+template <bool V, int K> struct FromTableRegs { static constexpr bool value = V; static constexpr int regk = K; };   // chunk K of a REGCHUNKS build
+template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6, int PVCHUNKS = 0, int REGCHUNKS = 0, bool REGQUATS = false>
 __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfConfig& cfg, const int64_t b, const int lane, const int64_t base,
                                                    const int64_t N, const Vec3& p0, const Quat& q0, const int32_t fit,
                                                    typename NextChunk<GSF_WIDE(SMALLBATCH)>::type nxt,
                                                    const double* pv = nullptr, const int pv_stride = 0, const int ring_slot = 0,
-                                                   double* ext_ring = nullptr)
+                                                   double* ext_ring = nullptr, const RoundRows<GSF_ROWS_ROUND>* regrows = nullptr, const Quat* regquats = nullptr)
 {
+    static_assert(REGCHUNKS == 0 || (!GSF_WIDE(SMALLBATCH) && PVCHUNKS > 0 && PVCHUNKS < REGCHUNKS && REGCHUNKS <= GSF_ROWS_ROUND),
+                  "rows from registers: the early-variance build's per-lane rows, one round of them");
     const double* __restrict__ tsb = a.ts + base;
     const double* __restrict__ posb = a.pos + base * 3;
     const double* __restrict__ quatb = a.quat + base * 4;
@@ -1078,6 +1086,20 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         if constexpr (GSF_WIDE(SMALLBATCH)) {
             in = unpack_chunk(nxt, wave_stage(), lane, L);
             nxt = load_chunk_wide(tsb, posb, quatb, gpsb, valb, c0 + 64, lane, N);
+        } else if constexpr (decltype(pv_tag)::regk >= 0) {
+            // (REGCHUNKS build: the next chunk's rows are the caller's registers; its quaternion alone is requested -- four loads, one
+            // address, clamped as load_chunk clamps it.  The last chunk requests nothing.)
+            constexpr int KN = decltype(pv_tag)::regk + 1;
+            in = nxt;
+            if constexpr (KN < REGCHUNKS) {
+                [[maybe_unused]] const int iq = 64 * KN + lane, ilq = (KN < REGCHUNKS - 1 || iq < (int)N) ? iq : (int)N - 1;
+                nxt.t = regrows->pt[KN]; nxt.v = regrows->pv[KN];
+                nxt.p = Vec3{ regrows->pa[KN][0], regrows->pa[KN][1], regrows->pa[KN][2] };
+                nxt.z = Vec3{ regrows->pz[KN][0], regrows->pz[KN][1], regrows->pz[KN][2] };
+                if constexpr (REGQUATS) nxt.q = regquats[KN];             // (A/B form: the caller's burst requested every chunk's quaternion as well)
+                else nxt.q = Quat{ __builtin_nontemporal_load(&quatb[ilq * 4]), __builtin_nontemporal_load(&quatb[ilq * 4 + 1]),
+                                   __builtin_nontemporal_load(&quatb[ilq * 4 + 2]), __builtin_nontemporal_load(&quatb[ilq * 4 + 3]) };
+            }
         } else {
             in = nxt;
             nxt = load_chunk(tsb, posb, quatb, gpsb, valb, c0 + 64 + lane, N);   // unconditional (clamped to the last row past the end): no branch between the loads and the arithmetic below
@@ -1328,7 +1350,19 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
     // In a sized kernel the loop's chunks are FULL ones by construction, so L = 63 is a constant there and the lane masks built from it
     // fold away -- measured, that is worth as much as the stages the last chunk skips (HISTORY.md, "Sized scans for a short last chunk").
     // (Three instances side by side in ONE loop, chosen per iteration, were measured first: the full chunk lost 130 cycles to them.)
-    if constexpr (PVCHUNKS > 0) {
+    if constexpr (REGCHUNKS > 0) {
+        // REGCHUNKS instances of the body in a row, c0 = 64 K and (but for the last chunk) L = 63 constants: init_m, step_m, act_mask and
+        // ap_m's carry bit of chunk 0 fold; the first PVCHUNKS read the table, the last keeps its sized instance.
+#define GSF_REG_CHUNK(K_)                                                                                                                   \
+        if constexpr (K_ < PVCHUNKS) chunk_body(ScanStages<6>{}, FromTableRegs<true, K_>{}, (int64_t)(64 * K_), 63);                          \
+        else if constexpr (K_ < REGCHUNKS - 1 || (K_ == REGCHUNKS - 1 && TAILNS == WAVE_TAIL_FULL))                                           \
+            chunk_body(ScanStages<6>{}, FromTableRegs<false, K_>{}, (int64_t)(64 * K_), 63);                                                  \
+        else if constexpr (K_ == REGCHUNKS - 1)                                                                                               \
+            chunk_body(ScanStages<(TAILNS == WAVE_TAIL_FULL ? 6 : TAILNS)>{}, FromTableRegs<false, K_>{}, (int64_t)(64 * K_), (int)(N - 64 * K_ - 1));
+        GSF_REG_CHUNK(0) GSF_REG_CHUNK(1) GSF_REG_CHUNK(2) GSF_REG_CHUNK(3) GSF_REG_CHUNK(4) GSF_REG_CHUNK(5)
+#undef GSF_REG_CHUNK
+        static_assert(GSF_ROWS_ROUND <= 6, "one instance per chunk of the round");
+    } else if constexpr (PVCHUNKS > 0) {
         // (the caller guarantees more than PVCHUNKS chunks: the chunks that read the table are full ones, the rest is the loop of the kernel without a table)
         int64_t c0 = 0;
 #pragma nounroll
