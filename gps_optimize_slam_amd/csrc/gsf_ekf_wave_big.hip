@@ -2,8 +2,8 @@
 // waves per SIMD (B > 2 048 trajectories; C3, the C5 shard).  Same template, same arithmetic, same bits as the small-batch builds; what
 // differs is how a chunk's rows travel: with several waves per SIMD the launch sits on the memory system under its mixed read + write
 // stream (the C3 timing probes), so the strided 8-byte loads / stores of a lane's own row are replaced by whole
-// 16-byte pieces of the chunk's contiguous slabs, lane after lane, transposed through a few KB of LDS (GSF_WIDE(SMALLBATCH) and
-// GSF_WIDE_STORES in gsf_wave_common.hpp).  A separate translation unit because the two regimes want different instruction schedulers
+// 16-byte pieces of the chunk's contiguous slabs, lane after lane, transposed through a few KB of LDS (the !SMALLBATCH
+// paths of gsf_wave_common.hpp).  A separate translation unit because the two regimes want different instruction schedulers
 // (Makefile): iterative-ilp for the lone wave of the small batches, max-ilp here.
 #define GSF_ROWS_ROUND 4                                                  // rounds of the row-choice pass: six chunks in flight spill 17 registers at 168 per lane
 #include "gsf_wave_common.hpp"

@@ -10,7 +10,8 @@
 //   2. waits for stamps and mask bytes ALONE and takes a set mask byte to mean a usable fix (true of every row the generator, the loaders
 //      and time_align_kernel produce; a NaN fix under a set mask byte is the reference's demotion quirk, see 4);
 //   3. runs the local scans of the first GSF_EARLY_CHUNKS chunks side by side in one basic block, applies the carried variance chunk after
-//      chunk and writes P_f, P_p and the gain of their poses into LDS, in the layout of the two-wave kernel's helper.  Only what fits the
+//      chunk and writes P_f, P_p and the gain of their poses into LDS, in the layout of the two-wave kernel's helper but for the y rows:
+//      y repeats x (AXMODE 1), so they are neither written nor read and the chunk loop copies x in registers.  Only what fits the
 //      shadow of the burst is done here: a chunk's scans are ~1 400-1 700 cycles of issue, and every cycle past the arrival of the rows
 //      delays the fit by as much as the chunk loop gains (all chunks early: +1.3 us; HISTORY.md, "Early variances");
 //  2b. chooses the rows of the fit (the reference's rule, ref :973-998) from the same stamps and mask bytes, still in the shadow: the
@@ -26,8 +27,8 @@
 //   5. runs wave_serial_chunks<PIPELINE, PREVAR = true, ..., PVCHUNKS, REGCHUNKS = NCH>: the first chunks read the table as the two-wave
 //      kernel's main wave does, the chunks behind them run their scans as the one-wave kernel does.  The kernel's type carries the number of
 //      chunks, so the chunks are NCH straight-line instances of the ONE chunk body (c0 = 64 k a constant, L = 63 but for the last chunk: the
-//      lane masks built from them fold), and chunk k + 1 takes its stamp, mask byte, SLAM position and fix from the registers of 1 -- the
-//      rolled loop asked memory for all of them again, 12 loads and the address arithmetic of five arrays per chunk.  Only the quaternion
+//      lane masks built from them fold), and chunk k + 1 takes its stamp, mask byte, SLAM position and fix from the registers of 1, not
+//      from memory again (12 loads and the address arithmetic of five arrays per chunk).  Only the quaternion
 //      of chunk k + 1 is requested in chunk k (four loads, one address); the last chunk requests nothing.  The registers hold what memory
 //      holds: nothing writes them after 2 (the fall-back pass of 4 reads them), and the idle lanes of a short last chunk hold the last row
 //      by il[] of 1, which is load_chunk's clamp.  The carried-outage patch reads stamps from memory and the LDS ring as before.
@@ -44,27 +45,6 @@
 using namespace gsf;
 
 namespace {
-
-// The row choice in the shadow of the burst (1) or behind the arrival of every row (0, the A/B form; HISTORY.md, "Early rows")
-#ifndef GSF_EARLY_RULE
-#define GSF_EARLY_RULE 1
-#endif
-// The rows part of chunk 0's head where the chunk loop forms it (0) or beside the fit's closed form (1, the A/B form: measured 0.2 us
-// SLOWER -- the closed form's block has no issue slots to spare; HISTORY.md, "Early head")
-#ifndef GSF_EARLY_HEAD
-#define GSF_EARLY_HEAD 0
-#endif
-// The chunk loop's rows from the registers of the burst, one straight-line instance of the chunk body per chunk (1), or from memory again in
-// the rolled loop (0, the A/B form; HISTORY.md, "Early rows from registers")
-#ifndef GSF_EARLY_REGROWS
-#define GSF_EARLY_REGROWS 1
-#endif
-// With GSF_EARLY_REGROWS: every chunk's quaternion requested where it is needed, one chunk ahead (0), or all of them at the end of the burst,
-// behind chunk 0's (1, the A/B form: 32 B/pose more in the phase where the memory system is the limit; HISTORY.md, same section)
-#ifndef GSF_EARLY_QBURST
-#define GSF_EARLY_QBURST 0
-#endif
-// (GSF_EARLY_SKIP_Y, the table without its y rows: gsf_wave_common.hpp, where the chunk loop reads the table)
 
 static_assert(GSF_ROWS_ROUND == 6, "the early-variance build hands the fit passes ONE round of six chunks");
 
@@ -110,13 +90,6 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     ChunkIn nxt;
     nxt.q = Quat{ __builtin_nontemporal_load(&quatb[il[0] * 4]), __builtin_nontemporal_load(&quatb[il[0] * 4 + 1]),
                   __builtin_nontemporal_load(&quatb[il[0] * 4 + 2]), __builtin_nontemporal_load(&quatb[il[0] * 4 + 3]) };
-#if GSF_EARLY_REGROWS && GSF_EARLY_QBURST
-    Quat qk[NCH];                                                         // (A/B form: vmcnt retires in order, no earlier use waits for these)
-#pragma unroll
-    for (int k = 1; k < NCH; ++k)
-        qk[k] = Quat{ __builtin_nontemporal_load(&quatb[il[k] * 4]), __builtin_nontemporal_load(&quatb[il[k] * 4 + 1]),
-                      __builtin_nontemporal_load(&quatb[il[k] * 4 + 2]), __builtin_nontemporal_load(&quatb[il[k] * 4 + 3]) };
-#endif
 #pragma unroll
     for (int k = NCH; k < 6; ++k) {                                       // (chunks past the end of the track, as the passes' own loads leave them)
         rr.pa[k][0] = rr.pa[k][1] = rr.pa[k][2] = 0.0; rr.pz[k][0] = rr.pz[k][1] = rr.pz[k][2] = 0.0; rr.pt[k] = 0.0; rr.pv[k] = 0u;
@@ -159,9 +132,6 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
         const AxisVar vx = variance_finish(mx[k], qx, rx, dt[k], cPx);
         const AxisVar vz = variance_finish(mz[k], qz, rz, dt[k], cPz);
         gsf_pv[0 * stride + i] = vx.Pf; gsf_pv[1 * stride + i] = vx.Pm; gsf_pv[2 * stride + i] = vx.kg;
-#if !GSF_EARLY_SKIP_Y
-        gsf_pv[3 * stride + i] = vx.Pf; gsf_pv[4 * stride + i] = vx.Pm; gsf_pv[5 * stride + i] = vx.kg;   // y repeats x
-#endif
         gsf_pv[6 * stride + i] = vz.Pf; gsf_pv[7 * stride + i] = vz.Pm; gsf_pv[8 * stride + i] = vz.kg;
         cPx = lane_bcast(vx.Pf, 63); cPz = lane_bcast(vz.Pf, 63);
     }
@@ -170,10 +140,6 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
 
     // ---- 2b. the row choice (ref :973-998) from stamps and mask bytes, under the assumption of 2: which rows the fit sums, as one lane mask
     // per chunk, before a row has been summed -- the fall-backs of the rule are decisions on popcounts (gsf_rows_rule.hpp), not second passes
-#if !GSF_EARLY_RULE                                                       // A/B form (a): the rule behind the arrival of every row
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) asm volatile("" :: "v"(rr.pz[k][0]), "v"(rr.pz[k][1]), "v"(rr.pz[k][2]), "v"(rr.pa[k][0]), "v"(rr.pa[k][1]), "v"(rr.pa[k][2]) : "memory");
-#endif
     u64 av[6];                                                            // rows of the track whose mask byte is set
 #pragma unroll
     for (int k = 0; k < 6; ++k) av[k] = k < NCH ? (mask_first(Ni - 64 * k) & mask_nonzero(rr.pv[k])) : 0ull;
@@ -305,32 +271,7 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     {
         const double as_[3] = { as0, as1, as2 };
         const Quat qraw0 = lane_bcast(nxt.q, 0);                          // pose 0's quaternion as stored: requested last, used after the closed form
-#if GSF_EARLY_HEAD
-        // ---- 4b (A/B form, not shipped). the rows part of chunk 0's head (GSF_CHUNK_HEAD_ROWS: unit quaternions, previous-lane moves, dt, the
-        // gate and the outage masks) needs no result of the fit, and every row it reads is in registers: formed HERE, in the basic block of the
-        // closed form, on the idea that its dependent chain leaves a lone wave issue slots.  Measured, it does not: chunk 0 gets 130 cycles
-        // shorter and the prelude 240 longer (HISTORY.md, "Early head").
-        // The chunk loop is untouched -- it expands the same statements on the same operands and finds the values formed.
-        // Too few rows (fit None without a closed form; wave-uniform, rare) leaves first, so that no branch stands between the head and the
-        // closed form; fit_from_partials' own test of the same condition then folds away.  The head has no side effect: the other exits
-        // (a degenerate fit, a bad pose-0 quaternion) leave behind it as they always did.
-        // (one test per operand of fit_from_partials' own condition, so that each is KNOWN where that condition is evaluated again: behind a
-        // joint test the compiler kept a second closed form in the exit)
-        const auto none = [&]() __attribute__((always_inline)) {
-            asm volatile("" ::: "memory");                               // (a real branch, not if-conversion)
-            fit_from_partials(a, b, base, N, lane, sums, as_, bs_, qraw0, p0, q0, fit, rows_flag, true);   // (writes the NaN rows and the status word)
-        };
-        if (!(sums[0] >= 3.0)) { none(); return; }
-        if (rows_flag & SIM3_FLAG_FEW_ROWS) { none(); return; }
-        // chunk 0's carry-in as wave_serial_chunks forms it: pose 0 is its own predecessor (ref :858)
-        Quat h_r; const bool h_ok = quat_unit(qraw0, h_r);
-        const ChunkHeadRows head0 = chunk_head_rows(nxt, ~0ull, 1ull, ~1ull, 0, lane_bcast(nxt.t, 0), lane_bcast(nxt.p, 0), h_ok,
-                                                    __builtin_amdgcn_readlane((int)nxt.v, 0) != 0);
-#endif
         if (!fit_from_partials(a, b, base, N, lane, sums, as_, bs_, qraw0, p0, q0, fit, rows_flag, true)) return;   // (fit None, bad pose-0 quaternion: the table is never read)
-#if GSF_EARLY_HEAD
-        chunk_head_pin(head0);
-#endif
     }
     if (miss != 0ull) {
         // a NaN fix under a set mask byte in the first NE chunks (wave-uniform, rare): their part of the table again, from memory, with the
@@ -346,9 +287,6 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
             AxisVar v0, v1, v2;
             variance_chunk<6>(cfg, 0, -1, dtk, step, avail, cP0, cP1, cP2, v0, v1, v2);   // (AXMODE 1: y repeats x, z has its own scan)
             gsf_pv[0 * stride + i] = v0.Pf; gsf_pv[1 * stride + i] = v0.Pm; gsf_pv[2 * stride + i] = v0.kg;
-#if !GSF_EARLY_SKIP_Y
-            gsf_pv[3 * stride + i] = v1.Pf; gsf_pv[4 * stride + i] = v1.Pm; gsf_pv[5 * stride + i] = v1.kg;
-#endif
             gsf_pv[6 * stride + i] = v2.Pf; gsf_pv[7 * stride + i] = v2.Pm; gsf_pv[8 * stride + i] = v2.kg;
             cP0 = lane_bcast(v0.Pf, 63); cP1 = lane_bcast(v1.Pf, 63); cP2 = lane_bcast(v2.Pf, 63); c_t = lane_bcast(t, 63);
         }
@@ -357,13 +295,7 @@ __device__ __forceinline__ void wave_early_body(const WaveArgs& a, const EkfConf
     GSF_STAMP(6);
 
     // ---- 5. the chunk loop: its first NE chunks as the two-wave kernel's main wave runs them, the rest as the one-wave kernel does
-#if GSF_EARLY_REGROWS && GSF_EARLY_QBURST
-    wave_serial_chunks<PIPELINE, true, true, 1, AXMODE, TAILNS, NE, NCH, true>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, gsf_pv, stride, 0, nullptr, &rr, qk);
-#elif GSF_EARLY_REGROWS
     wave_serial_chunks<PIPELINE, true, true, 1, AXMODE, TAILNS, NE, NCH>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, gsf_pv, stride, 0, nullptr, &rr);
-#else
-    wave_serial_chunks<PIPELINE, true, true, 1, AXMODE, TAILNS, NE>(a, cfg, b, lane, base, N, p0, q0, fit, nxt, gsf_pv, stride);
-#endif
 }
 
 #define GSF_WAVE_EARLY_KERNEL(C_, T_)                                                                                                 \

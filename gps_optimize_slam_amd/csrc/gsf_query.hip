@@ -15,8 +15,7 @@
 //     The searches whose key is the same in every lane (the wave's first and last query in q_offsets, its smallest and largest stamp in the
 //     track) spread their probes over the 64 lanes: ceil(log64 n) dependent loads instead of log2 n.
 //  The 24- / 32-byte rows of x, out_xyz, out_pos and out_quat are read and written row by row, one lane each: on the MI355X that is as fast
-//  as moving them as 16-byte pieces through the wave's LDS slice (the scheme of apply_sim3_slab_kernel), which -DGSF_QUERY_LDS_ROWS builds
-//  for the A/B of DESIGN.md 7e.
+//  as moving them as 16-byte pieces through the wave's LDS slice (the scheme of apply_sim3_slab_kernel; measured).
 #include "gsf_internal.hpp"
 #include "gsf_query_core.hpp"
 
@@ -26,7 +25,6 @@ using namespace gsf;
 
 typedef unsigned long long u64;
 typedef __attribute__((address_space(3))) const double* lds_cdp;
-typedef double q_v2 __attribute__((ext_vector_type(2), aligned(8)));
 
 struct QueryArgs {
     const double* ts; const double* pos; const double* quat; const int64_t* offsets; const uint8_t* pose_flags;
@@ -82,54 +80,22 @@ __device__ __forceinline__ int64_t wave_count_le(const T* __restrict__ a, const 
     return lo + __popcll(__ballot(p < hi && a[p] <= v));
 }
 
-// ---- 64 rows of C doubles between one lane each and a contiguous slab of global memory, through the wave's LDS slice `stage`
-// (>= 64 * C doubles).  rows <= 64 rows exist; the slab starts at g.  16-byte pieces lane after lane; an odd count of doubles leaves one
-// double to lane 0.  A wave's LDS operations complete in order: a wait, no barrier.
+// ---- 64 rows of C doubles, one lane each, of a contiguous slab of global memory that starts at g; rows <= 64 rows exist.  The idle
+// lanes of the last wave store nothing and load its last row.
 template <int C>
-__device__ __forceinline__ void wave_rows_store(double* stage, const int lane, const int rows, double* g, const double (&v)[C])
+__device__ __forceinline__ void wave_rows_store(const int lane, const int rows, double* g, const double (&v)[C])
 {
-#if !defined(GSF_QUERY_LDS_ROWS)
     if (lane < rows) {
 #pragma unroll
         for (int c = 0; c < C; ++c) g[lane * C + c] = v[c];
     }
-#else
-#pragma unroll
-    for (int c = 0; c < C; ++c) stage[lane * C + c] = v[c];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int doubles = rows * C, pieces = doubles >> 1;
-    const q_v2* sv = (const q_v2*)stage; q_v2* gv = (q_v2*)g;
-#pragma unroll
-    for (int k = 0; k < (C + 1) / 2; ++k) {
-        const int pc = lane + 64 * k;
-        if (pc < pieces) __builtin_nontemporal_store(sv[pc], &gv[pc]);
-    }
-    if ((doubles & 1) && lane == 0) __builtin_nontemporal_store(stage[doubles - 1], &g[doubles - 1]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    // the pieces are read before the slice is written again
-#endif
 }
 template <int C>
-__device__ __forceinline__ void wave_rows_load(double* stage, const int lane, const int rows, const double* g, double (&v)[C])
+__device__ __forceinline__ void wave_rows_load(const int lane, const int rows, const double* g, double (&v)[C])
 {
-#if !defined(GSF_QUERY_LDS_ROWS)
     const int r = lane < rows ? lane : rows - 1;
 #pragma unroll
     for (int c = 0; c < C; ++c) v[c] = g[r * C + c];
-#else
-    const int doubles = rows * C, pieces = doubles >> 1;
-    q_v2* sv = (q_v2*)stage; const q_v2* gv = (const q_v2*)g;
-#pragma unroll
-    for (int k = 0; k < (C + 1) / 2; ++k) {
-        const int pc = lane + 64 * k;
-        if (pc < pieces) sv[pc] = __builtin_nontemporal_load(&gv[pc]);
-    }
-    if ((doubles & 1) && lane == 0) stage[doubles - 1] = __builtin_nontemporal_load(&g[doubles - 1]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int r = lane < rows ? lane : rows - 1;
-#pragma unroll
-    for (int c = 0; c < C; ++c) v[c] = stage[r * C + c];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
 }
 
 template <bool POINTS>
@@ -145,7 +111,7 @@ __global__ __launch_bounds__(256) void query_kernel(const QueryArgs a)
     const double tau = a.q_t[m];
 
     double xin[3] = { 0.0, 0.0, 0.0 };
-    if (POINTS) wave_rows_load<3>(slice, lane, rows, a.x + m0 * 3, xin);
+    if (POINTS) wave_rows_load<3>(lane, rows, a.x + m0 * 3, xin);
 
     // ---- the query's track and its class
     const int64_t b_lo = wave_count_le(a.q_offsets, a.B + 1, m0, lane) - 1, b_hi = wave_count_le(a.q_offsets, a.B + 1, m0 + rows - 1, lane) - 1;
@@ -215,12 +181,12 @@ __global__ __launch_bounds__(256) void query_kernel(const QueryArgs a)
             if (!georef_point(pose, ext, Vec3{ xin[0], xin[1], xin[2] }, o)) flags |= Q_BAD_QUAT;
         }
         const double ov[3] = { o.x, o.y, o.z };
-        wave_rows_store<3>(slice, lane, rows, a.out_a + m0 * 3, ov);
+        wave_rows_store<3>(lane, rows, a.out_a + m0 * 3, ov);
     } else {
         const double pv[3] = { pose.p.x, pose.p.y, pose.p.z };
         const double qv[4] = { pose.q.x, pose.q.y, pose.q.z, pose.q.w };
-        wave_rows_store<3>(slice, lane, rows, a.out_a + m0 * 3, pv);
-        wave_rows_store<4>(slice, lane, rows, a.out_quat + m0 * 4, qv);
+        wave_rows_store<3>(lane, rows, a.out_a + m0 * 3, pv);
+        wave_rows_store<4>(lane, rows, a.out_quat + m0 * 4, qv);
     }
     if (lane < rows) {
         a.q_flags[m] = (uint8_t)flags;

@@ -178,9 +178,6 @@ struct WaveArgs {
     int64_t B, N;
     const int64_t* offsets;                       // ragged batches: trajectory b = rows offsets[b]..offsets[b+1] (else b*N.., N rows)
     FitRows rows;                                 // which rows feed the pipeline's fit (gsf_set_sim3_rows)
-#ifdef GSF_EXP_HYBRID
-    int32_t use_pv;                               // exp/gsf_ekf_wave_hybrid.hip only (`make hybrid`): run-time choice of the variance source
-#endif
 };
 
 __device__ __forceinline__ int64_t uniform64(int64_t v)
@@ -231,16 +228,6 @@ __device__ __forceinline__ int32_t* gsf_stamp_buf() { __shared__ int32_t buf[64]
 #define GSF_STAMP_HEAD(c0_)                                              // (no tokens at all: the other builds compile to what they always did)
 #endif
 
-// The early-variance build's table (gsf_ekf_wave_early.hip) under AXMODE 1: the y rows repeat x -- neither written nor read, x copied in
-// registers (1), or written and read as the two-wave kernel's helper has them (0, the A/B form; HISTORY.md, "Early head")
-#ifndef GSF_EARLY_SKIP_Y
-#define GSF_EARLY_SKIP_Y 1
-#endif
-
-#ifndef GSF_WIDE_STORES
-#define GSF_WIDE_STORES 1                                                 // big-batch builds store whole output slabs through LDS (see the chunk loop's store site)
-#endif
-
 struct ChunkIn { double t; Vec3 p; Quat q; Vec3 z; uint32_t v; };
 
 // pose i of one trajectory (clamped to the last pose for the idle lanes of the final chunk): one contiguous slab per array
@@ -277,9 +264,6 @@ __device__ __forceinline__ void chunk_arrived(const ChunkIn& c)
 // chunk is consumed and every lane picks its row up from there.  Stamps and mask bytes are contiguous per lane already.  Pieces past the
 // end of a short last chunk are clamped onto its last 16 bytes (same bytes written to the same LDS place twice), idle lanes read the
 // last row -- what the per-lane loads' clamping did.  Same values in the same registers afterwards: bit-identical results.
-#ifndef GSF_WIDE_LOADS
-#define GSF_WIDE_LOADS 1
-#endif
 typedef double gsf_v2 __attribute__((ext_vector_type(2), aligned(8)));
 struct ChunkWide { double t; gsf_v2 P[2], Q[2], Z[2]; uint32_t v; };
 __device__ __forceinline__ int wide_piece_off(const int piece, const int slab_bytes) { const int o = piece * 16; return o < slab_bytes - 16 ? o : slab_bytes - 16; }
@@ -336,8 +320,7 @@ __device__ __forceinline__ ChunkIn unpack_chunk(const ChunkWide& w, double* stag
     return c;
 }
 template <bool WIDE> struct NextChunk { typedef ChunkIn type; };
-template <> struct NextChunk<true> { typedef ChunkWide type; };
-#define GSF_WIDE(SMALLBATCH_) (GSF_WIDE_LOADS && !(SMALLBATCH_))
+template <> struct NextChunk<true> { typedef ChunkWide type; };          // (WIDE = !SMALLBATCH: whole slabs in and out in the big-batch builds)
 
 // Second half of the fused fit: wave totals of the per-lane partial moments (shifted by as_ / bs_), Umeyama closed form, R/t/s
 // outputs, Sim3 of pose 0 (ref :439-451, :464-466).  Returns false -- after writing NaN rows and the status word -- when the fit
@@ -363,11 +346,7 @@ __device__ __forceinline__ bool fit_from_partials(const WaveArgs& a, const int64
         for (int k = 0; k < 9; ++k) H[k] = S.v[7 + k] - n * ma[k / 3] * mb[k % 3];
         const double sc[3] = { as_[0] + ma[0], as_[1] + ma[1], as_[2] + ma[2] }, dc[3] = { bs_[0] + mb[0], bs_[1] + mb[1], bs_[2] + mb[2] };
         GSF_STAMP(3);
-#ifdef GSF_FIT_SVD                                                        // A/B build (make ab): the Jacobi SVD route
-        fit = umeyama_finalize<false>(H, ssq, sc, dc, n, Rb, tb, sb);
-#else
         fit = umeyama_finalize<true>(H, ssq, sc, dc, n, Rb, tb, sb);     // every lane redundantly (wave-uniform inputs)
-#endif
         GSF_STAMP(4);
     }
     Quat qn0; const bool q0ok = quat_unit(qraw0, qn0);
@@ -670,11 +649,7 @@ __device__ __forceinline__ bool wave_prelude(const WaveArgs& a, const int64_t b,
         constexpr int MOM_ROUND = 6;
         // ONE closed form behind either moments pass (the two row rules differ in which rows they sum, not in what happens to the sums)
         double sums[17], bs_[3]; int32_t rows_flag = 0;
-#ifdef GSF_NO_ROWS_RULE                                                    // A/B build (make norows): what the row-choice pass costs the OTHER path by being there
-        if (false) {
-#else
         if (a.rows.mode != 0) {                                           // wave-uniform: the reference's row choice (ref :973-998)
-#endif
             fit_moments_reference_rows<GSF_ROWS_ROUND, PRE>(a, b, base, N, lane, as0, as1, as2, sums, bs_, rows_flag,
                                                             (const RoundRows<GSF_ROWS_ROUND>*)pre, miss_out);   // (PRE: GSF_ROWS_ROUND is 6, checked by the caller)
         } else {
@@ -930,69 +905,6 @@ template <> struct RingStore<0> {
     static __device__ __forceinline__ double (*get(int, double* ext))[6][64] { return (double (*)[6][64])ext; }
 };
 
-// The ROWS part of a chunk's head in wave_serial_chunks: what its 64 poses need from the chunk's rows (in: t, p, q, z, the mask byte) and
-// from the carried ROWS (c_t, c_po, c_ok, c_prev_avail) alone -- neither the state (cp, cq, Cq) nor a variance:
-//   - calculate_relative_pose (ref :77-92) against the previous lane / the carry: the unit quaternion, the previous stamp and position.
-//     (The previous pose's unit quaternion is only needed on the cold paths -- generic orientation, sharp-turn pairs -- and the cross-lane
-//     move cannot be sunk there by the compiler: it is fetched inside those wave-uniform branches.)
-//   - both_m: pose i-1 and pose i both have a valid quaternion; dt (ref :865).
-//   - telescope, the fast path (every quaternion of the chunk and the carried one valid -- the normal case): the increments telescope,
-//       dq_first * ... * dq_i = conj(r_carry) * r_i   and   R(q_{i-1}) R(r_{i-1})^-1 = R(Cq),  Cq = q_carry * conj(r_carry),
-//     so the orientation needs no scan and the predicted displacement is ONE rotation by the wave-uniform Cq (identical up to rounding:
-//     r conj(r) = 1 to 1 ulp for unit r).  Any invalid quaternion -> the generic path -- calculate_relative_pose per pose + a quaternion
-//     prefix product -- which sits in ONE block further down, so that the usual chunk runs from the loads to the scans without a branch.
-//   - the GNSS gate (ref :867-869) and the outage structure of the chunk, as masks: avail_m, the fix of pose i is used; av_m, the "gnss
-//     available" flag of pose i (pose 0: raw mask, :848); ap_m, the flag of pose i-1 (lane 0: the carry; pose 0: true); start_mask, an
-//     outage begins at this pose (ref :875-877; pose 0: :861); rec_mask (ref :879); pair_mask, poses i-1 and i both inside the outage.
-// The statements are held ONCE, as text, for two users that must form the same values with the same operations in the same order:
-// chunk_body() expands them where they always stood, and chunk_head_rows() below forms them for a caller that has a chunk's rows in
-// registers ahead of the chunk loop (gsf_ekf_wave_early.hip: chunk 0, beside the fit's closed form).  A function called from chunk_body()
-// was tried first and changed what the other builds compile to (HISTORY.md, "Early head"); the text expanded in place cannot.
-#define GSF_CHUNK_HEAD_ROWS                                                                      \
-    const u64 vraw_m = __ballot(in.v != 0);                                                      \
-    Quat r; const bool ok = quat_unit(q, r);                                                     \
-    const double t_pr = prev_lane(c_t, t);                                                       \
-    const Vec3 p_pr{ prev_lane(c_po.x, p.x), prev_lane(c_po.y, p.y), prev_lane(c_po.z, p.z) };   \
-    const u64 ok_mask = __ballot(ok);                                                            \
-    const u64 both_m = ((ok_mask << 1) | (c_ok ? 1ull : 0ull)) & ok_mask;                        \
-    const bool both_ok = __builtin_amdgcn_inverse_ballot_w64(both_m);                            \
-    const double dt = fmax(1e-6, t - t_pr);                                                      \
-    const bool telescope = c_ok && ((ok_mask & act_mask) == act_mask);                           \
-    const u64 zfin_m = __ballot(!(isnan(z.x) || isnan(z.y) || isnan(z.z)));                      \
-    const u64 avail_m = step_m & vraw_m & zfin_m;                                                \
-    const bool avail = __builtin_amdgcn_inverse_ballot_w64(avail_m);                             \
-    const u64 av_m = (init_m & vraw_m) | avail_m;                                                \
-    const bool av = __builtin_amdgcn_inverse_ballot_w64(av_m);                                   \
-    const u64 a_mask = act_mask & av_m;                                                          \
-    const u64 ap_m = (a_mask << 1) | ((c0 == 0 || c_prev_avail) ? 1ull : 0ull);                  \
-    const u64 start_mask = act_mask & ~av_m & ap_m;                                              \
-    const u64 rec_mask = step_m & av_m & ~ap_m;                                                  \
-    const u64 pair_mask = step_m & ~av_m & ~ap_m;                                                \
-    const bool recovers = __builtin_amdgcn_inverse_ballot_w64(rec_mask);                         \
-    const bool outpair = __builtin_amdgcn_inverse_ballot_w64(pair_mask);                         \
-    status |= (start_mask != 0ull) ? ST_HAD_OUTAGE : 0;
-
-// The values of GSF_CHUNK_HEAD_ROWS for the chunk `in` whose first pose is c0, formed AHEAD of the chunk loop.  Nothing is handed over:
-// chunk_body() expands the same statements on the same operands, and the compiler's value numbering finds them formed already -- the
-// loop is the one every build runs, so the early values cannot change a result.  chunk_head_pin() after the code they are to be
-// interleaved with keeps them formed in front of it (not sunk back to their first use in the loop).
-struct ChunkHeadRows { Quat r; double t_pr; Vec3 p_pr; double dt; u64 ok_mask, both_m, avail_m, av_m, start_mask, rec_mask, pair_mask; bool telescope; };
-__device__ __forceinline__ ChunkHeadRows chunk_head_rows(const ChunkIn& in, const u64 act_mask, const u64 init_m, const u64 step_m, const int64_t c0,
-                                                         const double c_t, const Vec3& c_po, const bool c_ok, const bool c_prev_avail)
-{
-    const double t = in.t;
-    const Vec3 p = in.p; const Quat q = in.q; const Vec3 z = in.z;
-    int32_t status = 0;                                                  // (the loop's own expansion sets the flag)
-    GSF_CHUNK_HEAD_ROWS
-    (void)status; (void)both_ok; (void)avail; (void)av; (void)recovers; (void)outpair;   // (lane predicates: register copies of the masks, formed again at their use)
-    return ChunkHeadRows{ r, t_pr, p_pr, dt, ok_mask, both_m, avail_m, av_m, start_mask, rec_mask, pair_mask, telescope };
-}
-__device__ __forceinline__ void chunk_head_pin(const ChunkHeadRows& h)
-{
-    asm volatile("" :: "v"(h.r.x), "v"(h.r.y), "v"(h.r.z), "v"(h.r.w), "v"(h.p_pr.x), "v"(h.p_pr.y), "v"(h.p_pr.z), "v"(h.dt),
-                       "s"(h.ok_mask), "s"(h.both_m), "s"(h.avail_m), "s"(h.av_m), "s"(h.start_mask), "s"(h.rec_mask), "s"(h.pair_mask));
-}
-
 // The chunk loop of the wave-per-trajectory filter, entered with the initial pose (p0, q0) and the first 64 poses already requested
 // (nxt).  Split from the prelude so that a kernel with its own fit / initial-pose logic can fall back to it (gsf_ekf_lat.hip).
 // AXMODE 1: the caller has checked on the host that axes x and y share (P0, Q, R) and z does not -- the default CONFIG -- so the
@@ -1003,22 +915,23 @@ __device__ __forceinline__ void chunk_head_pin(const ChunkHeadRows& h)
 // guarantees that N is a multiple of 64.
 // PVCHUNKS (early-variance build, gsf_ekf_wave_early.hip): only the first PVCHUNKS chunks -- full ones -- take their variances from the
 // table, the chunks behind them run their scans; 0: PREVAR holds for every chunk.
-// REGCHUNKS (early-variance build, GSF_EARLY_REGROWS): the track has exactly REGCHUNKS chunks and the caller holds the stamp, mask byte,
+// REGCHUNKS (the same build): the track has exactly REGCHUNKS chunks and the caller holds the stamp, mask byte,
 // SLAM position and fix of every one of them in registers (regrows, as its burst left them: idle lanes of a short last chunk hold the
 // last row, load_chunk's clamp).  The chunks then run as REGCHUNKS straight-line instances of the body with c0 a constant; chunk k hands
-// chunk k + 1 those registers and requests its quaternion alone; the last chunk requests nothing.  (REGQUATS: the quaternions are in the
-// caller's registers too, regquats[k], and no chunk requests anything.)  0: the loops below, as every other build runs them.
+// chunk k + 1 those registers and requests its quaternion alone; the last chunk requests nothing.  0: the loops below, as every other
+// build runs them.
 template <bool V> struct FromTable { static constexpr bool value = V; static constexpr int regk = -1; };
 template <bool V, int K> struct FromTableRegs { static constexpr bool value = V; static constexpr int regk = K; };   // chunk K of a REGCHUNKS build
-template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6, int PVCHUNKS = 0, int REGCHUNKS = 0, bool REGQUATS = false>
+template <bool PIPELINE, bool PREVAR = false, bool SMALLBATCH = false, int RINGS = 1, int AXMODE = 0, int TAILNS = 6, int PVCHUNKS = 0, int REGCHUNKS = 0>
 __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfConfig& cfg, const int64_t b, const int lane, const int64_t base,
                                                    const int64_t N, const Vec3& p0, const Quat& q0, const int32_t fit,
-                                                   typename NextChunk<GSF_WIDE(SMALLBATCH)>::type nxt,
+                                                   typename NextChunk<!SMALLBATCH>::type nxt,
                                                    const double* pv = nullptr, const int pv_stride = 0, const int ring_slot = 0,
-                                                   double* ext_ring = nullptr, const RoundRows<GSF_ROWS_ROUND>* regrows = nullptr, const Quat* regquats = nullptr)
+                                                   double* ext_ring = nullptr, const RoundRows<GSF_ROWS_ROUND>* regrows = nullptr)
 {
-    static_assert(REGCHUNKS == 0 || (!GSF_WIDE(SMALLBATCH) && PVCHUNKS > 0 && PVCHUNKS < REGCHUNKS && REGCHUNKS <= GSF_ROWS_ROUND),
+    static_assert(REGCHUNKS == 0 || (SMALLBATCH && PVCHUNKS > 0 && PVCHUNKS < REGCHUNKS && REGCHUNKS <= GSF_ROWS_ROUND),
                   "rows from registers: the early-variance build's per-lane rows, one round of them");
+    static_assert(PVCHUNKS == 0 || REGCHUNKS > 0, "a table for the first chunks only: the early-variance build, whose chunks are straight-line instances");
     const double* __restrict__ tsb = a.ts + base;
     const double* __restrict__ posb = a.pos + base * 3;
     const double* __restrict__ quatb = a.quat + base * 4;
@@ -1048,7 +961,7 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
     // "previous original pose" of pose 0 is pose 0 itself (ref :858): taken from lane 0 of the chunk that has just arrived
     bool c_prev_avail = __builtin_amdgcn_readlane((int)nxt.v, 0) != 0;   // ref :848 (raw mask)
     Vec3 c_po; Quat c_q0;
-    if constexpr (GSF_WIDE(SMALLBATCH)) {
+    if constexpr (!SMALLBATCH) {
         // (the slab pieces hold pose 0 across lanes 0 and 1; these wave-uniform rows come through the scalar cache instead, other waves
         // cover the round trip in the big-batch build)
         c_po = Vec3{ posb[0], posb[1], posb[2] };
@@ -1083,7 +996,7 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         // ---- this chunk's poses were loaded one iteration ago; issue the loads of the NEXT 64 poses now so that their
         // latency overlaps the scans below (the mask byte is compared at use time, never at load time)
         ChunkIn in;
-        if constexpr (GSF_WIDE(SMALLBATCH)) {
+        if constexpr (!SMALLBATCH) {
             in = unpack_chunk(nxt, wave_stage(), lane, L);
             nxt = load_chunk_wide(tsb, posb, quatb, gpsb, valb, c0 + 64, lane, N);
         } else if constexpr (decltype(pv_tag)::regk >= 0) {
@@ -1092,13 +1005,12 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
             constexpr int KN = decltype(pv_tag)::regk + 1;
             in = nxt;
             if constexpr (KN < REGCHUNKS) {
-                [[maybe_unused]] const int iq = 64 * KN + lane, ilq = (KN < REGCHUNKS - 1 || iq < (int)N) ? iq : (int)N - 1;
+                const int iq = 64 * KN + lane, ilq = (KN < REGCHUNKS - 1 || iq < (int)N) ? iq : (int)N - 1;
                 nxt.t = regrows->pt[KN]; nxt.v = regrows->pv[KN];
                 nxt.p = Vec3{ regrows->pa[KN][0], regrows->pa[KN][1], regrows->pa[KN][2] };
                 nxt.z = Vec3{ regrows->pz[KN][0], regrows->pz[KN][1], regrows->pz[KN][2] };
-                if constexpr (REGQUATS) nxt.q = regquats[KN];             // (A/B form: the caller's burst requested every chunk's quaternion as well)
-                else nxt.q = Quat{ __builtin_nontemporal_load(&quatb[ilq * 4]), __builtin_nontemporal_load(&quatb[ilq * 4 + 1]),
-                                   __builtin_nontemporal_load(&quatb[ilq * 4 + 2]), __builtin_nontemporal_load(&quatb[ilq * 4 + 3]) };
+                nxt.q = Quat{ __builtin_nontemporal_load(&quatb[ilq * 4]), __builtin_nontemporal_load(&quatb[ilq * 4 + 1]),
+                              __builtin_nontemporal_load(&quatb[ilq * 4 + 2]), __builtin_nontemporal_load(&quatb[ilq * 4 + 3]) };
             }
         } else {
             in = nxt;
@@ -1106,7 +1018,42 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         }
         const double t = in.t;
         const Vec3 p = in.p; const Quat q = in.q; const Vec3 z = in.z;
-        GSF_CHUNK_HEAD_ROWS                                              // (the rows part of the head: the text above wave_serial_chunks)
+        // ---- the ROWS part of the chunk's head: what its 64 poses need from the chunk's rows (in: t, p, q, z, the mask byte) and
+        // from the carried ROWS (c_t, c_po, c_ok, c_prev_avail) alone -- neither the state (cp, cq, Cq) nor a variance:
+        //   - calculate_relative_pose (ref :77-92) against the previous lane / the carry: the unit quaternion, the previous stamp and position.
+        //     (The previous pose's unit quaternion is only needed on the cold paths -- generic orientation, sharp-turn pairs -- and the cross-lane
+        //     move cannot be sunk there by the compiler: it is fetched inside those wave-uniform branches.)
+        //   - both_m: pose i-1 and pose i both have a valid quaternion; dt (ref :865).
+        //   - telescope, the fast path (every quaternion of the chunk and the carried one valid -- the normal case): the increments telescope,
+        //       dq_first * ... * dq_i = conj(r_carry) * r_i   and   R(q_{i-1}) R(r_{i-1})^-1 = R(Cq),  Cq = q_carry * conj(r_carry),
+        //     so the orientation needs no scan and the predicted displacement is ONE rotation by the wave-uniform Cq (identical up to rounding:
+        //     r conj(r) = 1 to 1 ulp for unit r).  Any invalid quaternion -> the generic path -- calculate_relative_pose per pose + a quaternion
+        //     prefix product -- which sits in ONE block further down, so that the usual chunk runs from the loads to the scans without a branch.
+        //   - the GNSS gate (ref :867-869) and the outage structure of the chunk, as masks: avail_m, the fix of pose i is used; av_m, the "gnss
+        //     available" flag of pose i (pose 0: raw mask, :848); ap_m, the flag of pose i-1 (lane 0: the carry; pose 0: true); start_mask, an
+        //     outage begins at this pose (ref :875-877; pose 0: :861); rec_mask (ref :879); pair_mask, poses i-1 and i both inside the outage.
+        const u64 vraw_m = __ballot(in.v != 0);
+        Quat r; const bool ok = quat_unit(q, r);
+        const double t_pr = prev_lane(c_t, t);
+        const Vec3 p_pr{ prev_lane(c_po.x, p.x), prev_lane(c_po.y, p.y), prev_lane(c_po.z, p.z) };
+        const u64 ok_mask = __ballot(ok);
+        const u64 both_m = ((ok_mask << 1) | (c_ok ? 1ull : 0ull)) & ok_mask;
+        const bool both_ok = __builtin_amdgcn_inverse_ballot_w64(both_m);
+        const double dt = fmax(1e-6, t - t_pr);
+        const bool telescope = c_ok && ((ok_mask & act_mask) == act_mask);
+        const u64 zfin_m = __ballot(!(isnan(z.x) || isnan(z.y) || isnan(z.z)));
+        const u64 avail_m = step_m & vraw_m & zfin_m;
+        const bool avail = __builtin_amdgcn_inverse_ballot_w64(avail_m);
+        const u64 av_m = (init_m & vraw_m) | avail_m;
+        const bool av = __builtin_amdgcn_inverse_ballot_w64(av_m);
+        const u64 a_mask = act_mask & av_m;
+        const u64 ap_m = (a_mask << 1) | ((c0 == 0 || c_prev_avail) ? 1ull : 0ull);
+        const u64 start_mask = act_mask & ~av_m & ap_m;
+        const u64 rec_mask = step_m & av_m & ~ap_m;
+        const u64 pair_mask = step_m & ~av_m & ~ap_m;
+        const bool recovers = __builtin_amdgcn_inverse_ballot_w64(rec_mask);
+        const bool outpair = __builtin_amdgcn_inverse_ballot_w64(pair_mask);
+        status |= (start_mask != 0ull) ? ST_HAD_OUTAGE : 0;
         GSF_STAMP_HEAD(c0)
         // is_sharp_turn_in_segment (ref :808-826): pair (i-1, i) exceeds the yaw-rate threshold (or has a bad quaternion)
         u64 f_mask = 0ull;
@@ -1151,16 +1098,12 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
 
         // ---- variances (ref :712-713, :723-731): scanned here, or -- PREVAR -- already computed by the helper wave (LDS)
         double Pf[3], Pm[3], kg[3];
-#ifdef GSF_EXP_HYBRID
-        if (FROM_TABLE && (a).use_pv != 0) {
-#else
         if (FROM_TABLE) {
-#endif
             const int64_t il = active ? i : N - 1;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                // (the early-variance build's table has no y rows where y repeats x: GSF_EARLY_SKIP_Y)
-                if constexpr (GSF_EARLY_SKIP_Y && PVCHUNKS > 0 && AXMODE == 1) { if (c == 1) { Pf[1] = Pf[0]; Pm[1] = Pm[0]; kg[1] = kg[0]; continue; } }
+                // (the early-variance build's table has no y rows: under AXMODE 1 y repeats x)
+                if constexpr (PVCHUNKS > 0 && AXMODE == 1) { if (c == 1) { Pf[1] = Pf[0]; Pm[1] = Pm[0]; kg[1] = kg[0]; continue; } }
                 Pf[c] = pv[(c * 3 + 0) * pv_stride + il]; Pm[c] = pv[(c * 3 + 1) * pv_stride + il]; kg[c] = pv[(c * 3 + 2) * pv_stride + il];
             }
         } else {
@@ -1315,7 +1258,7 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         cP[0] = lane_bcast(Pf[0], L); cP[1] = lane_bcast(Pf[1], L); cP[2] = lane_bcast(Pf[2], L);
         c_po = lane_bcast(p, L); c_r = lane_bcast(r, L); c_ok = ((ok_mask >> L) & 1ull) != 0ull; c_t = lane_bcast(t, L);
         chunk_arrived(nxt);                                              // the next chunk's rows; then this chunk's stores
-        if (GSF_WIDE_STORES && !SMALLBATCH) {
+        if (!SMALLBATCH) {
             // Many waves per SIMD (C3-sized batches): the launch sits on the memory system under its mixed read + write stream, and
             // 8-byte stores at 24 / 32-byte stride leave L2 as incomplete lines (counter writes 1.11x the bytes).  The chunk's two output
             // slabs are contiguous (rows x 24 and rows x 32 bytes): the wave lays its rows out in LDS and stores the slabs as whole
@@ -1362,19 +1305,6 @@ __device__ __forceinline__ void wave_serial_chunks(const WaveArgs& a, const EkfC
         GSF_REG_CHUNK(0) GSF_REG_CHUNK(1) GSF_REG_CHUNK(2) GSF_REG_CHUNK(3) GSF_REG_CHUNK(4) GSF_REG_CHUNK(5)
 #undef GSF_REG_CHUNK
         static_assert(GSF_ROWS_ROUND <= 6, "one instance per chunk of the round");
-    } else if constexpr (PVCHUNKS > 0) {
-        // (the caller guarantees more than PVCHUNKS chunks: the chunks that read the table are full ones, the rest is the loop of the kernel without a table)
-        int64_t c0 = 0;
-#pragma nounroll
-        for (; c0 < 64 * PVCHUNKS; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<true>{}, c0, 63);
-        if constexpr (TAILNS == 6) {
-            for (; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<false>{}, c0, (int)((N - c0 < 64) ? (N - c0 - 1) : 63));
-        } else if constexpr (TAILNS == WAVE_TAIL_FULL) {
-            for (; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<false>{}, c0, 63);
-        } else {
-            for (; c0 + 64 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<false>{}, c0, 63);
-            chunk_body(ScanStages<TAILNS>{}, FromTable<false>{}, c0, (int)(N - c0 - 1));
-        }
     } else if constexpr (TAILNS == 6) {
         for (int64_t c0 = 0; c0 < N; c0 += 64) chunk_body(ScanStages<6>{}, FromTable<true>{}, c0, (int)((N - c0 < 64) ? (N - c0 - 1) : 63));
     } else if constexpr (TAILNS == WAVE_TAIL_FULL) {
@@ -1411,8 +1341,8 @@ __device__ __forceinline__ void wave_serial_body(const WaveArgs& a, const EkfCon
     const uint8_t* __restrict__ valb = a.valid + base;
 
     // the first 64 poses are requested before the prelude (fit / initial pose), whose latency then covers theirs
-    typename NextChunk<GSF_WIDE(SMALLBATCH)>::type nxt;
-    if constexpr (GSF_WIDE(SMALLBATCH)) nxt = load_chunk_wide(tsb, posb, quatb, gpsb, valb, 0, lane, N);
+    typename NextChunk<!SMALLBATCH>::type nxt;
+    if constexpr (!SMALLBATCH) nxt = load_chunk_wide(tsb, posb, quatb, gpsb, valb, 0, lane, N);
     else nxt = load_chunk(tsb, posb, quatb, gpsb, valb, lane, N);
     __builtin_amdgcn_sched_barrier(0);                                   // ... and stay requested HERE: nothing of the prelude is scheduled above them
     Vec3 p0; Quat q0; int32_t fit = 0;

@@ -1,9 +1,9 @@
-"""Chunk 0 of the early-variance build (csrc/gsf_ekf_wave_early.hip; GSF_CHUNK_HEAD_ROWS / chunk_head_rows() of csrc/gsf_wave_common.hpp).
+"""Chunk 0 of the early-variance build (csrc/gsf_ekf_wave_early.hip; the rows part of the head in chunk_body() of csrc/gsf_wave_common.hpp).
 
 Chunk 0 is the chunk the early-variance build treats differently from the one-wave kernel: its variances come from the table formed in
-the shadow of the input burst (without y rows where y repeats x: GSF_EARLY_SKIP_Y), and under -DGSF_EARLY_HEAD=1 the fit-independent rows
-part of its head -- unit quaternions, previous-lane moves, dt, the GNSS gate and the outage masks -- is formed ahead of the chunk loop,
-beside the fit's closed form.  The one-wave kernel (option 0) does all of it inside its chunk loop.  The claim is BITS: with
+the shadow of the input burst (without y rows where y repeats x), and the fit-independent rows part of its head -- unit quaternions,
+previous-lane moves, dt, the GNSS gate and the outage masks -- reads the registers that burst filled.  The one-wave kernel (option 0)
+scans the variances inside its chunk loop and loads the chunk's rows itself.  The claim is BITS: with
 "early_variances" at 1 and at 0 every byte of pos / quat / status / R / t / s is the same under both row rules, and option 1 agrees with
 the CPU oracle inside the tolerances tests/test_gpu_parity.py uses for the same outputs.
 

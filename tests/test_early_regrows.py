@@ -1,4 +1,4 @@
-"""The early-variance build's chunk sequence from registers (csrc/gsf_ekf_wave_early.hip, step 5; GSF_EARLY_REGROWS): the chunks of a track
+"""The early-variance build's chunk sequence from registers (csrc/gsf_ekf_wave_early.hip, step 5; REGCHUNKS of wave_serial_chunks): the chunks of a track
 run as straight-line instances of the one chunk body, and chunk k + 1 takes its stamp, mask byte, SLAM position and fix from the registers
 the input burst filled -- only its quaternion is requested again.  What can go wrong is a row in those registers that is not the row memory
 holds (the fall-back fit after a NaN under a set mask byte, the idle lanes of a short last chunk), a carry that a constant c0 or L folded

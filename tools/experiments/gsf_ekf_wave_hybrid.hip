@@ -1,4 +1,5 @@
-// exp/gsf_ekf_wave_hybrid.hip -- EXPERIMENT (`make hybrid` -> ../libgsf_hybrid.so): the fused pipeline at ONE wave per SIMD with a helper wave
+// gsf_ekf_wave_hybrid.hip -- REJECTED EXPERIMENT, kept for the record and compiled by nothing (README.md beside this file; it lived in
+// csrc/exp/ and a Makefile target `hybrid` linked it into a library of its own): the fused pipeline at ONE wave per SIMD with a helper wave
 // ONLY for the tracks that need it.  A launch of 1 000 tracks ends with its slowest wave, and the slowest waves are the tracks with a GNSS
 // outage (RTS patch, sharp-turn test, a fit on the first segment: +2.4 us).  The two-wave build (a helper wave
 // computes every chunk's variances while the main wave is in its fit: -28 % of a chunk's instructions) loses at 1 000 tracks because every
@@ -7,16 +8,16 @@
 // prelude (bounded wait, falls back to computing the variances itself): no barrier that a diverging decision could deadlock.
 // Same functions, same operands, same order: the bits of the one-wave kernel (51 parity tests green through this build).
 //
-// RESULT (round 4, same box, graph replay, 1 000 x 271; tools/experiments/hybrid_ab.sh, GSF_HYBRID_MODE): shipped one-wave kernel 18.4 us;
+// RESULT (round 4, same box, graph replay, 1 000 x 271; modes chosen with GSF_HYBRID_MODE): shipped one-wave kernel 18.4 us;
 // this kernel with the helper leaving at once (mode 0) or after its scan (mode 2) 19.2-19.5 us -- the two-wave blocks and the run-time choice
 // of the variance source cost every track a microsecond; with the helper working for the 134 outage tracks (mode 1) 24.0-24.6 us -- there is no
 // idle SIMD at 1 000 tracks, the helper shares one with some other track's main wave, finishes late and its own main wave waits for it; with
 // s_setprio(3) in the helper (mode 3) 20.1 us.  Two chunk loops inlined side by side instead of the run-time choice: 222 registers, 115 scalars
 // spilled into VGPR lanes, 24.1 us; the rare loop behind a call: 270 registers = one wave per SIMD, 34.3 us.  Not shipped.
 //
-// The run-time switch it needs in gsf_wave_common.hpp (`int32_t use_pv` as last member of WaveArgs, `PREVAR && a.use_pv` where
-// wave_serial_chunks chooses between the LDS variances and variance_chunk()) sits behind GSF_EXP_HYBRID, which only this file defines: the
-// shipped translation units compile the profiled sources unchanged.
+// The run-time switch it needed in gsf_wave_common.hpp (`int32_t use_pv` as last member of WaveArgs, `PREVAR && a.use_pv` where
+// wave_serial_chunks chooses between the LDS variances and variance_chunk()) sat behind GSF_EXP_HYBRID, which only this file defined; it
+// left the header with this file.
 #define GSF_EXP_HYBRID 1
 #include <cstdlib>
 #include "../gsf_wave_common.hpp"

@@ -6,8 +6,8 @@ general route).  Warm-up, then HIP events on torch's current stream, medians ove
 composition alternate inside one process.  Prints one JSON line per entry: ms, GB/s on the algorithmic bytes (georef 8 + 24 read, 24 + 1
 written = 57 B per point; poses 8 read, 56 + 1 written = 65 B per query; no optional output is asked for), the fraction of 8 TB/s, the same
 for the composition with the bytes it allocates beyond its inputs and outputs, and max |delta| between the two.
-GSF_LIBRARY=.../libgsf_query_lds_rows.so (make -C gps_optimize_slam_amd/csrc query_lds_rows) times the A/B build that moves the 24- / 32-byte
-rows as 16-byte pieces through LDS instead of row by row.
+GSF_LIBRARY=... times another build of the library (the form that moved the 24- / 32-byte rows as 16-byte pieces through LDS was measured
+this way and retired: tools/experiments/README.md).
 usage: python tools/pose_query_timing.py [reps] [log2 M]"""
 import json
 import os
