@@ -114,6 +114,11 @@ STREAM_LAG_MAX, STREAM_LAG_F64 = 512, 12                        # the largest la
 CLK_NONE, CLK_AT_EDGE, CLK_FLAT = 1, 2, 4                       # clk_status bits of gsf_clock_offset_search_dev
 QT_EMPTY, QT_UNSORTED, QT_SKIPPED, QT_BAD_EXTRINSIC = 1, 2, 4, 8    # track_state bits of gsf_pose_query_dev / gsf_georef_points_dev
 Q_EXACT, Q_BEFORE, Q_AFTER, Q_GAP, Q_NAN, Q_TRACK, Q_BAD_QUAT = 1, 2, 4, 8, 16, 32, 64      # ... and their q_flags bits
+TE_NEAREST, TE_INTERP = 0, 1                                    # assoc_mode of gsf_traj_eval_dev
+TE_ALIGN_NONE, TE_ALIGN_SE3, TE_ALIGN_SIM3 = 0, 1, 2            # ... its align_mode
+TE_FRAMES, TE_METRES, TE_SECONDS = 0, 1, 2                      # ... its rpe_kind values
+TE_MATCHED, TE_NO_TRUTH, TE_NAN, TE_BAD_QUAT, TE_TRACK = 1, 2, 4, 8, 16      # ... its pose_flags bits
+TE_TRACK_SKIPPED, TE_TRACK_EMPTY, TE_TRACK_UNSORTED, TE_TRACK_FEW, TE_TRACK_DEGENERATE = 1, 2, 4, 8, 16   # ... its track_state bits
 
 
 def library_path():
@@ -215,6 +220,7 @@ SIGNATURES = {
     "gsf_pose_query": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 6),
     "gsf_georef_points_dev": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 9),
     "gsf_georef_points": (C.c_int, [_vp] * 7 + [_i64, _vp, _vp, _i64, _f64] + [_vp] * 9),
+    "gsf_traj_eval_dev": (C.c_int, [_vp] * 5 + [_i64] + [_vp] * 5 + [_i64, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _i32] + [_vp] * 14),
     "gsf_utm_to_wgs84_rows_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gsf_tum_text_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "gsf_time_align_batch_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _vp, _vp, _vp]),

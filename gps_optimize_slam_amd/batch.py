@@ -2172,6 +2172,213 @@ def georef_fused(rb, r, pt_t, pt_xyz, pt_offsets, ext_q=None, ext_t=None, scale=
                                 zone=r.zone if wgs84 else None, south=r.south if wgs84 else None)
 
 
+# ---- trajectory evaluation against 6-DoF truth (gsf_traj_eval_dev) ----------------------------------------------------------------------------
+_TE_ALIGN = {"none": _lib.TE_ALIGN_NONE, "se3": _lib.TE_ALIGN_SE3, "sim3": _lib.TE_ALIGN_SIM3}
+_TE_ASSOC = {"nearest": _lib.TE_NEAREST, "interp": _lib.TE_INTERP}
+APE_STATS = ("n", "mean", "median", "rmse", "std", "min", "max", "sse")
+
+
+class RpeScenarios:
+    """K relative-error scenarios on the device: kind (K,) int32 of _lib.TE_FRAMES / TE_METRES / TE_SECONDS, value (K,) float64, stride (K,)
+    int64 (rpe_scenarios / kitti_scenarios build them)."""
+
+    def __init__(self, kind, value, stride):
+        self.kind, self.value, self.stride = kind, value, stride
+        self.K = int(kind.numel())
+        self.host = (kind.cpu().tolist(), value.cpu().tolist(), stride.cpu().tolist())
+
+
+def rpe_scenarios(frames=(), metres=(), seconds=(), stride=1, device="cuda"):
+    """Relative-error scenarios: one per delta, frames first, then metres, then seconds; stride = the step between first frames (an int, or
+    one per scenario).  Returns an RpeScenarios."""
+    kinds = [_lib.TE_FRAMES] * len(frames) + [_lib.TE_METRES] * len(metres) + [_lib.TE_SECONDS] * len(seconds)
+    values = [float(v) for v in tuple(frames) + tuple(metres) + tuple(seconds)]
+    strides = [int(stride)] * len(kinds) if isinstance(stride, int) else [int(v) for v in stride]
+    if len(strides) != len(kinds):
+        raise ValueError(f"rpe_scenarios: {len(kinds)} scenarios but {len(strides)} strides")
+    if any(v < 1 for v in strides):
+        raise ValueError("rpe_scenarios: a stride must be at least 1")
+    return RpeScenarios(torch.tensor(kinds, dtype=torch.int32, device=device), torch.tensor(values, dtype=torch.float64, device=device),
+                        torch.tensor(strides, dtype=torch.int64, device=device))
+
+
+def kitti_scenarios(device="cuda"):
+    """The KITTI odometry benchmark's segments: 100, 200, ... 800 m, a first frame every 10 poses."""
+    return rpe_scenarios(metres=tuple(100.0 * k for k in range(1, 9)), stride=10, device=device)
+
+
+class TrajectoryEval:
+    """What evaluate_trajectory_ragged returns.  Per track: R (B,9) / t (B,3) / s (B,) of the alignment, track_state (B,) int32 of
+    _lib.TE_TRACK_* bits.  Per pose: flags (P,) uint8 of _lib.TE_* bits, match_index (P,) int32, ape_t / ape_r (P,) (metres / radians, NaN
+    where the pose is not matched).  ape_stats (B,2,8): translation / rotation x APE_STATS.  rpe_n (B,K) int64 and rpe_sums (B,K,8) per
+    scenario; rpe_last (P,) int32 / rpe_t / rpe_r (P,) of the traced scenario, or None."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def ape(self, b):
+        """{'translation': {n, mean, ...}, 'rotation': {...}} of track b (one device -> host copy)"""
+        st = self.ape_stats[b].cpu().tolist()
+        return {"translation": dict(zip(APE_STATS, st[0])), "rotation": dict(zip(APE_STATS, st[1]))}
+
+    def ape_table(self):
+        """ape_stats on the host: (B,2,8) numpy, columns as APE_STATS"""
+        return self.ape_stats.cpu().numpy()
+
+    def rpe(self, k):
+        """scenario k per track: {'n' (B,) int64, 'mean_t', 'rmse_t', 'max_t', 'mean_r', 'rmse_r', 'max_r' (B,)}; NaN where a track has no pair"""
+        n, sm = self.rpe_n[:, k], self.rpe_sums[:, k]
+        nf = torch.where(n > 0, n.to(torch.float64), torch.full_like(sm[:, 0], float("nan")))
+        return {"n": n, "mean_t": sm[:, 0] / nf, "rmse_t": torch.sqrt(sm[:, 1] / nf), "max_t": torch.where(n > 0, sm[:, 2], nf),
+                "mean_r": sm[:, 3] / nf, "rmse_r": torch.sqrt(sm[:, 4] / nf), "max_r": torch.where(n > 0, sm[:, 5], nf)}
+
+    def kitti(self):
+        """KITTI's segment errors over every TE_METRES scenario: t_rel in percent = 100 sum(et / len) / n and r_rel in rad/m = sum(er / len) /
+        n, over all tracks and per track (t_rel_track / r_rel_track, NaN without a pair); a length with no pair contributes nothing."""
+        kinds = self.scenarios.host[0] if self.scenarios is not None else []
+        cols = [k for k, kind in enumerate(kinds) if kind == _lib.TE_METRES]
+        if not cols:
+            raise ValueError("TrajectoryEval.kitti: the evaluation has no scenario in metres")
+        n = self.rpe_n[:, cols].sum(dim=1)
+        st, sr = self.rpe_sums[:, cols, 6].sum(dim=1), self.rpe_sums[:, cols, 7].sum(dim=1)
+        nf = torch.where(n > 0, n.to(torch.float64), torch.full_like(st, float("nan")))
+        tot = int(n.sum())
+        return KittiErrors(t_rel=100.0 * float(st.sum()) / tot if tot else float("nan"), r_rel=float(sr.sum()) / tot if tot else float("nan"), n=tot,
+                           t_rel_track=100.0 * st / nf, r_rel_track=sr / nf, n_track=n)
+
+    def table(self):
+        """one text line per track: state, matched poses, APE rmse / median / max (m, deg)"""
+        import math
+        st, state = self.ape_table(), self.track_state.cpu().tolist()
+        lines = ["track state matched ape_t_rmse ape_t_median ape_t_max ape_r_rmse_deg ape_r_max_deg"]
+        for b, row in enumerate(st):
+            lines.append(f"{b} {state[b]} {int(row[0][0])} {row[0][3]:.4f} {row[0][2]:.4f} {row[0][6]:.4f} {math.degrees(row[1][3]):.4f} {math.degrees(row[1][6]):.4f}")
+        return "\n".join(lines)
+
+
+class KittiErrors:
+    """TrajectoryEval.kitti(): t_rel (percent), r_rel (rad/m), n pairs; the same per track as tensors."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def r_rel_deg_per_100m(self):
+        import math
+        return math.degrees(self.r_rel) * 100.0
+
+
+def evaluate_trajectory_ragged(ts, pos, quat, offsets, ref_ts, ref_pos, ref_quat, ref_offsets, align="se3", assoc="nearest", max_diff=0.01, rpe=None,
+                               trace=None, run_status=None, check_offsets=True):
+    """Grade B tracks against 6-DoF truth (gsf_traj_eval_dev): estimate ts (P,), pos (P,3), quat (P,4), offsets (B+1,) int64; truth ref_ts
+    (G,), ref_pos (G,3), ref_quat (G,4), ref_offsets (B+1,) int64.  assoc: "nearest" truth stamp within max_diff, or "interp" = the truth at
+    the estimate's stamp by the rule of query_poses_ragged (max_diff = the widest bracket).  align: "none", "se3" or "sim3" over the matched
+    pairs.  rpe: an RpeScenarios or None; trace: the scenario whose pairs are returned per first frame.  run_status (B,) int32: tracks with
+    run_status != 0 are not read.  check_offsets: both offsets arrays are copied to the host and checked (ascending, inside their arrays: the
+    kernels trust them), which waits for the stream; False for offsets already known to be good leaves the call asynchronous.  Returns a
+    TrajectoryEval."""
+    name = "evaluate_trajectory_ragged"
+    if align not in _TE_ALIGN:
+        raise ValueError(f"{name}: align must be one of {sorted(_TE_ALIGN)}, got {align!r}")
+    if assoc not in _TE_ASSOC:
+        raise ValueError(f"{name}: assoc must be one of {sorted(_TE_ASSOC)}, got {assoc!r}")
+    if not float(max_diff) == float(max_diff):
+        raise ValueError(f"{name}: max_diff is NaN")
+    B = _offsets_chk(offsets)
+    if _offsets_chk(ref_offsets) != B:
+        raise ValueError(f"{name}: offsets and ref_offsets must describe the same number of tracks")
+    P = int(ts.shape[0]) if ts.dim() == 1 else -1
+    G = int(ref_ts.shape[0]) if ref_ts.dim() == 1 else -1
+    _chk(ts, torch.float64, (P,), "ts"); _chk(pos, torch.float64, (P, 3), "pos"); _chk(quat, torch.float64, (P, 4), "quat")
+    _chk(ref_ts, torch.float64, (G,), "ref_ts"); _chk(ref_pos, torch.float64, (G, 3), "ref_pos"); _chk(ref_quat, torch.float64, (G, 4), "ref_quat")
+    if run_status is not None:
+        _chk(run_status, torch.int32, (B,), "run_status")
+    K = 0
+    if rpe is not None:
+        K = int(rpe.kind.numel()) if rpe.kind.dim() == 1 else -1
+        _chk(rpe.kind, torch.int32, (K,), "rpe.kind"); _chk(rpe.value, torch.float64, (K,), "rpe.value"); _chk(rpe.stride, torch.int64, (K,), "rpe.stride")
+    if trace is not None and not 0 <= int(trace) < K:
+        raise ValueError(f"{name}: trace = {trace} names none of the {K} scenarios")
+    for o, rows, what in ((offsets, P, "offsets"), (ref_offsets, G, "ref_offsets")) if check_offsets else ():
+        oh = o.cpu()
+        if int(oh[0]) < 0 or int(oh[-1]) > rows or bool((oh[1:] < oh[:-1]).any()):
+            raise ValueError(f"{name}: {what} must ascend from >= 0 to <= {rows}, the rows of its arrays")
+    dev = ts.device
+    f = dict(dtype=torch.float64, device=dev)
+    tr = trace is not None
+    r = TrajectoryEval(R=torch.empty((B, 9), **f), t=torch.empty((B, 3), **f), s=torch.empty((B,), **f),
+                       track_state=torch.empty((B,), dtype=torch.int32, device=dev), flags=torch.empty((P,), dtype=torch.uint8, device=dev),
+                       match_index=torch.empty((P,), dtype=torch.int32, device=dev), ape_t=torch.empty((P,), **f), ape_r=torch.empty((P,), **f),
+                       ape_stats=torch.empty((B, 2, 8), **f), rpe_n=torch.empty((B, K), dtype=torch.int64, device=dev),
+                       rpe_sums=torch.empty((B, K, 8), **f), rpe_last=torch.empty((P,), dtype=torch.int32, device=dev) if tr else None,
+                       rpe_t=torch.empty((P,), **f) if tr else None, rpe_r=torch.empty((P,), **f) if tr else None, scenarios=rpe,
+                       offsets=offsets, align=align, assoc=assoc)
+    if B == 0:
+        return r
+    ts_, pos_, quat_ = _unread_rows(ts, pos, quat)
+    rts_, rpos_, rquat_ = _unread_rows(ref_ts, ref_pos, ref_quat)
+    check(_lib.load().gsf_traj_eval_dev(context().handle, _p(ts_), _p(pos_), _p(quat_), _p(offsets), P, _p(rts_), _p(rpos_), _p(rquat_), _p(ref_offsets),
+                                        _p(run_status), B, _TE_ASSOC[assoc], float(max_diff), _TE_ALIGN[align], K,
+                                        _p(rpe.kind) if K else None, _p(rpe.value) if K else None, _p(rpe.stride) if K else None,
+                                        int(trace) if tr else -1, _p(r.R), _p(r.t), _p(r.s), _p(r.track_state), _p(r.flags), _p(r.match_index),
+                                        _p(r.ape_t), _p(r.ape_r), _p(r.ape_stats), _p(r.rpe_n) if K else None, _p(r.rpe_sums) if K else None,
+                                        _p(r.rpe_last), _p(r.rpe_t), _p(r.rpe_r)))
+    return r
+
+
+def evaluate_fused(rb, r, truth, **kw):
+    """Grade a run_fusion_ragged result against truth = (ref_ts, ref_pos, ref_quat, ref_offsets): the Sim3-aligned raw track (apply_sim3_batch
+    under r.R / r.t / r.s) and the fused track (r.fused), one evaluate_trajectory_ragged call each with the run's run_status; keyword arguments
+    go to both.  Returns (raw, fused), two TrajectoryEval."""
+    ref_ts, ref_pos, ref_quat, ref_offsets = truth
+    ts, pos, quat = rb.ts.reshape(-1), rb.pos.reshape(-1, 3), rb.quat.reshape(-1, 4)
+    sp, sq, _ = apply_sim3_batch(pos, quat, rb.slam_offsets, r.R, r.t, r.s)
+    kw.setdefault("run_status", r.run_status)
+    raw = evaluate_trajectory_ragged(ts, sp, sq, rb.slam_offsets, ref_ts, ref_pos, ref_quat, ref_offsets, **kw)
+    kw["check_offsets"] = False                                           # (the same offsets: checked by the first call, if at all)
+    fused = evaluate_trajectory_ragged(ts, r.fused.pos.reshape(-1, 3), r.fused.quat.reshape(-1, 4), rb.slam_offsets, ref_ts, ref_pos, ref_quat,
+                                       ref_offsets, **kw)
+    return raw, fused
+
+
+def read_kitti_poses(poses_path, times_path):
+    """A KITTI pose file (12 numbers a row: the 3x4 matrix [R | t], row-major) and its stamp file (one number a row) on the host, in NumPy:
+    -> {'timestamps' (n,), 'positions' (n,3), 'quaternions' (n,4)} with unit quaternions [x, y, z, w], w >= 0, by the branch on the largest
+    of the diagonal and the trace.  ValueError where the row counts differ or a row has another width, as kitti2tum.py refuses them."""
+    import numpy as np
+    try:
+        m, t = np.loadtxt(poses_path, dtype=np.float64, ndmin=2), np.loadtxt(times_path, dtype=np.float64, ndmin=2)
+    except OSError as e:
+        raise ValueError(f"read_kitti_poses: {e}")
+    if m.shape[1] != 12:
+        raise ValueError(f"read_kitti_poses: a KITTI pose row holds 12 numbers, {poses_path} has {m.shape[1]}")
+    if t.shape[1] != 1 or t.shape[0] != m.shape[0]:
+        raise ValueError("read_kitti_poses: the timestamp file must have one column of timestamps and the same number of rows as the pose file")
+    return {"timestamps": t[:, 0].copy(), "positions": np.ascontiguousarray(m[:, [3, 7, 11]]), "quaternions": kitti_rotations_to_quat(m)}
+
+
+def kitti_rotations_to_quat(m):
+    """(n,12) KITTI pose rows -> (n,4) unit quaternions [x, y, z, w] with w >= 0 (NumPy, host)"""
+    import numpy as np
+    R = np.asarray(m, np.float64).reshape(-1, 3, 4)[:, :, :3]
+    n = R.shape[0]
+    d = np.stack([R[:, 0, 0], R[:, 1, 1], R[:, 2, 2], R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2]], axis=1)
+    c = np.argmax(d, axis=1)
+    q = np.empty((n, 4))
+    for i in range(3):
+        j, k = (i + 1) % 3, (i + 2) % 3
+        sel = c == i
+        q[sel, i] = 1.0 - d[sel, 3] + 2.0 * R[sel, i, i]
+        q[sel, j] = R[sel, j, i] + R[sel, i, j]
+        q[sel, k] = R[sel, k, i] + R[sel, i, k]
+        q[sel, 3] = R[sel, k, j] - R[sel, j, k]
+    sel = c == 3
+    q[sel, 0], q[sel, 1], q[sel, 2], q[sel, 3] = R[sel, 2, 1] - R[sel, 1, 2], R[sel, 0, 2] - R[sel, 2, 0], R[sel, 1, 0] - R[sel, 0, 1], 1.0 + d[sel, 3]
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    q[q[:, 3] < 0] *= -1.0
+    return q
+
+
 # ---- streaming fusion: append poses to live tracks (gsf_stream_*) ----------------------------------------------------------------------------
 class StreamStep:
     """What FusionStream.append returns: pos (P,3) / quat (P,4) = the fused rows of this call's segments as they stand when the call ends,

@@ -887,6 +887,29 @@ def georeference_points(timestamps, positions, quaternions, point_times, points,
     return xyz, fl
 
 
+def evaluate_trajectory(est, truth, align="se3", assoc="nearest", max_diff=0.01, frames=(), metres=(), seconds=(), stride=1, trace=None):
+    """One track against 6-DoF truth (gsf_traj_eval_dev through batch.evaluate_trajectory_ragged): est and truth are dicts as
+    load_slam_trajectory returns them ('timestamps', 'positions', 'quaternions'; batch.read_kitti_poses gives the same for KITTI files).
+    Returns the TrajectoryEval of the one-track batch: .ape(0), .rpe(k), .kitti(), R / t / s, flags, ape_t, ape_r (device tensors)."""
+    import torch
+    from . import batch
+    arrays = []
+    for name, d in (("est", est), ("truth", truth)):
+        t = f64(d["timestamps"]).reshape(-1)
+        n = t.shape[0]
+        p, q = np.asarray(d["positions"], dtype=np.float64), np.asarray(d["quaternions"], dtype=np.float64)
+        if p.shape != (n, 3) or q.shape != (n, 4):
+            raise ValueError(f"evaluate_trajectory: {name} has {n} stamps, positions {p.shape} and quaternions {q.shape}")
+        arrays.append((t, f64(p), f64(q), n))
+    dev = lambda a: torch.as_tensor(a).cuda()
+    (t, p, q, n), (rt, rp, rq, g) = arrays
+    rpe = None
+    if len(frames) + len(metres) + len(seconds):
+        rpe = batch.rpe_scenarios(frames=frames, metres=metres, seconds=seconds, stride=stride)
+    return batch.evaluate_trajectory_ragged(dev(t), dev(p), dev(q), dev(np.array([0, n], dtype=np.int64)), dev(rt), dev(rp), dev(rq),
+                                            dev(np.array([0, g], dtype=np.int64)), align=align, assoc=assoc, max_diff=max_diff, rpe=rpe, trace=trace)
+
+
 # ---------------------------------------------------------------------------- helpers of the EKF surface (EKFGPSSLAM.py:77-105, :679-826)
 def calculate_relative_pose(pose1_pos, pose1_quat, pose2_pos, pose2_quat):
     """Relative motion pose1 -> pose2 in pose1's frame: (delta_pos_local (3,), delta_quat (4,)); an invalid (zero-norm)

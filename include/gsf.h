@@ -1162,6 +1162,85 @@ GSF_API int gsf_georef_points(gsf_ctx *ctx, const double *ts, const double *pos,
                               int64_t M, double max_gap, const double *x, const double *ext_q, const double *ext_t, const double *scale,
                               double *out_xyz, uint8_t *q_flags, int32_t *q_index, uint8_t *q_pose_flags, int32_t *track_state);
 
+/* ---- trajectory evaluation: absolute / relative pose error and KITTI's segment errors against 6-DoF truth ---------------------------------
+   gsf_eval_errors_batch_dev (step 6) grades positions against the GNSS fixes the filter was fed.  This entry grades whole poses against a
+   truth trajectory of its own (KITTI ground truth, a survey, a simulator), after an alignment, as evo and the KITTI devkit do.
+   Estimate: ts[P], pos[P][3], quat[P][4], offsets int64[B+1] as every ragged entry takes them; P (the rows of the per-pose arrays) is
+   passed by the host.  Truth per track: ref_ts[G], ref_pos[G][3], ref_quat[G][4], ref_offsets int64[B+1].  All indexing is int64; all
+   pointers are device pointers; the call is asynchronous on the context's stream.  Quaternions are [x, y, z, w].
+   Track state, track_state[B], GSF_TE_TRACK_* bits, 0 = evaluated:
+   - SKIPPED: run_status != NULL && run_status[b] != 0.  Neither the track's rows nor its truth are read; no other bit is set.
+   - EMPTY: the track has no poses or no truth poses.
+   - UNSORTED: ts[0] or ref_ts[0] of the track is NaN, or !(x[i] >= x[i-1]) inside either stamp array (a NaN stamp counts, as in
+     GSF_QT_UNSORTED).  Decided before anything is searched.
+   - FEW: align_mode is _SE3 / _SIM3 and fewer than 3 poses are matched.   - DEGENERATE: the closed form returns GSF_SIM3_NONE.
+   Any bit: R, t, s of the track are NaN, ape_t / ape_r of its poses are NaN, ape_stats holds n = 0 and NaN, rpe_n = 0 with zero sums.
+   Under SKIPPED / EMPTY / UNSORTED every pose has pose_flags GSF_TE_TRACK and match_index -1; under FEW / DEGENERATE pose_flags and
+   match_index keep what the association found.
+   Association, per estimate pose i of a usable track (checked in this order; the first failure is the flag, the per-pose outputs are NaN
+   and match_index is -1):
+   - the position holds a NaN or an infinity: GSF_TE_NAN;   - the quaternion's norm is 0, NaN or infinite: GSF_TE_BAD_QUAT;
+   - GSF_TE_NEAREST: the truth pose j with the smallest |ref_ts[j] - ts[i]|, on a tie the earlier j, among equal truth stamps the first;
+     matched when that difference is <= max_diff, else GSF_TE_NO_TRUTH.  Two estimate poses may match the same truth pose; both are kept.
+     match_index = j, relative to the track's first truth pose.
+   - GSF_TE_INTERP: the truth pose at ts[i] by the rule of gsf_pose_query_dev with max_gap = max_diff (position linear, orientation
+     quaternion_nlerp, an exact stamp is that pose bit for bit); before the first / after the last truth stamp or across a bracket wider
+     than max_diff (> 0): GSF_TE_NO_TRUTH.  match_index = the bracket's i.
+   - the truth position holds a NaN or an infinity: GSF_TE_NAN;   the truth quaternion cannot be normalised: GSF_TE_BAD_QUAT;
+   - else GSF_TE_MATCHED.  Both quaternions of the pair are normalised once.
+   Alignment over the matched pairs (src = estimate, dst = truth): GSF_TE_ALIGN_NONE: identity, s = 1.  _SIM3: centroids, centred moments,
+   the Umeyama closed form by its SVD route (compute_sim3_transform, EKFGPSSLAM.py:436-451, scale rules included).  _SE3: that rotation,
+   s = 1, t = dc - R sc.  The aligned estimate is p' = s R p + t, q' = q_R (x) q (transform_trajectory, :461-468).
+   Absolute errors per matched pose: ape_t = |p' - g|; ape_r = the angle of conj(q_g) (x) q' as 2 atan2(|v|, |w|), radians in [0, pi].
+   ape_stats[B][2][8] (0: translation, 1: rotation) = {n, mean, median, rmse, std, min, max, sse} of the track's matched poses, evo's
+   statistics: std is np.std (ddof 0) in two passes; median (the mean of the two middle values for an even n), min and max are exact order
+   statistics of the per-pose values returned.
+   Relative errors: K >= 0 scenarios (rpe_kind[K], rpe_value[K], rpe_stride int64[K]) over the matched poses m = 0 .. M-1 of a track, in
+   order; d[m] = the truth path length over matched poses.  First frames f = 0, stride, 2 stride, ... (stride < 1: no pair); last frame:
+   - GSF_TE_FRAMES: l = f + (int64) value (value < 1: no pair);
+   - GSF_TE_METRES: the smallest l > f with d[l] > d[f] + value (KITTI's lastFrameFromSegmentLength);
+   - GSF_TE_SECONDS: the smallest l > f with ts[l] >= ts[f] + value;   no such l < M: no pair.
+   Pair error E = (g_f^-1 g_l)^-1 (e'_f^-1 e'_l): et = |E.t|, er = the angle of E.R (the same atan2 form).
+   rpe_n int64[B][K] = pairs; rpe_sums[B][K][8] = {sum et, sum et^2, max et, sum er, sum er^2, max er, sum et / value, sum er / value}; the
+   last two for GSF_TE_METRES only, NaN otherwise; no pair: zeros.  Sums are reduced in a fixed order: a track's results do not depend on
+   the other tracks or scenarios of the call.  With 0 <= trace_k < K the optional outputs (each may be NULL; rpe_t / rpe_r are written only
+   with rpe_last) hold, at the estimate row of every first frame of scenario trace_k that has a pair, rpe_last = the estimate row of l
+   relative to the track's first pose, rpe_t = et, rpe_r = er; every other row is -1 / NaN.
+   K == 0: the scenario arrays may be NULL.  B == 0: nothing is done, GSF_OK.  Three launches (association; alignment, absolute errors and
+   statistics; scenarios -- not launched for K == 0); scratch (16 doubles and one int32 a pose = 132 bytes, 8 bytes a
+   track, 8 bytes) from the context's kernel workspace.
+   Input range: positions whose differences, and whose products with s R, stay below 1e150 in magnitude, so that no square overflows.
+   Beyond it a matched pose's error can come out infinite or NaN; a NaN error is left out of the sums, min, max and median of ape_stats
+   while n still counts the pose, and moments that overflow give GSF_TE_TRACK_DEGENERATE -- in range the closed form's SVD route
+   always returns a fit (a collinear or a single-point cloud included), so DEGENERATE marks exactly that overflow. */
+#define GSF_TE_NEAREST 0
+#define GSF_TE_INTERP 1
+#define GSF_TE_ALIGN_NONE 0
+#define GSF_TE_ALIGN_SE3 1
+#define GSF_TE_ALIGN_SIM3 2
+#define GSF_TE_FRAMES 0
+#define GSF_TE_METRES 1
+#define GSF_TE_SECONDS 2
+#define GSF_TE_MATCHED 1
+#define GSF_TE_NO_TRUTH 2
+#define GSF_TE_NAN 4
+#define GSF_TE_BAD_QUAT 8
+#define GSF_TE_TRACK 16
+#define GSF_TE_TRACK_SKIPPED 1
+#define GSF_TE_TRACK_EMPTY 2
+#define GSF_TE_TRACK_UNSORTED 4
+#define GSF_TE_TRACK_FEW 8
+#define GSF_TE_TRACK_DEGENERATE 16
+/* Out: R[B][9] row-major, t[B][3], s[B], track_state[B], pose_flags uint8[P], match_index int32[P], ape_t[P], ape_r[P],
+   ape_stats[B][2][8], rpe_n int64[B][K], rpe_sums[B][K][8]; optional rpe_last int32[P], rpe_t[P], rpe_r[P]. */
+GSF_API int gsf_traj_eval_dev(gsf_ctx *ctx, const double *ts, const double *pos, const double *quat, const int64_t *offsets, int64_t P,
+                              const double *ref_ts, const double *ref_pos, const double *ref_quat, const int64_t *ref_offsets,
+                              const int32_t *run_status, int64_t B, int32_t assoc_mode, double max_diff, int32_t align_mode, int32_t K,
+                              const int32_t *rpe_kind, const double *rpe_value, const int64_t *rpe_stride, int32_t trace_k, double *R,
+                              double *t, double *s, int32_t *track_state, uint8_t *pose_flags, int32_t *match_index, double *ape_t,
+                              double *ape_r, double *ape_stats, int64_t *rpe_n, double *rpe_sums, int32_t *rpe_last, double *rpe_t,
+                              double *rpe_r);
+
 /* ---- step 7 of main_process_gui (EKFGPSSLAM.py:1085-1104): the corrected track as WGS84 rows and as the bytes of its TUM files ------------
    Rows are flat over P poses with offsets int64[B+1], as in gsf_run_fusion_ragged_dev; any offsets work (a dense batch: b * N). */
 /* Rows [E, N, alt] (pos[P][3]) -> rows [lon deg, lat deg, alt] (lonlatalt[P][3]): utm_to_wgs84(corrected_pos, projector) (:1097, :291-296),
